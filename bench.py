@@ -20,6 +20,10 @@ chain x = f^-1(z) in one launch), the roofline of the step's dominant kernel, th
 the default single-GPU run - `other_workloads`: BASELINE.json's other configs (cfg 3 GAS, cfg 5 MINIBOONE,
 the d = 100 lane of cfg 4 and cfg 4's two-lane conditional model) timed the same way, each with its
 dominant kernel's roofline and an NLL cross-check against the CPU oracle.
+
+--dump-outputs DIR: right after the headline's timed region, rank 0 writes what the last timed step handed its caller
+(see dump_outputs) as DIR/<name>.npy.  Weights, batch, permutations and the in-kernel noise stream are all seeded, so the
+same arguments give the same inputs on every run and two builds can be compared output for output.
 """
 import argparse
 import glob
@@ -55,6 +59,8 @@ OTHER_WORKLOADS = ["gas_hint_8", "miniboone_hint_10", "plus_hint_4", "conditiona
 PEAK_F32_MFMA_TFLOPS = 157.3   # MI355X_MICROARCH.md: v_mfma_f32_16x16x4_f32 = fp32 vector rate
 PEAK_HBM_GBS = 8000.0
 CHECK_THREADS = 16             # host threads of the oracle cross-checks (one per core is pathological for these small matrices)
+DUMP_MAX_BYTES = 64 * 2 ** 20  # --dump-outputs: budget of all files together
+TRAINER_SEED = 0               # the trainers' in-kernel noise stream (unseeded it is drawn from os.urandom)
 
 
 def flops_per_sample_block(d, widths, dc=0):
@@ -196,6 +202,32 @@ def timed_reps(step, barrier, steps, reps, use_dist, dist, dev):
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             el = float(t.item())
         out.append(el)
+    return out
+
+
+def dump_outputs(out_dir, losses, params):
+    """--dump-outputs: what a caller of the timed step receives from its last iteration - the two loss terms (l0, l1) it
+    returns and the parameters its fused clamp + Adam update left in place (every parameter of the model, flattened and
+    concatenated in named_parameters() order) - as float32 .npy files.  Should they exceed DUMP_MAX_BYTES, the budget is
+    shared out from the smallest array up: an array larger than its share is cut to a fixed seeded sample of its elements,
+    in index order.  Returns {name: elements written}."""
+    import numpy as np
+    arrays = {"loss_terms": torch.stack([torch.as_tensor(v).reshape(()) for v in losses]),
+              "parameters": torch.cat([p.detach().reshape(-1) for p in params])}
+    arrays = {k: v.float().cpu().numpy().reshape(-1) for k, v in arrays.items()}
+    rng = np.random.default_rng(0)
+    left = (DUMP_MAX_BYTES - 4096 * len(arrays)) // 4         # float32 elements (4 KB per file for the .npy header)
+    os.makedirs(out_dir, exist_ok=True)
+    out = {}
+    names = sorted(arrays, key=lambda k: arrays[k].size)
+    for i, k in enumerate(names):
+        a = arrays[k]
+        n = min(a.size, left // (len(names) - i))
+        if n < a.size:
+            a = a[np.sort(rng.choice(a.size, n, replace=False))]
+        left -= a.size
+        np.save(os.path.join(out_dir, f"{k}.npy"), a)
+        out[k] = int(a.size)
     return out
 
 
@@ -458,7 +490,7 @@ def run_flow(args, name, rank, world, dev, use_dist, dist, headline):
         gw = torch.Generator().manual_seed(0)
         for p in flow.parameters():                          # train_unconditional.py:165-167
             p.data = (0.005 * torch.randn(p.shape, generator=gw)).to(dev)
-    trainer = hint_amd.FlowTrainer(flow, use_graph=not args.no_graph)
+    trainer = hint_amd.FlowTrainer(flow, use_graph=not args.no_graph, seed=TRAINER_SEED)
     gx = torch.Generator().manual_seed(1000 + rank)          # each rank its own shard of the global batch
     x = torch.randn(B, d, generator=gx).to(dev)
 
@@ -470,6 +502,8 @@ def run_flow(args, name, rank, world, dev, use_dist, dist, headline):
     # the batch is resident in HBM before the timed region starts (the bench contract): it is written
     # once into the captured step's own input buffer, so that no device-to-device copy of it runs per step
     spg = args.steps_per_graph if (headline and args.steps_per_graph > 1 and not use_dist and not args.no_graph) else 1
+    if args.steps % spg:
+        raise SystemExit(f"--steps {args.steps} is not a multiple of --steps-per-graph {spg}")
     x, _ = trainer.input_buffers(x)
     if spg > 1:                              # K resident batches (K different shards of synthetic data) per replay
         xs = torch.randn(spg, B, d, generator=gx).to(dev)
@@ -489,6 +523,9 @@ def run_flow(args, name, rank, world, dev, use_dist, dist, headline):
         times = timed_reps(lambda: trainer.step(x), barrier, args.steps, args.reps, use_dist, dist, dev)
         steps_timed = args.steps
     elapsed, reps_info = rep_stats(times, steps_timed)
+    dumped = None
+    if args.dump_outputs and headline and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, trainer.last_losses(), flow.parameters())
 
     ms_per_step = elapsed / steps_timed * 1e3
     value = B * world * steps_timed / elapsed
@@ -553,6 +590,8 @@ def run_flow(args, name, rank, world, dev, use_dist, dist, headline):
         "mean_nll_nats": nll, "last_step_loss": loss_last,
     }
     res.update(reps_info)
+    if dumped is not None:
+        res["dumped_outputs"] = {"dir": args.dump_outputs, "elements": dumped}
     # HBM traffic per launch comes from rocprofv3 PMC passes run separately (tools/refresh_profiles.sh); it is NOT measured in
     # this process - the line says where it was read from
     pmc, pmc_file = newest_pmc(name) if B == cfg["batch"] else ({}, None)
@@ -682,7 +721,7 @@ def run_conditional(args, name, rank, world, dev, use_dist, dist, headline):
         gw = torch.Generator().manual_seed(0)
         for p in model.parameters():
             p.data = (0.005 * torch.randn(p.shape, generator=gw)).to(dev)
-    tr = hint_amd.ConditionalFlowTrainer(model, use_graph=not args.no_graph)
+    tr = hint_amd.ConditionalFlowTrainer(model, use_graph=not args.no_graph, seed=TRAINER_SEED)
     gx = torch.Generator().manual_seed(1000 + rank)
     x = torch.randn(B, cfg["nx"], generator=gx).to(dev)
     y = torch.randn(B, cfg["ny"], generator=gx).to(dev)
@@ -702,6 +741,9 @@ def run_conditional(args, name, rank, world, dev, use_dist, dist, headline):
     elapsed, reps_info = rep_stats(times, args.steps)
     if rank != 0:
         return None
+    dumped = None
+    if args.dump_outputs and headline:
+        dumped = dump_outputs(args.dump_outputs, out[0], model.parameters())
     l0, l1 = out[0]
     # algorithmic FLOPs of a step: forward MACs of every subnet (SURVEY §8d's F, summed over the three modules of a
     # block) x 3 (forward, dX, dW)
@@ -726,6 +768,8 @@ def run_conditional(args, name, rank, world, dev, use_dist, dist, headline):
                      "timing": "wall clock of the timed steps (graph replays), all launches of a step"},
     }
     res.update(reps_info)
+    if dumped is not None:
+        res["dumped_outputs"] = {"dir": args.dump_outputs, "elements": dumped}
     if world == 1 and not args.no_cpu_baseline:
         if headline:
             res["cpu_baseline"] = cpu_baseline_conditional(model, cfg, x, y)
@@ -759,8 +803,13 @@ def main():
                     help="weak: the workload's batch per rank; strong: the workload's batch is the global batch")
     ap.add_argument("--legs", action="store_true",
                     help="also time every kernel in a hot back-to-back loop (single-block and chained launches)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the headline's timed steps, write what its last step returned (loss terms) and left in place "
+                         "(parameters) as DIR/<name>.npy, float32, at most 64 MB in all")
     args = ap.parse_args()
     args.reps = max(1, args.reps)
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))

@@ -1,7 +1,9 @@
 """Pin the CPU oracle (oracle/hint_oracle.py) to golden vectors produced by the real
 reference hint.py (tests/golden/make_golden.py).  Tolerances: the oracle and the reference
 run the same ATen ops, but the flat schedule sums J in a different order and the GPU box's
-CPU may take different BLAS paths, so compare at rtol 1e-5 / atol 1e-5 (observed ≤ 2e-6)."""
+CPU may take different BLAS paths, so compare at rtol 1e-5 / atol 1e-5 (observed ≤ 2e-6).
+An ill-conditioned block (big_s: scales e^+-4 on |z| ~ 5e3) is further from the exact result
+than that in float32 itself; its bounds follow the fixture's own float32 error (ILL_CONDITIONED_TOL)."""
 import math
 
 import numpy as np
@@ -13,6 +15,10 @@ from util import (BLOCK_CASES, CHAIN_CASES, REV_GRAD_CASES, case_perms, load_blo
                   to_torch)
 
 TOL = dict(rtol=1e-5, atol=1e-5)
+# z and J of a block whose float32 result is further from the exact one than TOL: big_s's fixture lies 1.6e-4 (z) and
+# 1.6e-5 (J) from the float64 oracle on the same inputs, as max |err| / (|exact| + 1), and a float32 evaluation on another
+# host CPU's BLAS path (AVX2, SSE4.2) up to 2.4e-4 / 1.6e-5 - so two float32 results may differ by 4e-4 / 3.2e-5
+ILL_CONDITIONED_TOL = {"big_s_d6": {"z": dict(rtol=1e-3, atol=1e-3), "J": dict(rtol=1e-4, atol=1e-4)}}
 
 
 @pytest.mark.parametrize("case", BLOCK_CASES, ids=lambda c: c["name"])
@@ -26,8 +32,9 @@ def test_block_forward_inverse_grads(case):
     perms = {k: torch.from_numpy(v) for k, v in case_perms(g).items()}
     assert bool(perms) == c["reshuffle"]
     z, J = orc.block_apply(nodes, P, x, conds, rev=False, clamp=c["clamp"], perms=perms)
-    np.testing.assert_allclose(z.detach().numpy(), g["z"], **TOL)
-    np.testing.assert_allclose(J.detach().numpy(), g["J"], **TOL)
+    tol = ILL_CONDITIONED_TOL.get(c["name"], {"z": TOL, "J": TOL})
+    np.testing.assert_allclose(z.detach().numpy(), g["z"], **tol["z"])
+    np.testing.assert_allclose(J.detach().numpy(), g["J"], **tol["J"])
     L = (0.5 * torch.sum(z ** 2, dim=1) - J).mean()
     assert abs(L.item() - float(g["L"])) <= 1e-5 * max(1.0, abs(float(g["L"])))
     L.backward()
@@ -39,9 +46,13 @@ def test_block_forward_inverse_grads(case):
     with torch.no_grad():
         xr, Jr = orc.block_apply(nodes, P, z.detach(), [cc.detach() for cc in conds], rev=True, clamp=c["clamp"], perms=perms)
         xi, Ji = orc.block_apply(nodes, P, x.detach(), [cc.detach() for cc in conds], rev=True, clamp=c["clamp"], perms=perms)
+    # the round trip of big_s is float32 noise in the fixture too (|x_rec - x| ~ 6): bound the oracle's deviation from the
+    # fixture by the fixture's own round-trip error where that is the larger term (everywhere else it is below 4e-6)
     scale = max(1.0, float(np.abs(g["x_rec"]).max()))
-    np.testing.assert_allclose(xr.numpy(), g["x_rec"], rtol=1e-4, atol=2e-5 * scale)
-    np.testing.assert_allclose(Jr.numpy(), g["J_rev"], **TOL)
+    ref_rt = float(np.abs(g["x_rec"] - x_np).max())
+    ref_jj = float(np.abs(g["J"] + g["J_rev"]).max())
+    np.testing.assert_allclose(xr.numpy(), g["x_rec"], rtol=1e-4, atol=max(2e-5 * scale, ref_rt))
+    np.testing.assert_allclose(Jr.numpy(), g["J_rev"], rtol=TOL["rtol"], atol=max(TOL["atol"], ref_jj))
     assert rel_err(xi.numpy(), g["x_inv"]) < 1e-4
     np.testing.assert_allclose(Ji.numpy(), g["J_inv"], rtol=1e-4, atol=1e-4)
 

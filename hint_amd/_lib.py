@@ -11,7 +11,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("HINT_AMD_LIB") or os.path.join(_HERE, "lib", "libhint_amd.so")
-ABI_VERSION = 7
+ABI_VERSION = 8
 
 
 class HintAmdError(RuntimeError):
@@ -44,6 +44,9 @@ _PROTOS = {
     "hint_plan_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int32]),
     "hint_plan_lds_bytes": (C.c_int32, [C.c_void_p, C.c_int32]),
     "hint_plan_describe": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]),
+    "hint_plan_dispatch": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.c_int32]),
+    "hint_plan_check_dispatch": (C.c_int, [C.POINTER(NodeDesc), C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32,
+                                           C.c_int32, C.POINTER(C.c_int32), C.c_int32]),
     "hint_block_pack": (C.c_int, [C.c_void_p] * 4),
     "hint_pack_group_create": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
                                          C.c_int32, C.POINTER(C.c_void_p)]),

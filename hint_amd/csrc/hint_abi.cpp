@@ -216,6 +216,34 @@ int grid_for(const hint_plan* P, int B) {
     return std::min((ntiles + nr - 1) / nr, P->num_cu * 8);
 }
 
+// the row kernels loop over tile groups `for (tg = blockIdx.x; tg < groups; tg += gridDim.x)`: passes = ceil(groups / grid)
+Dispatch dispatch(const hint_plan* P, int B, int n_chain) {
+    Dispatch D;
+    P = variant(P, B);
+    D.P = P;
+    D.ntiles = (B + ROWS - 1) / ROWS;
+    D.nr = wl_nr_for(P, B);
+    D.groups = (D.ntiles + D.nr - 1) / D.nr;
+    D.grid = grid_for(P, B);
+    D.passes = D.grid > 0 ? (D.groups + D.grid - 1) / D.grid : 0;
+    D.fwd = P->wl ? FWD_WL : P->has_fly ? FWD_FLY : FWD_GEN;
+    D.bwd = P->wl ? BWD_WL : P->has_fly && !no_bwd_fly() ? BWD_FLY : P->row_ntt <= 3 && P->rowdw_lds == 0 ? BWD_N3 : BWD_GEN;
+    D.dw_small = P->n_wsmall > 0;
+    D.dw_wide = P->has_leanw != 0;
+    if (B > 0) wgrad_splits(P, B, n_chain, &D.dw_splits, &D.dw_rows);
+    return D;
+}
+
+int dispatch_out(const hint_plan* P, int B, int32_t* out, int32_t n_out) {
+    const Dispatch D = dispatch(P, B);
+    const hint_plan* V = D.P;
+    const int32_t v[HINT_DISPATCH_FIELDS] = {V->wl, D.nr, V->nw, V != P ? 1 : 0, D.ntiles, D.groups, D.grid, D.passes, D.fwd, D.bwd,
+                                             D.dw_small, D.dw_wide, D.dw_splits, D.dw_rows, V->n_sub, V->lean, V->has_leanw,
+                                             V->rowdw_lds > 0 ? 1 : 0, V->fuse_dw1, V->num_cu};
+    for (int i = 0; i < n_out && i < HINT_DISPATCH_FIELDS; ++i) out[i] = v[i];
+    return 0;
+}
+
 // part A (row-parallel, bit 0 of `parts`) and part B (weight gradients, bit 1) of the backward pass of
 // one block or a chain
 int run_backward(const hint_plan* P, const ChainBlock& one, const ChainBlock* chain, const ChainBlock* chain_host, int n_chain,
@@ -227,32 +255,33 @@ int run_backward(const hint_plan* P, const ChainBlock& one, const ChainBlock* ch
     if (!knobs().ablation_ok) return fail("this is an ablation build (HINT_ABLATE_STORE): its gradients are wrong; set HINT_ABLATION_OK=1 for timing runs");
 #endif
 
-    if ((parts & 1) && P->wl) {
+    const Dispatch D = dispatch(P, B, n_total);
+    P = D.P;
+    if ((parts & 1) && D.bwd == BWD_WL) {
         KArgs a = make_args(P, B, true);
-        const int nr = wl_nr_for(P, B);
+        const int nr = D.nr;
         WlArgs w = P->wl_b[nr - 1];
         bool any_perm = one.perm != nullptr;
         if (chain_host) for (int i = 0; i < n_chain; ++i) any_perm = any_perm || chain_host[i].perm != nullptr;
         const int lds = lds_with_perms(P, plan_lds(P, true, nr), n_chain, any_perm, &a, true);
         w.off_perm = a.perm_lds;
-        HIP_TRY(launch_wl_bwd(a, w, lds, grid_for(P, B), one, chain, n_chain, x, g_z, g_J, g_x, gz_scale, gJ_const, s));
+        HIP_TRY(launch_wl_bwd(a, w, lds, D.grid, one, chain, n_chain, x, g_z, g_J, g_x, gz_scale, gJ_const, s));
     } else if (parts & 1) {
         // (the permutation matrices stay in global memory here: one d x d product per block)
         // (round 5: the backward's L2 warm-up gets its sink too - until then KArgs::sink_lds was 0 here and the block in hint_bwd.hip dead code)
         KArgs a = make_args(P, B, true);
         const int lds = add_sink(P, P->lds_bwd, &a);
         g_last_lds[1].store(lds, std::memory_order_relaxed);
-        HIP_TRY((P->has_fly && !no_bwd_fly() ? launch_bwd_fly : P->row_ntt <= 3 && P->rowdw_lds == 0 ? launch_bwd_n3 : launch_bwd)(a, lds, grid_for(P, B), one, chain, n_chain, x, c,
+        HIP_TRY((D.bwd == BWD_FLY ? launch_bwd_fly : D.bwd == BWD_N3 ? launch_bwd_n3 : launch_bwd)(a, lds, D.grid, one, chain, n_chain, x, c,
                                                                g_z, g_J, g_x, g_c, gz_scale, gJ_const, s));
     }
     if (!(parts & 2)) return 0;
-    int splits, rows_per_wg;
-    wgrad_splits(P, B, n_total, &splits, &rows_per_wg);     // (the whole chain's count: a bucketed launch sums in the same order)
+    const int splits = D.dw_splits, rows_per_wg = D.dw_rows;   // (the whole chain's count: a bucketed launch sums in the same order)
     HIP_TRY(launch_wgrad(P->d_wjobs, P->n_wjobs, P->wsorted ? -P->n_wsmall - 1 : P->n_wsmall, splits, one, chain, n_chain, cb0, P->WT, P->ST, P->d, P->dc, P->n_levels, B,
                          rows_padded(B), rows_per_wg, act_stride(P, B), P->lean ? 0 : act_stride(P, B),
                          (P->lean ? 1 : 2) * act_stride(P, B) * 4 + bits_stride(P, B), P->param_floats, x, c, P->d_real,
-                         accumulate, P->fuse_dw1 ? P->d_twmap : nullptr, P->tw_floats, ws_thin_off(P, B), grid_for(P, B),
-                         P->num_cu, adam, P->has_leanw != 0, s));
+                         accumulate, P->fuse_dw1 ? P->d_twmap : nullptr, P->tw_floats, ws_thin_off(P, B), D.grid,
+                         P->num_cu, adam, D.dw_small, D.dw_wide, s));
     return 0;
 }
 
@@ -267,21 +296,22 @@ static int apply(const hint_plan* P, bool rev, const float* params, const float*
     if (P->dc > 0 && !c) return fail("hint_block_%s: plan has dc=%d but c is NULL", what, P->dc);
     if (B < 0) return fail("negative batch");
     if (B == 0) return 0;
-    P = variant(P, B);
+    const Dispatch D = dispatch(P, B);
+    P = D.P;
     ChainBlock one{};
     one.params = params; one.packed = packed; one.perm = perm;
     bind_tape(P, B, rev ? nullptr : tape, &one);
     KArgs a = make_args(P, B, false);
-    const int nr = wl_nr_for(P, B);
+    const int nr = D.nr;
     const int lds = lds_with_perms(P, plan_lds(P, false, nr), 1, perm != nullptr, &a);
-    if (P->wl) {
+    if (D.fwd == FWD_WL) {
         WlArgs w = P->wl_f[nr - 1];
         w.off_perm = a.perm_lds;
-        HIP_TRY(launch_wl_apply(rev, a, w, lds, grid_for(P, B), one, nullptr, 1, x, z, J, J_in, loss_acc, noise,
+        HIP_TRY(launch_wl_apply(rev, a, w, lds, D.grid, one, nullptr, 1, x, z, J, J_in, loss_acc, noise,
                                 (const unsigned long long*)rng_state, x_noisy, (hipStream_t)stream));
         return 0;
     }
-    HIP_TRY(launch_apply(rev, P->has_fly != 0, a, lds, grid_for(P, B), one, nullptr, 1, x, c, z, J, J_in, loss_acc, noise,
+    HIP_TRY(launch_apply(rev, D.fwd == FWD_FLY, a, lds, D.grid, one, nullptr, 1, x, c, z, J, J_in, loss_acc, noise,
                          (const unsigned long long*)rng_state, x_noisy, (hipStream_t)stream));
     return 0;
 }
@@ -350,6 +380,11 @@ int hint_plan_describe(const hint_plan* P, int32_t B, int32_t* out) {
     out[0] = P->wl; out[1] = wl_nr_for(P, B); out[2] = P->nw; out[3] = P->lean;
     out[4] = P->n_sub; out[5] = P->row_ntt; out[6] = P->rowdw_lds > 0 ? 1 : 0; out[7] = P->has_fly;
     return 0;
+}
+
+int hint_plan_dispatch(const hint_plan* P, int32_t B, int32_t* out, int32_t n_out) {
+    if (!P || !out || B < 1 || n_out < 1) return fail("hint_plan_dispatch: bad arguments");
+    return dispatch_out(P, B, out, n_out);
 }
 
 int hint_block_pack(const hint_plan* P, const float* params, float* packed, void* stream) {

@@ -100,17 +100,18 @@ int hint_chain_forward_noisy(const hint_chain* C, const float* x, const float* c
     if (chain_gathered(C)) return fail("hint_chain_forward: the chain's blocks have inputs of their own (hint_chain_set_block_io): it serves part B only");
     const hint_plan* P = C->plan;
     if (P->dc > 0 && !c) return fail("hint_chain_forward: plan has dc=%d but c is NULL", P->dc);
+    const Dispatch D = dispatch(P, C->B);
     KArgs a = make_args(P, C->B, false);
-    const int nr = wl_nr_for(P, C->B);
+    const int nr = D.nr;
     const int lds = lds_with_perms(P, plan_lds(P, false, nr), C->n, chain_any_perm(C), &a);
-    if (P->wl) {
+    if (D.fwd == FWD_WL) {
         WlArgs w = P->wl_f[nr - 1];
         w.off_perm = a.perm_lds;
-        HIP_TRY(launch_wl_apply(false, a, w, lds, grid_for(P, C->B), C->host[0], C->d_table, C->n, x, z, J, J_in, loss_acc, noise,
+        HIP_TRY(launch_wl_apply(false, a, w, lds, D.grid, C->host[0], C->d_table, C->n, x, z, J, J_in, loss_acc, noise,
                                 (const unsigned long long*)rng_state, x_noisy, (hipStream_t)stream));
         return 0;
     }
-    HIP_TRY(launch_apply(false, P->has_fly != 0, a, lds, grid_for(P, C->B), C->host[0], C->d_table, C->n, x, c, z, J,
+    HIP_TRY(launch_apply(false, D.fwd == FWD_FLY, a, lds, D.grid, C->host[0], C->d_table, C->n, x, c, z, J,
                          J_in, loss_acc, noise, (const unsigned long long*)rng_state, x_noisy, (hipStream_t)stream));
     return 0;
 }
@@ -122,17 +123,18 @@ int hint_chain_inverse(const hint_chain* C, const float* z, const float* c, floa
     if (chain_gathered(C)) return fail("hint_chain_inverse: the chain's blocks have inputs of their own (hint_chain_set_block_io): it serves part B only");
     const hint_plan* P = C->plan;
     if (P->dc > 0 && !c) return fail("hint_chain_inverse: plan has dc=%d but c is NULL", P->dc);
+    const Dispatch D = dispatch(P, C->B);
     KArgs a = make_args(P, C->B, false);
-    const int nr = wl_nr_for(P, C->B);
+    const int nr = D.nr;
     const int lds = lds_with_perms(P, plan_lds(P, false, nr), C->n, chain_any_perm(C), &a);
-    if (P->wl) {
+    if (D.fwd == FWD_WL) {
         WlArgs w = P->wl_f[nr - 1];
         w.off_perm = a.perm_lds;
-        HIP_TRY(launch_wl_apply(true, a, w, lds, grid_for(P, C->B), C->host[0], C->d_table, C->n, z, x, J, J_in, nullptr, 0.f,
+        HIP_TRY(launch_wl_apply(true, a, w, lds, D.grid, C->host[0], C->d_table, C->n, z, x, J, J_in, nullptr, 0.f,
                                 nullptr, nullptr, (hipStream_t)stream));
         return 0;
     }
-    HIP_TRY(launch_apply(true, P->has_fly != 0, a, lds, grid_for(P, C->B), C->host[0], C->d_table, C->n, z, c, x, J, J_in, nullptr, 0.f,
+    HIP_TRY(launch_apply(true, D.fwd == FWD_FLY, a, lds, D.grid, C->host[0], C->d_table, C->n, z, c, x, J, J_in, nullptr, 0.f,
                          nullptr, nullptr, (hipStream_t)stream));
     return 0;
 }

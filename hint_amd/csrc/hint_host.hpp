@@ -42,7 +42,8 @@ hipError_t launch_wgrad(const WJob* jobs, int n_jobs, int n_small, int splits, c
                         int n_chain, int cb0, int WT, int ST, int d, int dc, int n_levels, int B, int Bp, int rows_per_wg,
                         int64_t act_stride, int64_t a2_off, int64_t bits_a2_off, int64_t param_floats, const float* x,
                         const float* c, const uint8_t* real, int accumulate, const int32_t* twmap, int tw_floats,
-                        int64_t thin_slab_off, int thin_slabs, int num_cu, const AdamFuse* adam, bool wide, hipStream_t stream);
+                        int64_t thin_slab_off, int thin_slabs, int num_cu, const AdamFuse* adam, bool small, bool wide,
+                        hipStream_t stream);
 hipError_t launch_bwd_n3(const KArgs& a, int lds_bytes, int grid, const ChainBlock& one, const ChainBlock* chain,
                          int n_chain, const float* x, const float* c, const float* g_z, const float* g_J,
                          float* g_x, float* g_c, float gz_scale, float gJ_const, hipStream_t stream);      // (hint_bwd3.hip: rows of <= 3 tiles)
@@ -194,6 +195,20 @@ int64_t tape_act_off(const hint_plan* P, int B);
 int64_t act_stride(const hint_plan* P, int B);
 int64_t bits_stride(const hint_plan* P, int B);
 int grid_for(const hint_plan* P, int B);
+// Which kernel instances a batch of B rows runs on: the one decision every launch site takes (apply, run_backward, the chain's
+// forward and inverse) and what hint_plan_dispatch / hint_plan_check_dispatch report.  P may already be the variant (variant()
+// returns a variant unchanged); n_chain: blocks of the launch whose part-B batch split counts (run_backward's n_total).
+enum { FWD_WL = 0, FWD_GEN = 1, FWD_FLY = 2 };                  // hint_wl_apply_kernel, hint_apply_kernel<REV, false | true>
+enum { BWD_WL = 0, BWD_GEN = 1, BWD_N3 = 2, BWD_FLY = 3 };      // hint_wl_bwd_kernel, hint_bwd_kernel, hint_bwd_kernel_n3, hint_bwd_kernel_fly
+struct Dispatch {
+    const hint_plan* P = nullptr;       // the plan variant
+    int ntiles = 0, nr = 1, groups = 0, grid = 0, passes = 0;   // row tiles, tiles per workgroup, tile groups, workgroups, passes of the tile loop
+    int fwd = FWD_WL, bwd = BWD_WL;
+    bool dw_small = false, dw_wide = false;                     // part B: hint_wgrad_kernel<S, W>
+    int dw_splits = 0, dw_rows = 0;                             // part B: batch splits, rows per split
+};
+Dispatch dispatch(const hint_plan* P, int B, int n_chain = 1);
+int dispatch_out(const hint_plan* P, int B, int32_t* out, int32_t n_out);     // (the exports' layout: include/hint_amd.h)
 int lds_with_perms(const hint_plan* P, int lds_plan, int n_blocks, bool any_perm, KArgs* a, bool backward = false);     // (backward: which slot of hint_debug_last_lds_bytes the launch's size goes to)
 KArgs make_args(const hint_plan* P, int B, bool backward);
 void split_workspace(const hint_plan* P, int B, void* workspace, ChainBlock* b);

@@ -1111,6 +1111,22 @@ int hint_plan_check(const hint_node_desc* nodes, int32_t n_nodes, int32_t d, int
     return 0;
 }
 
+int hint_plan_check_dispatch(const hint_node_desc* nodes, int32_t n_nodes, int32_t d, int32_t dc, float clamp, int32_t B,
+                             int32_t num_cu, int32_t* out, int32_t n_out) {
+    if (!out || B < 1 || num_cu < 1 || n_out < 1) return fail("hint_plan_check_dispatch: bad arguments");
+    hint_plan* P = nullptr;
+    g_host_only = true;
+    const int st = hint_plan_create(nodes, n_nodes, d, dc, clamp, &P);
+    g_host_only = false;
+    if (st != 0) return st;
+    P->num_cu = num_cu;
+    if (P->alt4) P->alt4->num_cu = num_cu;
+    dispatch_out(P, B, out, n_out);
+    delete P->alt4;
+    delete P;
+    return 0;
+}
+
 void hint_plan_destroy(hint_plan* P) {
     if (!P) return;
     hint_plan_destroy(P->alt4);

@@ -774,11 +774,13 @@ hipError_t launch_wgrad(const WJob* jobs, int n_jobs, int n_small, int splits, c
                         int n_chain, int cb0, int WT, int ST, int d, int dc, int n_levels, int B, int Bp, int rows_per_wg,
                         int64_t act_stride, int64_t a2_off, int64_t bits_a2_off, int64_t param_floats, const float* x,
                         const float* c, const uint8_t* real, int accumulate, const int32_t* twmap, int tw_floats,
-                        int64_t thin_slab_off, int thin_slabs, int num_cu, const AdamFuse* adam, bool wide, hipStream_t stream) {
+                        int64_t thin_slab_off, int thin_slabs, int num_cu, const AdamFuse* adam, bool small, bool wide,
+                        hipStream_t stream) {
     const bool interleave = n_small < 0;       // (flag in the sign: the planner sorted the jobs)
     if (interleave) n_small = -n_small - 1;
 #ifdef HINT_DW_SOLO_ALL
     n_small = n_jobs;                          // (experiment: one (job, split) per wavefront for every job)
+    small = n_jobs > 0;
 #endif
     const int used = (n_jobs - n_small + (n_small + DW_WAVES - 1) / DW_WAVES) * splits;
     const int grid_pb = n_chain > 1 ? (used + 7) / 8 * 8 : used;
@@ -791,8 +793,9 @@ hipError_t launch_wgrad(const WJob* jobs, int n_jobs, int n_small, int splits, c
 #define HINT_DW_LAUNCH(S_, W_) hipLaunchKernelGGL((hint_wgrad_kernel<S_, W_>), dim3(grid_pb * n_chain), dim3(DW_WAVES * 64), 0, stream, jobs, n_jobs, n_small, splits, \
                                one, chain, gpb, cb0, WT, ST, d, dc, n_levels, B, Bp, rows_per_wg, act_stride, a2_off, bits_a2_off, param_floats, x, c)
 #endif
-        if (wide) { if (n_small > 0) HINT_DW_LAUNCH(true, true); else HINT_DW_LAUNCH(false, true); }
-        else if (n_small > 0) HINT_DW_LAUNCH(true, false);
+        // (small, wide: dispatch() in hint_abi.cpp - small is n_small > 0)
+        if (wide) { if (small) HINT_DW_LAUNCH(true, true); else HINT_DW_LAUNCH(false, true); }
+        else if (small) HINT_DW_LAUNCH(true, false);
         else HINT_DW_LAUNCH(false, false);
 #undef HINT_DW_LAUNCH
     }

@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define HINT_AMD_ABI_VERSION 7
+#define HINT_AMD_ABI_VERSION 8
 
 /* index into hint_node_desc.p_off: [net][tensor]; net 0 = s, net 1 = t (hint.py:44-45);
  * tensors in nn.Sequential order (hint.py:11-13): W1 [h,cin], b1 [h], W2 [h,h], b2 [h],
@@ -107,6 +107,26 @@ int32_t hint_plan_lds_bytes(const hint_plan* plan, int32_t backward);
  * out[7] = 1 when some general group is lean: forward and inverse run on hint_apply_kernel<REV, true>, whose rows make such groups'
  * first layer themselves (no thin phase), else on hint_apply_kernel<REV, false>.  out must hold 8 values. */
 int hint_plan_describe(const hint_plan* plan, int32_t B, int32_t* out);
+
+/* The launch decision for a batch of B >= 1 rows, as the entry points take it (one function decides for hint_block_forward*,
+ * hint_block_inverse*, hint_block_backward* and the chain's forward, inverse and backward): which compiled kernel instance every
+ * launch runs on and how often its tile loop `for (tg = blockIdx.x; tg < groups; tg += gridDim.x)` goes round.  Writes the first
+ * min(n_out, HINT_DISPATCH_FIELDS) of:
+ *   [0] 1: wave-local kernels (hint_wl_apply_kernel<REV, NR, CH> / hint_wl_bwd_kernel<NR, CH>), 0: general ones
+ *   [1] NR, 16-row tiles per workgroup (2: row pairs)        [2] wavefronts per workgroup
+ *   [3] 1 when the batch runs on the plan's 4-wavefront variant
+ *   [4] 16-row tiles    [5] tile groups (ceil(tiles / NR))    [6] workgroups of the row kernels    [7] passes (ceil(groups / grid))
+ *   [8] forward / inverse: 0 hint_wl_apply_kernel, 1 hint_apply_kernel<REV, false>, 2 hint_apply_kernel<REV, true>
+ *   [9] backward part A: 0 hint_wl_bwd_kernel, 1 hint_bwd_kernel, 2 hint_bwd_kernel_n3, 3 hint_bwd_kernel_fly
+ *   [10] [11] part B: S and W of hint_wgrad_kernel<S, W>      [12] [13] part B's batch splits and rows per split (one block)
+ *   [14] subtree groups    [15] lean    [16] some group is lean-wide    [17] rows of the backward kernel compute dW1 | db1 (rowdw)
+ *   [18] first-layer weight gradients come from the backward kernel (fuse_dw1)    [19] CUs the decision assumed.
+ * CH (chained launch or single block) is the entry point's, not part of the decision. */
+#define HINT_DISPATCH_FIELDS 20
+int hint_plan_dispatch(const hint_plan* plan, int32_t B, int32_t* out, int32_t n_out);
+/* The same for a host-only plan (as hint_plan_check builds it: no device needed) on a device of num_cu CUs. */
+int hint_plan_check_dispatch(const hint_node_desc* nodes, int32_t n_nodes, int32_t d, int32_t dc, float clamp, int32_t B,
+                             int32_t num_cu, int32_t* out, int32_t n_out);
 
 /* Re-pack the flat parameters into `packed` (hint_plan_packed_floats floats).  Must be called
  * after every change of the parameters and before the next forward / inverse / backward that

@@ -33,8 +33,9 @@ WORKLOADS = [
     ("cfg3_gas_hint_8_B8192", 8, 0, 8, [128, 64, 32, 16], 8192, 0.06),
     ("cfg2_power_hint_8_B8192", 6, 0, 8, [140, 70, 35, 17], 8192, 0.06),
     # gradients at the batch sizes the general plans really run at: more row tiles than the chip has CUs (273 tiles, the last
-    # one ragged: the persistent tile loop of hint_apply_kernel / hint_bwd_kernel_fly and part B's row splits at d = 100 - the
-    # reference's own batch for cfg 4 is 10 000 rows, configs/plus_shape/conditional_hint_4_full.py:37), with and without a
+    # one ragged, on 273 workgroups: one pass of hint_apply_kernel / hint_bwd_kernel_fly's tile loop - tests/test_gpu_instances.py
+    # runs two - and part B's row splits at d = 100; the reference's own batch for cfg 4 is 10 000 rows,
+    # configs/plus_shape/conditional_hint_4_full.py:37), with and without a
     # condition, and cfg 5's whole chain at its per-GPU batch (configs/uci_data/miniboone_hint_8.py; BASELINE cfg 5: 4096 rows per GPU)
     ("cfg4_plus_x_lane_B4368", 100, 0, 2, [224, 112, 56], 4368, 0.03),
     ("cfg4_plus_x_lane_cond_B4368", 100, 4, 2, [224, 112, 56], 4368, 0.03),

@@ -211,11 +211,16 @@ def test_parameter_rebinding_and_empty_batch():
 
 
 def test_persistent_tile_loop_large_batch():
-    """more row tiles than the launch has workgroups (grid is capped at 8 per CU): the kernels
-    loop over tiles, re-using the LDS tables and prefetching the first group's lists again"""
+    """more row-tile pairs than the launch has workgroups (grid is capped at 8 per CU): the wave-local kernels go round
+    their tile loop twice, the second pass ragged, re-using the LDS tables and prefetching the first group's lists again
+    (B follows the CU count; hint_plan_dispatch shows the passes before anything is compared)"""
+    from instance_cases import multi_pass_b, plan_dispatch
     torch.manual_seed(1)
-    d, widths, B = 6, [24, 12], 16 * 2048 + 16 * 300 + 5
+    d, widths = 6, [24, 12]
+    B = multi_pass_b(torch.cuda.get_device_properties(0).multi_processor_count, 2)
     blk = hint_amd.HierarchicalAffineCouplingBlock([(d,)], c_internal=widths).to(DEV)
+    disp = plan_dispatch(blk.tree.engine(torch.device(DEV)).lib, blk.tree.engine(torch.device(DEV)).plan, B)
+    assert disp["passes"] >= 2 and disp["groups"] % disp["grid"] != 0, disp
     x = torch.randn(B, d, device=DEV)
     nodes = orc.build_nodes(d, (), widths)
     P = {k: v.detach().cpu().clone().requires_grad_(True) for k, v in blk.state_dict().items()}

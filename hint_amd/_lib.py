@@ -80,6 +80,8 @@ _PROTOS = {
     "hint_chain_wgrad_adam": (C.c_int, [C.c_void_p] * 6 + [C.c_int64, C.c_void_p] + [C.c_float] * 6 + [C.c_void_p]),
     "hint_block_forward_noisy": (C.c_int, [C.c_void_p] * 11 + [C.c_float, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "hint_block_backward_rows": (C.c_int, [C.c_void_p] * 11 + [C.c_size_t, C.c_void_p, C.c_float, C.c_float, C.c_int32, C.c_void_p]),
+    "hint_block_ext_coeffs": (C.c_int, [C.c_void_p] * 4 + [C.c_int32, C.c_void_p, C.c_void_p]),
+    "hint_chain_set_block_affine": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64]),
     "hint_adam_step_dev": (C.c_int, [C.c_void_p] * 4 + [C.c_int64, C.c_void_p] + [C.c_float] * 6 + [C.c_int32, C.c_void_p]),
     "hint_adam_step": (C.c_int, [C.c_void_p] * 4 + [C.c_int64, C.c_int32] + [C.c_float] * 7 + [C.c_int32,
                                                                                                  C.c_void_p]),

@@ -99,6 +99,26 @@ class ConditionalHintFlow(nn.Module):
                                                          F_args={"internal_size": hidden}))             # :78-82
             self.ac_y.append(AffineCoupling([(ndim_y,)], F_args={"internal_size": hidden // 2}))        # :84-88
         self._jac_x = self._jac_y = None
+        self._post: Optional["_PosteriorSampler"] = None       # sample_conditional / x_lane_forward: chain handles, built on first use
+
+    # (the sampler holds raw chain handles: copies and pickles of the model leave it behind and build their own, as the trees do
+    #  with their engines)
+    def __getstate__(self):
+        state = self.__dict__.copy()
+        state["_post"] = None
+        return state
+
+    def __deepcopy__(self, memo):
+        import copy
+        post, self._post = self._post, None
+        try:
+            new = self.__class__.__new__(self.__class__)
+            memo[id(self)] = new
+            for k, v in self.__dict__.items():
+                setattr(new, k, copy.deepcopy(v, memo))
+        finally:
+            self._post = post
+        return new
 
     def forward(self, inputs: Sequence[torch.Tensor], rev: bool = False):
         a, b = inputs
@@ -141,6 +161,208 @@ class ConditionalHintFlow(nn.Module):
     def x_jac(self):
         """train_conditional.py:50-55: log-det of the x lane (hac_x_* and ac_y_to_x_* nodes)"""
         return self._jac_x
+
+    # ---- posterior sampling (conditional_hint_4_full.py:99-113) and the x-lane density (train_conditional.py:58-100) ----
+    @torch.no_grad()
+    def sample_conditional(self, y: torch.Tensor, z_x: torch.Tensor):
+        """x ~ p(x | y) from z_x: the reference config's `sample_conditional(y, z_x)` / `model_inverse(y, z)` - the x lane of
+        `self([z_y, z_x], rev=True)` with z_y the y lane's forward of y - on the current weights, without autograd.
+        y: [ny] or [1, ny] (one observation for every row of z_x) or [B, ny]; z_x: [B, nx].
+        -> (x [B, nx], J_x [B]): J_x is the x lane's inverse log-det (the reference's rev=True sign, what x_jac() holds after
+        the module route's inverse).  Runs as the y lane on the distinct observations, the four ExternalAffineCouplings'
+        coefficients (hint_block_ext_coeffs) and ONE chained inverse of the x lane with the couplings and the permutations fused
+        (hint_chain_set_block_affine); a plan on the wave-local kernels (narrow trees) takes the module route instead."""
+        return self._posterior().run(y, z_x, rev=True)
+
+    @torch.no_grad()
+    def x_lane_forward(self, x: torch.Tensor, y: torch.Tensor):
+        """(z_x, J_x) of `self([y, x])` / `x_jac()` - what evaluate(only_x=True) needs (train_conditional.py:58-100: the x-lane
+        density 0.5 |z_x|^2 - J_x) - as the same fused chain run forward; y as in sample_conditional."""
+        return self._posterior().run(y, x, rev=False)
+
+    def _posterior(self) -> "_PosteriorSampler":
+        dev = next(self.parameters()).device
+        ps = getattr(self, "_post", None)
+        if ps is None or ps.device != dev:
+            if dev.type != "cuda":
+                raise HintAmdError("hint_amd: no CPU implementation; move the model and data to the GPU")
+            if dev.index is None:
+                dev = torch.device("cuda", torch.cuda.current_device())
+            ps = self._post = _PosteriorSampler(self, dev)
+        return ps
+
+
+class _PosteriorSampler:
+    """The fused x lane of a ConditionalHintFlow for a given y (ConditionalHintFlow.sample_conditional / x_lane_forward): per batch
+    size and y mode (one observation broadcast, or one per row) an inference chain over the hac_x blocks - block i's permutation
+    perm_x_i fused in front, ac_y_to_x_i as the block's affine step behind it - and the coefficient buffer it reads."""
+
+    def __init__(self, flow: "ConditionalHintFlow", device: torch.device):
+        from . import _lib
+        self._lib, self.lib = _lib, _lib.load()
+        self.flow, self.device = flow, device
+        nb = flow.n_blocks
+        self.hx = [flow.hac_x[i].tree.engine(device) for i in range(nb)]
+        self.ex = [flow.ac_y_to_x[i].tree.engine(device) for i in range(nb)]
+        self.ey = [flow.ac_y[i].tree.engine(device) for i in range(nb)]
+        self.engines = self.hx + self.ex + self.ey
+        # the fused route needs one plan for every hac_x block and ExternalAffineCouplings without node permutations of their own
+        self.fusable = all(e.shape_key == self.hx[0].shape_key for e in self.hx) and all(e.total_perm() is None for e in self.ex)
+        self._pack_group, self._pack_key = None, None
+        self._chains = {}            # (B, per_row) -> (handle, key, coef, perms)
+
+    def __del__(self):
+        try:
+            for h, _, _, _ in self._chains.values():
+                self.lib.hint_chain_destroy(h)
+            self._chains = {}
+            if self._pack_group:
+                self.lib.hint_pack_group_destroy(self._pack_group)
+        except Exception:
+            pass
+
+    def _pack_all(self):
+        """one launch re-packs the twelve modules from their arenas (the weights may have changed since the last call: a
+        trainer step, load_state_dict, an optimizer on the parameters)"""
+        import ctypes as C
+        for e in self.engines:
+            e.ensure_arena()
+            if e.packed is None or e.packed.device != self.device:
+                e.pack()
+        key = tuple((e.arena.data_ptr(), e.packed.data_ptr()) for e in self.engines)
+        if self._pack_key != key:
+            if self._pack_group:
+                self.lib.hint_pack_group_destroy(self._pack_group)
+                self._pack_group = None
+            n = len(self.engines)
+            plans = (C.c_void_p * n)(*[e.plan.value for e in self.engines])
+            params = (C.c_void_p * n)(*[e.arena.data_ptr() for e in self.engines])
+            packed = (C.c_void_p * n)(*[e.packed.data_ptr() for e in self.engines])
+            handle = C.c_void_p()
+            with torch.cuda.device(self.device):
+                self._lib.check(self.lib.hint_pack_group_create(plans, params, packed, n, C.byref(handle)), "hint_pack_group_create")
+            self._pack_group, self._pack_key = handle, key
+        with torch.cuda.device(self.device):
+            self._lib.check(self.lib.hint_pack_group_run(self._pack_group, torch.cuda.current_stream(self.device).cuda_stream),
+                            "hint_pack_group_run")
+
+    def _wave_local(self, B: int) -> bool:
+        import ctypes as C
+        out = (C.c_int32 * 20)()
+        self._lib.check(self.lib.hint_plan_dispatch(self.hx[0].plan, B, out, 20), "hint_plan_dispatch")
+        return out[0] != 0
+
+    def _chain(self, B: int, per_row: bool):
+        """the inference chain of batch size B and its coefficient buffer [n_blocks, R, 2, nx] (R = B per row, else 1)"""
+        import ctypes as C
+        flow, nb, dx = self.flow, self.flow.n_blocks, self.flow.ndim_x
+        for i in range(1, nb):                          # (the kernels read W through its raw pointer, row-major)
+            if not flow.perm_x[i].W.is_contiguous():
+                flow.perm_x[i].W = flow.perm_x[i].W.contiguous()
+        perms = [e.compose_perm(flow.perm_x[i].W if i > 0 else None) for i, e in enumerate(self.hx)]
+        key = tuple((e.arena.data_ptr(), e.packed.data_ptr()) for e in self.hx) + tuple(p.data_ptr() if p is not None else 0 for p in perms)
+        have = self._chains.get((B, per_row))
+        if have is not None and have[1] == key:
+            return have[0], have[2]
+        torch.cuda.synchronize(self.device)             # (a launch on a stale chain's device table may still be queued)
+        if have is not None:
+            self.lib.hint_chain_destroy(have[0])
+            del self._chains[(B, per_row)]
+        elif len(self._chains) >= 8:                    # ragged batch sizes: forget the older ones
+            for k in list(self._chains):
+                self.lib.hint_chain_destroy(self._chains[k][0])
+                del self._chains[k]
+        R = B if per_row else 1
+        coef = torch.empty(nb, R, 2, dx, dtype=torch.float32, device=self.device)
+        handle = C.c_void_p()
+        chk = self._lib.check
+        with torch.cuda.device(self.device):
+            chk(self.lib.hint_chain_create(self.hx[0].plan, nb, B, C.byref(handle)), "hint_chain_create")
+            try:
+                for i, e in enumerate(self.hx):
+                    chk(self.lib.hint_chain_set_block(handle, i, e.arena.data_ptr(), e.packed.data_ptr(),
+                                                      perms[i].data_ptr() if perms[i] is not None else None, None, None, 0, None),
+                        "hint_chain_set_block")
+                    chk(self.lib.hint_chain_set_block_affine(handle, i, coef[i].data_ptr(), 2 * dx if per_row else 0),
+                        "hint_chain_set_block_affine")
+                chk(self.lib.hint_chain_commit(handle), "hint_chain_commit")
+            except Exception:
+                self.lib.hint_chain_destroy(handle)
+                raise
+        self._chains[(B, per_row)] = (handle, key, coef, perms)
+        return handle, coef
+
+    def _y_lane(self, y: torch.Tensor):
+        """the conditions of the x lane's couplings: the y lane before ac_y_i (conditional_hint_4_full.py:76-88), on the module
+        kernels (the last ac_y is not needed)"""
+        flow, conds = self.flow, []
+        for i in range(flow.n_blocks):
+            if i > 0:
+                (y,) = flow.perm_y[i]([y])
+            y = y.contiguous()
+            conds.append(y)
+            if i + 1 < flow.n_blocks:
+                y, _ = self.ey[i].apply(y, None, rev=False)
+        return conds
+
+    def _module_route(self, conds, x, rev: bool):
+        """the x lane through its modules (wave-local plans, or modules the chain cannot hold)"""
+        flow, B = self.flow, x.shape[0]
+        conds = [c.expand(B, -1).contiguous() if c.shape[0] != B else c for c in conds]
+        J = torch.zeros(B, dtype=torch.float32, device=x.device)
+        if rev:
+            for i in reversed(range(flow.n_blocks)):
+                (x,) = flow.ac_y_to_x[i]([x], c=[conds[i]], rev=True); J = J + flow.ac_y_to_x[i].jacobian(None)
+                (x,) = flow.hac_x[i]([x], rev=True);                   J = J + flow.hac_x[i].jacobian(None)
+                if i > 0:
+                    (x,) = flow.perm_x[i]([x], rev=True)
+        else:
+            for i in range(flow.n_blocks):
+                if i > 0:
+                    (x,) = flow.perm_x[i]([x])
+                (x,) = flow.hac_x[i]([x]);                    J = J + flow.hac_x[i].jacobian(None)
+                (x,) = flow.ac_y_to_x[i]([x], c=[conds[i]]);  J = J + flow.ac_y_to_x[i].jacobian(None)
+        return x, J
+
+    def run(self, y: torch.Tensor, x: torch.Tensor, rev: bool):
+        flow = self.flow
+        if not isinstance(x, torch.Tensor) or not isinstance(y, torch.Tensor):
+            raise HintAmdError("sample_conditional / x_lane_forward take tensors")
+        if x.dim() != 2 or x.shape[1] != flow.ndim_x:
+            raise HintAmdError(f"x lane input must be [B, {flow.ndim_x}], got {tuple(x.shape)}")
+        B = x.shape[0]
+        if y.dim() == 1:
+            y = y.unsqueeze(0)
+        if y.dim() != 2 or y.shape[1] != flow.ndim_y or y.shape[0] not in (1, B):
+            raise HintAmdError(f"y must be [{flow.ndim_y}], [1, {flow.ndim_y}] or [{B}, {flow.ndim_y}], got {tuple(y.shape)}")
+        if x.device != self.device or y.device != self.device:
+            raise HintAmdError(f"inputs must be on the model's device {self.device}")
+        x = x.to(torch.float32).contiguous()
+        y = y.to(torch.float32).contiguous()
+        out = torch.empty_like(x)
+        J = torch.empty(B, dtype=torch.float32, device=x.device)
+        if B == 0:
+            return out, J
+        per_row = y.shape[0] > 1
+        R = y.shape[0]
+        self._pack_all()
+        conds = self._y_lane(y)
+        if not self.fusable or self._wave_local(B):
+            return self._module_route(conds, x, rev)
+        chain, coef = self._chain(B, per_row)
+        chk = self._lib.check
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            for i, e in enumerate(self.ex):
+                chk(self.lib.hint_block_ext_coeffs(e.plan, e.arena.data_ptr(), e.packed.data_ptr(), conds[i].data_ptr(), R,
+                                                   coef[i].data_ptr(), stream), "hint_block_ext_coeffs")
+            if rev:
+                chk(self.lib.hint_chain_inverse(chain, x.data_ptr(), None, out.data_ptr(), J.data_ptr(), None, stream),
+                    "hint_chain_inverse")
+            else:
+                chk(self.lib.hint_chain_forward(chain, x.data_ptr(), None, out.data_ptr(), J.data_ptr(), None, None, stream),
+                    "hint_chain_forward")
+        return out, J
 
 
 class _LossPair:

@@ -394,6 +394,29 @@ int hint_block_pack(const hint_plan* P, const float* params, float* packed, void
     return 0;
 }
 
+int hint_block_ext_coeffs(const hint_plan* P, const float* params, const float* packed, const float* c, int32_t R,
+                          float* coef_out, void* stream) {
+    if (!P || !params || !packed || !c || !coef_out) return fail("hint_block_ext_coeffs: null argument");
+    if (R < 0) return fail("hint_block_ext_coeffs: R = %d < 0", R);
+    if (P->nodes.size() != 1 || P->nodes[0].k != 0 || P->dc == 0 || P->unit_w23.size() != 2)
+        return fail("hint_block_ext_coeffs: the plan is not a one-node coupling with an empty upper half and a condition "
+                    "(an ExternalAffineCoupling)");
+    if (R == 0) return 0;
+    const hint_node_desc& n = P->nodes[0];
+    ExtArgs a{};
+    a.params = params; a.packed = packed; a.c = c; a.coef = coef_out;
+    a.R = R; a.dc = P->dc; a.h = n.h; a.r = n.r;
+    a.NT = (n.h + 15) / 16; a.RT = (n.r + 15) / 16;
+    for (int net = 0; net < 2; ++net) {
+        a.f2[net] = P->unit_w23[net].x; a.f3[net] = P->unit_w23[net].y;
+        a.w1[net] = n.p_off[net * 6 + HINT_W1]; a.b1[net] = n.p_off[net * 6 + HINT_B1];
+        a.b2[net] = n.p_off[net * 6 + HINT_B2]; a.b3[net] = n.p_off[net * 6 + HINT_B3];
+    }
+    a.alpha = P->alpha;
+    HIP_TRY(launch_ext_coeff(a, (hipStream_t)stream));
+    return 0;
+}
+
 struct hint_pack_group {
     PackItem* d_items = nullptr;
     int n = 0, grid = 0;

@@ -72,6 +72,22 @@ int hint_chain_set_block_io(hint_chain* C, int32_t i, const float* x_in, const f
     return 0;
 }
 
+int hint_chain_set_block_affine(hint_chain* C, int32_t i, const float* coef, int64_t row_stride) {
+    if (!C) return fail("hint_chain_set_block_affine: null argument");
+    if (i < 0 || i >= C->n) return fail("hint_chain_set_block_affine: block %d out of range (chain has %d)", i, C->n);
+    if (!C->set[i]) return fail("hint_chain_set_block_affine: hint_chain_set_block(%d) comes first", i);
+    if (coef && C->host[i].tape)
+        return fail("hint_chain_set_block_affine: block %d belongs to a training chain (it has a tape); the affine step is inference only", i);
+    if (coef && row_stride != 0 && row_stride < 2 * (int64_t)C->plan->d)
+        return fail("hint_chain_set_block_affine: row_stride %lld must be 0 (broadcast) or >= 2d = %d", (long long)row_stride, 2 * C->plan->d);
+    if (coef && dispatch(C->plan, C->B).fwd == FWD_WL)
+        return fail("hint_chain_set_block_affine: this plan runs B = %d on the wave-local kernels, which have no affine step", C->B);
+    C->host[i].affine = coef;
+    C->host[i].affine_stride = coef ? row_stride : 0;
+    C->committed = false;
+    return 0;
+}
+
 // blocks gathered for part B only (they ran as launches of their own): no chained forward / inverse / part A over them
 static bool chain_gathered(const hint_chain* C) {
     for (const ChainBlock& b : C->host) if (b.x_in != nullptr || b.c_in != nullptr) return true;

@@ -79,6 +79,11 @@ struct ChainBlock {
     const float* x_in;     // or nullptr: the chain's x (first block) / the tape's top slice
     const float* c_in;     // or nullptr: the launch's c
     const float* g_add;    // or nullptr
+    // hint_chain_set_block_affine (inference chains only): an element-wise step x' = x exp(a) + b behind the block's tree (forward;
+    // the inverse undoes it in front of the tree's inverse), J +- sum a.  Row `row` reads a = affine + row * affine_stride, b = a + d:
+    // stride 0 broadcasts one row of coefficients to the batch.  nullptr: no step
+    const float* affine;
+    int64_t affine_stride;
 };
 
 // one block's share of a multi-block pack launch (hint_pack_group_*)
@@ -240,6 +245,19 @@ struct KArgs {
     int32_t lop_cnt;               // index in the ranges table of the backward boundaries' slot counts (boundary b = in front of group b; n_groups: the tail's)
     int32_t sink_lds;              // float offset in LDS of a 64-float sink for the L2 prefetch (hint_device.hpp prefetch_consumer); 0: no prefetch
     int32_t rowdw_lds;             // backward: float offset in LDS of one scratch tile (256 floats) per wavefront for the rows that compute dW1 | db1 themselves; 0: none do
+};
+
+// hint_ext_coeff_kernel (hint_ext.hip): the coefficients of a one-node block whose upper half is empty
+struct ExtArgs {
+    const float* params;
+    const float* packed;
+    const float* c;
+    float* coef;                  // [R][2][r]: alpha * atan(s), then t
+    int32_t R, dc, h, r;
+    int32_t NT, RT;               // 16-wide tiles of h and of r
+    int32_t f2[2], f3[2];         // first packed tile of W2 / W3 of the s and the t net (tiles (nt, kb) at f + nt * NT + kb)
+    int64_t w1[2], b1[2], b2[2], b3[2];   // float offsets in the flat parameter buffer
+    float alpha;
 };
 
 // ---- wave-local plans (hint_wl.hpp) ----

@@ -50,6 +50,8 @@ struct GBlock {
     const GLOBAL_AS float* x_in;
     const GLOBAL_AS float* c_in;
     const GLOBAL_AS float* g_add;
+    const GLOBAL_AS float* affine;
+    int64_t affine_stride;
 };
 template <int MODE = 0>        // 0: whichever is there; 1: the table (chained launch); 2: the by-value block
 __device__ __forceinline__ GBlock chain_block(const ChainBlock* __restrict__ chain, const ChainBlock& one, int i) {
@@ -67,6 +69,8 @@ __device__ __forceinline__ GBlock chain_block(const ChainBlock* __restrict__ cha
     g.x_in = (const GLOBAL_AS float*)b.x_in;
     g.c_in = (const GLOBAL_AS float*)b.c_in;
     g.g_add = (const GLOBAL_AS float*)b.g_add;
+    g.affine = (const GLOBAL_AS float*)b.affine;
+    g.affine_stride = b.affine_stride;
     return g;
 }
 

@@ -29,6 +29,32 @@
 
 using namespace hint;
 
+// The element-wise affine step of a chain block (hint_chain_set_block_affine): x' = x exp(a) + b behind the tree going forward,
+// x = (x' - b) exp(-a) in front of the tree's inverse; J +- sum a.  What an ExternalAffineCoupling whose s / t nets see the condition
+// only (conditional_hint_4_full.py:76-82) does once its coefficients are known.  The lane tile is in LDS; the caller barriers.
+template <bool REV>
+__device__ __forceinline__ void affine_step(float* xs, int xld, float* jac, const GLOBAL_AS float* coef, int64_t stride, int d,
+                                            float inv_d, int row0, int B, int tid, int nthreads) {
+    const int nvalid = B - row0 < ROWS ? B - row0 : ROWS;
+    for (int i = tid; i < nvalid * d; i += nthreads) {
+        const int r = fdiv(i, inv_d), j = i - r * d;
+        const GLOBAL_AS float* cr = coef + (size_t)(row0 + r) * stride;
+        const float av = cr[j], bv = cr[d + j];
+        float* px = xs + r * xld + j;
+        if (!REV) *px = expf(av) * (*px) + bv;
+        else      *px = ((*px) - bv) * __builtin_amdgcn_rcpf(expf(av));
+    }
+    if (tid < nvalid) {
+        const GLOBAL_AS float* cr = coef + (size_t)(row0 + tid) * stride;
+        float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+        int j = 0;
+        for (; j + 4 <= d; j += 4) { s0 += cr[j]; s1 += cr[j + 1]; s2 += cr[j + 2]; s3 += cr[j + 3]; }
+        for (; j < d; ++j) s0 += cr[j];
+        const float s = (s0 + s1) + (s2 + s3);
+        jac[tid] += REV ? -s : s;
+    }
+}
+
 // FLYK: the instance for plans with lean general groups (hint_plan::has_fly) - their rows make the first layer themselves, no
 // thin phase (hint_rows.hpp row_body FLY); plans without such groups keep the instance without that code (its mere presence cost
 // MINIBOONE's forward 20 us of 300)
@@ -118,6 +144,10 @@ __global__ __launch_bounds__(64 * MAX_NW) void hint_apply_kernel(
             } else if (!REV && cb > 0 && tape != nullptr) {
                 // inner block of a chain without a permutation: its input exists nowhere else
                 store_tile(tape + (size_t)(a.n_levels - 1) * a.B * a.d, XS, a.xld, a.d, row0, a.B, tid, nthreads);
+            }
+            if (REV && blk.affine != nullptr) {     // inverse of the block's affine step, before the tree's inverse
+                affine_step<true>(XS, a.xld, jac, blk.affine, blk.affine_stride, a.d, inv_d, row0, a.B, tid, nthreads);
+                lds_barrier();
             }
             STAMP((cb * a.n_groups + a.n_groups - a.n_sub) * 16 + 12)
             {   // the subtree groups' parameters and the block's thin-layer vectors -> LDS (every wavefront re-reads them for its units,
@@ -301,6 +331,10 @@ __global__ __launch_bounds__(64 * MAX_NW) void hint_apply_kernel(
                 sub_apply<true>(a, T, lds, blk, XS, false, row0, wave, lane, (cb * a.n_groups + ngen) * 16);
                 lds_barrier();
                 if (tid < ROWS) { float t = 0.f; for (int w = 0; w < a.nw; ++w) t += (lds + a.sub_misc)[w * ROWS + tid]; jac[tid] += t; }
+            }
+            if (!REV && blk.affine != nullptr) {    // the block's affine step behind its tree
+                affine_step<false>(XS, a.xld, jac, blk.affine, blk.affine_stride, a.d, inv_d, row0, a.B, tid, nthreads);
+                lds_barrier();
             }
             if (REV && perm != nullptr) {     // inverse of the fused permutation: x = x' W^T
                 f32x4 pacc[PERM_TQ];

@@ -48,6 +48,7 @@ hipError_t launch_bwd_n3(const KArgs& a, int lds_bytes, int grid, const ChainBlo
                          int n_chain, const float* x, const float* c, const float* g_z, const float* g_J,
                          float* g_x, float* g_c, float gz_scale, float gJ_const, hipStream_t stream);      // (hint_bwd3.hip: rows of <= 3 tiles)
 hipError_t set_max_lds_apply(int bytes);
+hipError_t launch_ext_coeff(const ExtArgs& a, hipStream_t stream);        // (hint_ext.hip)
 hipError_t set_max_lds_bwd(int bytes);
 hipError_t set_max_lds_bwd_n3(int bytes);
 hipError_t launch_bwd_fly(const KArgs& a, int lds_bytes, int grid, const ChainBlock& one, const ChainBlock* chain,
@@ -170,6 +171,7 @@ struct hint_plan {
     // level (its nodes as a forest of depth 0) with the lanes each level transforms
     std::vector<hint_node_desc> nodes;
     float clamp = 0.f;
+    std::vector<int2> unit_w23;                 // per unit (s, t of every node, in the plan's unit order): first packed tile of W2, of W3 (hint_block_ext_coeffs)
     std::mutex inv_mu;
     std::vector<hint_plan*> inv_levels;         // deepest level last
     uint8_t* d_inv_lower = nullptr;             // [levels][d]

@@ -476,6 +476,7 @@ static int build_plan(const hint_node_desc* nodes, int32_t n_nodes, int32_t d, i
                 u.ku = n.k; u.r = n.r; u.xoff = n.off; u.h = n.h;
                 u.lcol = sub ? gcol : gcol - g.gcol0;       // (subtree groups: one coupling-gradient buffer for all of them)
                 units.push_back(u);
+                P->unit_w23.push_back(int2{u.f2, u.f3});
                 unit_node.push_back(order[pos]);
                 wcol += 16 * NT; gcol += pad4(n.r); tiles += NT;
             }

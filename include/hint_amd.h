@@ -313,6 +313,27 @@ int hint_block_backward_rows(const hint_plan* plan, const float* params, const f
                              float* g_c, void* workspace, size_t workspace_bytes, const float* perm, float gz_scale,
                              float gJ_const, int32_t B, void* stream);
 
+/* ---- posterior sampling of the conditional model (abi 8, additive) ----
+ * For one observation y the reference's ExternalAffineCoupling ac_y_to_x_i (configs/plus_shape/conditional_hint_4_full.py:76-82)
+ * is a fixed per-lane affine map of the x lane: its s and t nets see the condition only.  model_inverse / sample_conditional
+ * (conditional_hint_4_full.py:99-113, called by train_conditional.py:36-47 and timed by rejection_sampling.py:168-213) and the
+ * x-lane density of evaluate(only_x=True) (train_conditional.py:58-100) then reduce to the coefficients of the four couplings
+ * and ONE chained launch over the x lane's hierarchical blocks.
+ *   hint_block_ext_coeffs: plan = a one-node plan whose upper half is empty (node k = 0, dc > 0: an ExternalAffineCoupling);
+ *     params / packed as for hint_block_forward (packed must be current: hint_block_pack); c [R, dc] condition rows.  Writes
+ *     coef_out [R][2][d] = (clamp * 0.636 * atan(s), t) per row (hint.py:56-60, the plan's clamp), what the coupling's forward
+ *     applies as x' = x e^a + t, J += sum a.  No argument may be NULL; R = 0 does nothing.
+ *   hint_chain_set_block_affine: block i of an INFERENCE chain (set without tape) gets an element-wise affine step behind its
+ *     tree: forward x' = x exp(a) + b, J += sum a; hint_chain_inverse undoes it in front of the tree's inverse, J -= sum a.
+ *     Row r of the batch reads a = coef + r * row_stride, b = a + d (row_stride = 0: one row of coefficients for every row of
+ *     the batch; 2d: one per row, hint_block_ext_coeffs' layout).  coef NULL removes the step.  Call after
+ *     hint_chain_set_block(i) (which clears it) and before hint_chain_commit; the pointer is captured, not copied.  Fails for a
+ *     training chain (block set with a tape), and for a chain whose plan runs this B on the wave-local kernels (narrow trees:
+ *     hint_plan_dispatch field 0), which have no affine step. */
+int hint_block_ext_coeffs(const hint_plan* plan, const float* params, const float* packed, const float* c, int32_t R,
+                          float* coef_out, void* stream);
+int hint_chain_set_block_affine(hint_chain* chain, int32_t i, const float* coef, int64_t row_stride);
+
 /* Fused gradient clamp + Adam step over a flat fp32 arena of n parameters; replaces
  *   for p in params: p.grad.data.clamp_(-5, 5)        (train_unconditional.py:140-141)
  *   torch.optim.Adam(..., eps, weight_decay).step()    (train_unconditional.py:144,174-176)

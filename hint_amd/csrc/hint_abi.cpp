@@ -353,8 +353,8 @@ int hint_debug_set_prefetch(int on) {
 int32_t hint_debug_last_lds_bytes(int32_t backward) { return g_last_lds[backward ? 1 : 0].load(std::memory_order_relaxed); }
 
 int64_t hint_plan_param_floats(const hint_plan* P) { return P ? P->param_floats : -1; }
-// + 4 KiB of slack behind the bias region (a padded row's dummy steps load up to three tiles past its last)
-int64_t hint_plan_packed_floats(const hint_plan* P) { return P ? P->packed_floats + P->n_bias + 1024 : -1; }
+// + PACK_SLACK floats of zeros behind the bias region (a padded row's dummy steps load up to three tiles past its last)
+int64_t hint_plan_packed_floats(const hint_plan* P) { return P ? P->packed_floats + P->n_bias + PACK_SLACK : -1; }
 
 static inline int rows_padded(int B) { return (B + ROWS - 1) / ROWS * ROWS; }
 int64_t hint_plan_tape_floats(const hint_plan* P, int32_t B) {
@@ -433,7 +433,7 @@ int hint_pack_group_create(const hint_plan* const* plans, const float* const* pa
         PackItem& q = items[i];
         q.segs = P->d_segs; q.ptiles = P->d_ptiles; q.bmap = P->d_bmap; q.params = params[i]; q.packed = packed[i];
         q.bias_off = P->packed_floats; q.n_tiles = P->n_ptiles; q.n_bias = P->n_bias; q.grid_begin = grid; q.pad = 0;
-        grid += P->n_ptiles + (P->n_bias + 255) / 256;
+        grid += P->n_ptiles + (P->n_bias + PACK_SLACK + 255) / 256;
     }
     hint_pack_group* G = new hint_pack_group();
     G->n = n; G->grid = grid;

@@ -48,6 +48,9 @@ constexpr int LV_REGS = 4;      // hint_bwd.hip holds a prefetched [16, d] tile 
 // vector-layout segments of a block form two contiguous "thin blobs" (forward, backward) at the start of
 // the packed buffer, small enough to be staged in LDS once per block.
 // ---------------------------------------------------------------------------------------
+// floats of zeros behind the packed bias region (a padded row's dummy steps load up to three tiles past its last); the pack
+// writes them, so that every float of the packed buffer is defined
+constexpr int PACK_SLACK = 1024;
 struct PackSeg {
     int64_t dst;        // float offset of the segment in the packed buffer
     int64_t src;        // float offset into the flat parameter buffer
@@ -55,7 +58,7 @@ struct PackSeg {
     int32_t NB;         // k-blocks per n-tile (vector layout: Kp)
     int32_t ld;         // row stride of the source tensor
     int32_t trans;      // 0: Wlog[n][k] = P[src + n*ld + k];  1: Wlog[n][k] = P[src + k*ld + n]
-    int32_t kmap;       // layout: 0 fragment, 2 vector
+    int32_t kmap;       // layout: 0 fragment, 2 vector, 3 zeros (N floats: the padding behind a vector blob)
     int32_t tile_begin; // index of this segment's first n-tile in the global n-tile list
     int32_t pad;
     int64_t src2;       // vector layout: float offset of a bias tensor stored as vector K of every tile, or -1

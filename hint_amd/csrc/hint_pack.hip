@@ -11,12 +11,18 @@ __device__ __forceinline__ void pack_body(int bid, const PackSeg* __restrict__ s
     if (bid >= n_tiles) {
         // trailing workgroups: biases b1, b2, b3 per unit, zero padded to 16
         const int i = (bid - n_tiles) * 256 + (int)threadIdx.x;
+        // (then the PACK_SLACK floats of zeros behind them)
         if (i < n_bias) { const int off = bmap[i]; packed[bias_off + i] = off >= 0 ? P[off] : 0.f; }
+        else if (i < n_bias + PACK_SLACK) packed[bias_off + i] = 0.f;
         return;
     }
     const int2 pt = ptiles[bid];
     const PackSeg sg = segs[pt.x];
     const int nt = pt.y;
+    if (sg.kmap == 3) {
+        for (int idx = (int)threadIdx.x; idx < sg.N; idx += 256) packed[sg.dst + idx] = 0.f;
+        return;
+    }
     if (sg.kmap == 2) {
         // vector layout (thin layers): dst[(nt*KV + k)*16 + f] = Wlog[nt*16 + f][k] for k < K, zero up to Kp = NB;
         // vector Kp: the bias
@@ -158,7 +164,7 @@ hipError_t launch_inv_rowmat(const float* x, const float* P, float* y, long n, i
 
 hipError_t launch_pack(const PackSeg* segs, const int2* ptiles, int n_tiles, const int32_t* bmap, int n_bias,
                        long bias_off, const float* params, float* packed, hipStream_t stream) {
-    const int grid = n_tiles + (n_bias + 255) / 256;
+    const int grid = n_tiles + (n_bias + PACK_SLACK + 255) / 256;
     if (grid > 0)
         hipLaunchKernelGGL(hint_pack_kernel, dim3(grid), dim3(256), 0, stream, segs, ptiles, n_tiles, bmap, n_bias,
                            bias_off, params, packed);

@@ -572,6 +572,16 @@ static int build_plan(const hint_node_desc* nodes, int32_t n_nodes, int32_t d, i
     P->n_units = (int)units.size();
     P->WT = wcol;
     P->ST = gcol;
+    // the padding of the two vector blobs to whole tiles: zero segments, so that the pack writes every float of the buffer
+    const int64_t holes[2][2] = {{cur_f, blob_f_pad}, {cur_b, blob_f_pad + blob_b_pad}};
+    for (const auto& hole : holes) {
+        if (hole[1] <= hole[0]) continue;
+        PackSeg sg{};
+        sg.dst = hole[0]; sg.src = 0; sg.src2 = -1; sg.N = (int32_t)(hole[1] - hole[0]); sg.kmap = 3;
+        sg.tile_begin = (int)ptiles.size();
+        ptiles.push_back(int2{(int)segs.size(), 0});
+        segs.push_back(sg);
+    }
     P->param_floats = (pmax + 3) / 4 * 4;
     P->packed_floats = packed;
     P->n_bias = (int)bmap.size();

@@ -22,6 +22,9 @@
  *     it may be shared by threads.  Parameters are passed per call as ONE flat fp32 buffer
  *     whose layout the caller described at plan creation (p_off, in floats), because the
  *     reference loops rebind p.data / call .to() (train_unconditional.py:165-167).
+ *   - outputs, tapes, workspaces and packed buffers need no initialisation: only buffers documented
+ *     as accumulated (g_params with accumulate != 0, loss_acc) are read before they are written
+ *     (tests/test_gpu_poison.py runs every entry point on NaN- and junk-filled memory).
  */
 #ifndef HINT_AMD_H
 #define HINT_AMD_H
@@ -79,7 +82,8 @@ void hint_plan_destroy(hint_plan* plan);
  * variant's, so query them with the B you will run.) */
 int64_t hint_plan_param_floats(const hint_plan* plan);
 /* floats of the packed-weight buffer (both subnets of every node, forward and transposed
- * copies, in MFMA fragment order, zero padded). */
+ * copies, in MFMA fragment order, zero padded, and 1024 floats of zeros at the end); the pack writes
+ * every float of it. */
 int64_t hint_plan_packed_floats(const hint_plan* plan);
 /* floats of the forward "tape" for a batch of B rows, recorded by the training forward and read
  * by the backward pass: per tree level one [B,d] snapshot of the lane tensor as that level saw it

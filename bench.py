@@ -2,7 +2,7 @@
 """Benchmark of the HINT coupling-flow training step on MI355X (BASELINE.json metric:
 training samples/s + mean NLL, UCI POWER d=6, batch 4096 per GPU, 1/2/4/8 GPUs).
 
-    python bench.py --gpus 1 --steps 200 --warmup 20
+    python bench.py --gpus 1 --steps 200 --warmup 20 [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W [--scaling strong]
 
@@ -15,11 +15,14 @@ Timing: after the warm-up the region "exactly --steps steps between barrier + sy
 --reps times (default 7); `value` / `ms_per_step` are the MEDIAN repetition (max over ranks per
 repetition), `rep_min_ms` / `rep_max_ms` / `reps` say how far the others lay.
 
-Rank 0 prints ONE JSON line; it also carries the sampling direction (`inverse_samples_per_sec`, the whole
-chain x = f^-1(z) in one launch), the roofline of the step's dominant kernel, the CPU baseline and - on
-the default single-GPU run - `other_workloads`: BASELINE.json's other configs (cfg 3 GAS, cfg 5 MINIBOONE,
-the d = 100 lane of cfg 4 and cfg 4's two-lane conditional model) timed the same way, each with its
-dominant kernel's roofline and an NLL cross-check against the CPU oracle.
+Rank 0 prints ONE JSON line.  A plain run does only what the headline needs: it sets up, warms up, times
+the steps, writes --dump-outputs and prints the line.  --full adds everything else, after the headline's
+timed region: the sampling direction (`inverse_samples_per_sec`, the whole chain x = f^-1(z) in one launch),
+the roofline of the step's dominant kernel (kernel timings in un-captured steps, HBM bytes measured under
+rocprofv3), the CPU baseline, the NLL cross-checks against the CPU oracle and - on a single-GPU run of the
+default workload - `other_workloads`: BASELINE.json's other configs (cfg 3 GAS, cfg 5 MINIBOONE, the
+d = 100 lane of cfg 4 and cfg 4's two-lane conditional model) timed the same way, each with its dominant
+kernel's roofline and an NLL cross-check, and `extra.module_path`, the drop-in module route.
 
 --dump-outputs DIR: right after the headline's timed region, rank 0 writes what the last timed step handed its caller
 (see dump_outputs) as DIR/<name>.npy.  Weights, batch, permutations and the in-kernel noise stream are all seeded, so the
@@ -535,7 +538,7 @@ def run_flow(args, name, rank, world, dev, use_dist, dist, headline):
     # the step's launches inside real (un-captured) steps, HIP events between them: what the roofline
     # is priced on.  Every rank runs them (the steps contain the gradient all-reduce).
     in_step = {}
-    if trainer._chainable:
+    if args.full and trainer._chainable:
         for k in range(3 + 20):
             t = trainer.timed_step(x)
             if k >= 3:
@@ -543,12 +546,12 @@ def run_flow(args, name, rank, world, dev, use_dist, dist, headline):
                     in_step[n_] = in_step.get(n_, 0.0) + v_ / 20
     # mean NLL of the weights as they are NOW (after every step above), on this rank's resident rows: the same weights the
     # CPU oracle re-evaluates below (`nll_rel_err`)
-    nll = trainer.nll(x)
+    nll = trainer.nll(x) if args.full else None
 
     # the sampling direction: x = f^-1(z) through the whole chain, one launch (hint_chain_inverse), on the same
     # resident rows; HIP events on the launch stream
     inv_us = None
-    if trainer._chainable and headline:
+    if args.full and trainer._chainable and headline:
         from hint_amd import _lib
         lib = _lib.load()
         chain = trainer._chain_infer(B)
@@ -575,7 +578,6 @@ def run_flow(args, name, rank, world, dev, use_dist, dist, headline):
 
     if rank != 0:
         return None
-    F = flops_per_sample_block(d, cfg["c_internal"])
     nb = cfg["n_blocks"]                           # blocks one launch processes
     legs = kernel_legs(trainer, x) if (args.legs and headline) else {}
     res = {
@@ -587,11 +589,19 @@ def run_flow(args, name, rank, world, dev, use_dist, dist, headline):
                    "global_batch": B * world, "parallelism": f"dp{world}", "hip_graph": not args.no_graph, "steps_per_graph": spg,
                    "input": "batch resident in the captured step's input buffer (no per-step copy)",
                    **runtime_info(world, use_dist, dist, trainer)},
-        "mean_nll_nats": nll, "last_step_loss": loss_last,
+        "last_step_loss": loss_last,
     }
     res.update(reps_info)
     if dumped is not None:
         res["dumped_outputs"] = {"dir": args.dump_outputs, "elements": dumped}
+    if world > 1:
+        res["config"]["rows_per_gpu"] = B
+    if legs:
+        res["kernels_hot_loop_us"] = legs         # back-to-back loops of one kernel (caches hot)
+    if not args.full:                              # a plain run's line: the headline alone
+        return res
+    res["mean_nll_nats"] = nll
+    F = flops_per_sample_block(d, cfg["c_internal"])
     # HBM traffic per launch comes from rocprofv3 PMC passes run separately (tools/refresh_profiles.sh); it is NOT measured in
     # this process - the line says where it was read from
     pmc, pmc_file = newest_pmc(name) if B == cfg["batch"] else ({}, None)
@@ -669,10 +679,6 @@ def run_flow(args, name, rank, world, dev, use_dist, dist, headline):
         res["inverse_samples_per_sec"] = B * world / (inv_us * 1e-6)
         res["inverse"] = {"what": f"x = f^-1(z), {nb} blocks in one launch of {inv_name}, {B} rows per GPU, no tape",
                           "avg_launch_us": inv_us, "roofline": mfma_roofline(inv_name, inv_us, F * B * nb)}
-    if world > 1:
-        res["config"]["rows_per_gpu"] = B
-    if legs:
-        res["kernels_hot_loop_us"] = legs         # back-to-back loops of one kernel (caches hot)
     if world == 1 and not args.no_cpu_baseline:
         if headline:
             res["cpu_baseline"] = cpu_baseline(dict(cfg, batch=B))
@@ -770,7 +776,7 @@ def run_conditional(args, name, rank, world, dev, use_dist, dist, headline):
     res.update(reps_info)
     if dumped is not None:
         res["dumped_outputs"] = {"dir": args.dump_outputs, "elements": dumped}
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         if headline:
             res["cpu_baseline"] = cpu_baseline_conditional(model, cfg, x, y)
             res["speedup_vs_cpu"] = res["value"] / res["cpu_baseline"]["value"]
@@ -789,14 +795,17 @@ def main():
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--steps-per-graph", type=int, default=1,
                     help="training iterations per hipGraph replay (FlowTrainer.step_many; one process only)")
-    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU baseline and the oracle cross-checks")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, measure and check everything else: CPU baselines, oracle NLL cross-checks, kernel "
+                         "timings and rooflines, the sampling direction, BASELINE's other configs and the module route")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline and the oracle cross-checks")
     ap.add_argument("--no-other-workloads", action="store_true",
-                    help="default single-GPU run: do not time BASELINE's other configs after the headline")
+                    help="--full, single-GPU default workload: do not time BASELINE's other configs after the headline")
     ap.add_argument("--no-live-traffic", action="store_true",
-                    help="default single-GPU run: do not measure the headline kernels' HBM bytes under rocprofv3 (two child processes); "
+                    help="--full, single-GPU run: do not measure the headline kernels' HBM bytes under rocprofv3 (two child processes); "
                          "roofline.traffic then comes from the committed counter summary")
     ap.add_argument("--no-module-path", action="store_true",
-                    help="default single-GPU run: do not time the drop-in module route (extra.module_path) after the headline")
+                    help="--full, single-GPU default workload: do not time the drop-in module route (extra.module_path) after the headline")
     ap.add_argument("--batch", type=int, default=0,
                     help="rows per GPU instead of the workload's (small-batch measurements; the config line says so)")
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
@@ -835,7 +844,7 @@ def main():
 
     # the other BASELINE configs, same protocol (their own warm-up, the same --steps / --reps), after the headline's timed
     # region: single-GPU default run only - the multi-GPU lines stay what the contract asks for
-    if rank == 0 and world == 1 and not use_dist and args.workload == "power_hint_8" and args.batch == 0 \
+    if args.full and rank == 0 and world == 1 and not use_dist and args.workload == "power_hint_8" and args.batch == 0 \
             and args.scaling == "weak" and not args.no_other_workloads:
         others = {}
         keep = ("value", "unit", "ms_per_step", "reps", "rep_min_ms", "rep_max_ms", "roofline", "roofline_whole_step",
@@ -855,7 +864,7 @@ def main():
         res["other_workloads"] = others
     # the DROP-IN module route (north_star: "drops into train_unconditional.py unchanged"): the reference loop body verbatim on
     # hint_amd's nn.Modules with torch.optim.Adam and the per-parameter clamp - outside the headline's timed region
-    if rank == 0 and world == 1 and not use_dist and args.workload == "power_hint_8" and args.batch == 0 \
+    if args.full and rank == 0 and world == 1 and not use_dist and args.workload == "power_hint_8" and args.batch == 0 \
             and args.scaling == "weak" and not args.no_module_path:
         try:
             sys.path.insert(0, os.path.join(ROOT, "tools"))

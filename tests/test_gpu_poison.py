@@ -746,6 +746,7 @@ def engines_of(*modules):
 
 def product_run(fill, B=1000):
     """the product's eager paths with torch's caching allocator primed with freed blocks that hold `fill`: -> every result"""
+    import gc
     import hint_amd
     from hint_amd import _lib
     lib = _lib.load()
@@ -770,6 +771,9 @@ def product_run(fill, B=1000):
         for n in (tape_n, ws_b // 4, lib.hint_plan_packed_floats(e.plan), e.total, B * e.d, B * max(e.dc, 1), B, 128):
             sizes.update({n, n + 7, int(n * 1.1) + 1, max(1, int(n * 0.9))})
     tape_n = engines_of(flow)[0].sizes(B)[0]
+    # a flow and its ChainRunner refer to each other: what an earlier run (or test) left is freed by the cycle collector
+    # alone, and until it runs empty_cache cannot release the segments it holds - the probe below may then land on stale data
+    gc.collect()
     torch.cuda.synchronize()
     torch.cuda.empty_cache()
     bits = NAN_BITS if fill == "nan" else 0

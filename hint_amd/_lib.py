@@ -18,6 +18,11 @@ class HintAmdError(RuntimeError):
     pass
 
 
+class AdamSeg(C.Structure):
+    """mirror of `hint_adam_seg` (include/hint_amd.h)"""
+    _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("n", C.c_int64)]
+
+
 class NodeDesc(C.Structure):
     """mirror of `hint_node_desc` (include/hint_amd.h)"""
     _fields_ = [("off", C.c_int32), ("D", C.c_int32), ("k", C.c_int32), ("r", C.c_int32),
@@ -85,6 +90,10 @@ _PROTOS = {
     "hint_adam_step_dev": (C.c_int, [C.c_void_p] * 4 + [C.c_int64, C.c_void_p] + [C.c_float] * 6 + [C.c_int32, C.c_void_p]),
     "hint_adam_step": (C.c_int, [C.c_void_p] * 4 + [C.c_int64, C.c_int32] + [C.c_float] * 7 + [C.c_int32,
                                                                                                  C.c_void_p]),
+    "hint_adam_multi_create": (C.c_int, [C.POINTER(AdamSeg), C.c_int32, C.POINTER(C.c_void_p)]),
+    "hint_adam_multi_step": (C.c_int, [C.c_void_p, C.c_int32] + [C.c_float] * 7 + [C.c_int32, C.c_void_p]),
+    "hint_adam_multi_destroy": (None, [C.c_void_p]),
+    "hint_adam_multi_chunk": (C.c_int64, [C.POINTER(AdamSeg), C.c_int32, C.c_int64, C.c_int32]),
 }
 
 

@@ -609,4 +609,112 @@ int hint_adam_step_dev(float* params, float* grads, float* exp_avg, float* exp_a
     return 0;
 }
 
+// ---- the step over a table of segments (hint_adam_multi_*) ----
+struct hint_adam_multi {
+    hint::AdamSeg* segs = nullptr;        // device
+    hint::AdamChunk* chunks = nullptr;    // device
+    int32_t n_segs = 0;
+    int64_t n_chunks = 0;
+    int device = -1, num_cu = 0;
+};
+static_assert(sizeof(hint::AdamSeg) == sizeof(hint_adam_seg), "AdamSeg mirrors hint_adam_seg");
+
+// argument checks shared by hint_adam_multi_chunk and hint_adam_multi_create (no device call)
+static int adam_multi_check(const char* who, const hint_adam_seg* segs, int32_t n_segs) {
+    if (n_segs < 0) return fail("%s: n_segs must be >= 0", who);
+    if (n_segs > 0 && !segs) return fail("%s: null segment table", who);
+    for (int32_t i = 0; i < n_segs; ++i) {
+        const hint_adam_seg& s = segs[i];
+        if (s.n < 0) return fail("%s: segment %d has negative n (%lld)", who, i, (long long)s.n);
+        if (!s.p || !s.g || !s.m || !s.v) return fail("%s: segment %d has a null pointer", who, i);
+        if ((((uintptr_t)s.p | (uintptr_t)s.g | (uintptr_t)s.m | (uintptr_t)s.v) & 3) != 0)
+            return fail("%s: segment %d has a pointer that is not 4-byte aligned", who, i);
+    }
+    // two segments whose p ranges overlap would take two steps (or race): sort by address, compare neighbours
+    std::vector<int32_t> order;
+    for (int32_t i = 0; i < n_segs; ++i)
+        if (segs[i].n > 0) order.push_back(i);
+    std::sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return (uintptr_t)segs[a].p < (uintptr_t)segs[b].p; });
+    for (size_t k = 1; k < order.size(); ++k) {
+        const hint_adam_seg& a = segs[order[k - 1]];
+        if ((uintptr_t)a.p + 4 * (uintptr_t)a.n > (uintptr_t)segs[order[k]].p)
+            return fail("%s: the p ranges of segments %d and %d overlap", who, order[k - 1], order[k]);
+    }
+    return 0;
+}
+
+// chunk c of the table: floats [off, off + len) of segment seg.  The first chunk of a segment whose four pointers agree
+// modulo 16 also takes the floats in front of the first 16-byte boundary, so that every later chunk starts on one.
+static void adam_multi_cut(const hint_adam_seg* segs, int32_t n_segs, std::vector<hint::AdamChunk>& out) {
+    for (int32_t i = 0; i < n_segs; ++i) {
+        const hint_adam_seg& s = segs[i];
+        const uintptr_t mis = (uintptr_t)s.p & 15;
+        const bool same = ((uintptr_t)s.g & 15) == mis && ((uintptr_t)s.m & 15) == mis && ((uintptr_t)s.v & 15) == mis;
+        const int64_t head = same ? (int64_t)(((16 - mis) & 15) >> 2) : 0;
+        for (int64_t off = 0; off < s.n;) {
+            const int64_t len = std::min<int64_t>(s.n - off, hint::ADAM_CHUNK + (off == 0 ? head : 0));
+            out.push_back(hint::AdamChunk{i, (int32_t)len, off});
+            off += len;
+        }
+    }
+}
+
+int64_t hint_adam_multi_chunk(const hint_adam_seg* segs, int32_t n_segs, int64_t c, int32_t field) {
+    if (adam_multi_check("hint_adam_multi_chunk", segs, n_segs)) return -1;
+    std::vector<hint::AdamChunk> ch;
+    adam_multi_cut(segs, n_segs, ch);
+    if (c == -1) return (int64_t)ch.size();
+    if (c < 0 || c >= (int64_t)ch.size() || field < 0 || field > 2) {
+        fail("hint_adam_multi_chunk: no chunk %lld / field %d (%lld chunks)", (long long)c, field, (long long)ch.size());
+        return -1;
+    }
+    return field == 0 ? ch[c].seg : field == 1 ? ch[c].off : ch[c].len;
+}
+
+int hint_adam_multi_create(const hint_adam_seg* segs, int32_t n_segs, hint_adam_multi_out out) {
+    if (!out) return fail("hint_adam_multi_create: null argument");
+    *out = nullptr;
+    if (adam_multi_check("hint_adam_multi_create", segs, n_segs)) return 1;
+    std::vector<hint::AdamChunk> ch;
+    adam_multi_cut(segs, n_segs, ch);
+    hint_adam_multi* h = new hint_adam_multi();
+    h->n_segs = n_segs;
+    h->n_chunks = (int64_t)ch.size();
+    if (h->n_chunks > 0) {
+        hipError_t e = hipGetDevice(&h->device);
+        if (e == hipSuccess) e = hipMalloc((void**)&h->segs, sizeof(hint::AdamSeg) * (size_t)n_segs);
+        if (e == hipSuccess) e = hipMalloc((void**)&h->chunks, sizeof(hint::AdamChunk) * ch.size());
+        if (e == hipSuccess) e = hipMemcpy(h->segs, segs, sizeof(hint::AdamSeg) * (size_t)n_segs, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(h->chunks, ch.data(), sizeof(hint::AdamChunk) * ch.size(), hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            hint_adam_multi_destroy(h);
+            return fail("hint_adam_multi_create: %s", hipGetErrorString(e));
+        }
+        h->num_cu = adam_num_cu();
+    }
+    *out = h;
+    return 0;
+}
+
+int hint_adam_multi_step(const hint_adam_multi* h, int32_t step, float lr, float beta1, float beta2, float eps,
+                         float weight_decay, float grad_scale, float grad_clamp, int32_t zero_grads, void* stream) {
+    if (!h) return fail("hint_adam_multi_step: null argument");
+    if (step < 1) return fail("hint_adam_multi_step: step must be >= 1");
+    if (h->n_chunks == 0) return 0;
+    // bias corrections in double like torch.optim.Adam's python scalars (hint_adam_step's expressions)
+    const double bc1 = 1.0 - std::pow((double)beta1, (double)step);
+    const double bc2 = 1.0 - std::pow((double)beta2, (double)step);
+    HIP_TRY(launch_adam_multi(h->segs, h->chunks, (long)h->n_chunks, (float)((double)lr / bc1), beta1, beta2,
+                              (float)(1.0 / std::sqrt(bc2)), eps, weight_decay, grad_scale,
+                              grad_clamp > 0.f ? grad_clamp : 3.0e38f, zero_grads ? 1 : 0, h->num_cu, (hipStream_t)stream));
+    return 0;
+}
+
+void hint_adam_multi_destroy(const hint_adam_multi* h) {
+    if (!h) return;
+    if (h->segs) (void)hipFree(h->segs);
+    if (h->chunks) (void)hipFree(h->chunks);
+    delete h;
+}
+
 }  // extern "C"

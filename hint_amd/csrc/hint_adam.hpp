@@ -3,6 +3,7 @@
 // bit for bit.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stdint.h>
 
 namespace hint {
 
@@ -13,6 +14,12 @@ struct AdamFuse {
     float* p; float* m; float* v; const float* st;
     float b1, b2, eps, wd, gscale, gclamp;
 };
+
+// hint_adam_multi_kernel's tables (device memory owned by a hint_adam_multi handle).  AdamSeg mirrors hint_adam_seg of the C ABI;
+// a chunk is `len` floats of segment `seg` from float offset `off`.
+struct AdamSeg { float* p; float* g; float* m; float* v; int64_t n; };
+struct AdamChunk { int32_t seg; int32_t len; int64_t off; };
+constexpr int ADAM_CHUNK = 1024;    // floats: one f32x4 per lane of a 256-thread workgroup
 
 __device__ __forceinline__ void adam_update(float& p, float& m, float& v, float g, float lr_t, float b1, float b2,
                                             float inv_sqrt_bc2, float eps, float wd, float gscale, float gclamp) {

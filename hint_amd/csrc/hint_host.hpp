@@ -67,6 +67,9 @@ hipError_t set_max_lds_wl_bwd(int bytes);
 hipError_t launch_adam(float* p, float* g, float* m, float* v, long n, float lr_t, float b1, float b2,
                        float inv_sqrt_bc2, float eps, float wd, float gscale, float gclamp, int zero_grads,
                        int num_cu, const float* dev_state, hipStream_t stream);
+hipError_t launch_adam_multi(const AdamSeg* segs, const AdamChunk* chunks, long n_chunks, float lr_t, float b1, float b2,
+                             float inv_sqrt_bc2, float eps, float wd, float gscale, float gclamp, int zero_grads, int num_cu,
+                             hipStream_t stream);
 }  // namespace hint
 
 namespace hint {

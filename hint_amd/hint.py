@@ -50,6 +50,9 @@ _PARAM_GRADS = os.environ.get("HINT_PARAM_GRADS", "direct")
 # set_pack_cache(True) / HINT_PACK_CACHE=1 skips it when no parameter's (`data_ptr`, `_version`) moved since the last pack -
 # for loops that only ever change weights through optimizers / load_state_dict / `p.data = ...`.
 _PACK_CACHE = os.environ.get("HINT_PACK_CACHE", "0") not in ("", "0")
+# ... and through hint_amd.ClampAdam, whose kernel writes the weights through raw pointers: every step advances this
+# process-wide generation, which is part of the pack key.
+_WEIGHT_GEN = 0
 
 
 def set_param_grad_mode(mode: str) -> str:
@@ -65,6 +68,12 @@ def set_pack_cache(on: bool) -> bool:
     global _PACK_CACHE
     prev, _PACK_CACHE = _PACK_CACHE, bool(on)
     return prev
+
+
+def weights_changed():
+    """some parameter's storage was written behind torch's back (a kernel of this package): no cached pack is current"""
+    global _WEIGHT_GEN
+    _WEIGHT_GEN += 1
 
 
 # ---- where a step's time goes (bench.py's module_path entry): host clock + HIP events around hint_amd's entry points ----
@@ -372,7 +381,7 @@ class _Engine:
             self._pack_key = None
         _mark_launch()
         if _PACK_CACHE:
-            key = [self._gathers] + [(p.data_ptr(), p._version) for p in self.params]
+            key = [self._gathers, _WEIGHT_GEN] + [(p.data_ptr(), p._version) for p in self.params]
             if key == self._pack_key:
                 return
             self._pack_key = key

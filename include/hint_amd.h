@@ -357,6 +357,35 @@ int hint_adam_step_dev(float* params, float* grads, float* exp_avg, float* exp_a
                        float weight_decay, float grad_scale, float grad_clamp, int32_t zero_grads,
                        void* stream);
 
+/* The same clamp + Adam step for a model whose parameters live in MANY buffers (one arena per block, the twelve modules of
+ * the conditional model, tensors of other modules): one launch over a table of segments, for a training loop that keeps its
+ * own statements and only replaces
+ *   for p in params_trainable: p.grad.data.clamp_(-5.00, 5.00)     (train_unconditional.py:140-141, train_conditional.py:146-147)
+ *   optim.step()                                                     (train_unconditional.py:144, train_conditional.py:150;
+ *                                                                     the torch.optim.Adam of :174-176 / :180-182)
+ * A segment is n consecutive floats of parameters, gradients and both moments; every element takes the arithmetic of the
+ * flat-arena step above, bit for bit.  Pointers need 4-byte alignment only: where the four pointers of a segment agree
+ * modulo 16 the step moves 16 bytes per lane, elsewhere single floats.  n may be 0.  The p ranges of two segments must not
+ * overlap.  The table is copied to device memory when the handle is created (synchronous; the current device); the buffers
+ * themselves are read at each step only, and only p, g, m, v - nothing else needs initialising.
+ *   multi_create   rejects (before any device call) a null pointer, a negative n, a misaligned pointer, overlapping p ranges;
+ *                  n_segs == 0 gives a valid handle whose step does nothing.
+ *   multi_step     step, lr, ..., zero_grads as in the flat-arena step; stream-ordered, no host-device traffic.
+ *   multi_chunk    host only: how multi_create cuts the segments into the work items of the launch.  c == -1 returns their
+ *                  number; 0 <= c < number returns field 0 (segment), 1 (first float) or 2 (floats) of chunk c; -1 on an error.
+ *                  Every float of every segment is in exactly one chunk; a chunk has at most 1024 (+3 in front of a segment's
+ *                  first 16-byte boundary) floats.
+ * None of these has a caller's device buffer among its parameters: the buffers are named by the table.  (out is host memory:
+ * the handle.) */
+typedef struct hint_adam_seg { float* p; float* g; float* m; float* v; int64_t n; } hint_adam_seg;
+typedef struct hint_adam_multi hint_adam_multi;
+typedef hint_adam_multi** hint_adam_multi_out;
+int hint_adam_multi_create(const hint_adam_seg* segs, int32_t n_segs, hint_adam_multi_out out);
+int hint_adam_multi_step(const hint_adam_multi* h, int32_t step, float lr, float beta1, float beta2, float eps,
+                         float weight_decay, float grad_scale, float grad_clamp, int32_t zero_grads, void* stream);
+void hint_adam_multi_destroy(const hint_adam_multi* h);
+int64_t hint_adam_multi_chunk(const hint_adam_seg* segs, int32_t n_segs, int64_t c, int32_t field);
+
 int hint_abi_version(void);
 const char* hint_last_error(void);
 /* what the library binary was built with and runs with: "libhint_amd abi N, gfx950, HIP x.y.z, clang ..., src <12 hex digits: hash

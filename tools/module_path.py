@@ -1,13 +1,14 @@
 """Throughput of the DROP-IN module path: the statements of /root/reference/train_unconditional.py:114-144 executed verbatim on
 hint_amd's nn.Modules (autograd route, torch.optim.Adam, the per-parameter clamp), and where a step's time goes.
-    python tools/module_path.py [workload] [steps] [--per-block] [--profile]
+    python tools/module_path.py [workload] [steps] [--per-block] [--profile] [--optim clampadam]
+--optim clampadam: the same loop with hint_amd.ClampAdam(..., grad_clamp=5.0) in place of the clamp loop and torch.optim.Adam.
 bench.py imports run() for its `extra.module_path` entry."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 
 
-def run(name="power_hint_8", steps=60, warmup=10, per_block=False, dev=None, profile=False):
+def run(name="power_hint_8", steps=60, warmup=10, per_block=False, dev=None, profile=False, optim_name="adam"):
     import bench, hint_amd
     from hint_amd import hint as H
     dev = dev or torch.device("cuda:0")
@@ -20,7 +21,14 @@ def run(name="power_hint_8", steps=60, warmup=10, per_block=False, dev=None, pro
     params_trainable = list(filter(lambda p: p.requires_grad, model.parameters()))
     for p in params_trainable:            # train_unconditional.py:165-167
         p.data = 0.005 * torch.randn_like(p.data)
-    optim = torch.optim.Adam(params_trainable, lr=0.01 * 3e-2, betas=(0.9, 0.95), eps=1e-4, weight_decay=1.86e-5)
+    if optim_name not in ("adam", "clampadam"):
+        raise ValueError("--optim takes adam or clampadam")
+    fused = optim_name == "clampadam"
+    if fused:
+        optim = hint_amd.ClampAdam(params_trainable, lr=0.01 * 3e-2, betas=(0.9, 0.95), eps=1e-4, weight_decay=1.86e-5,
+                                   grad_clamp=5.0)
+    else:
+        optim = torch.optim.Adam(params_trainable, lr=0.01 * 3e-2, betas=(0.9, 0.95), eps=1e-4, weight_decay=1.86e-5)
     x0 = torch.randn(B, d, device=dev)
     loss_history = []
 
@@ -36,8 +44,9 @@ def run(name="power_hint_8", steps=60, warmup=10, per_block=False, dev=None, pro
         loss_total = sum(batch_losses)
         loss_history.append([l.item() for l in batch_losses])
         loss_total.backward()
-        for p in params_trainable:
-            p.grad.data.clamp_(-5.00, 5.00)
+        if not fused:
+            for p in params_trainable:
+                p.grad.data.clamp_(-5.00, 5.00)
         optim.step()
 
     for _ in range(warmup):
@@ -58,6 +67,7 @@ def run(name="power_hint_8", steps=60, warmup=10, per_block=False, dev=None, pro
     torch.cuda.synchronize()
     split = H.profile_stop(prof, n2) if prof is not None else {}
     out = {"workload": f"{name}: d={d}, {cfg['n_blocks']} blocks, batch {B}", "route": "per block (FrEIA-style graph walk)" if per_block else "HintFlow",
+           "optim": "hint_amd.ClampAdam" if fused else "clamp loop + torch.optim.Adam",
            "samples_per_sec": B / wall, "ms_per_step": wall * 1e3, "steps": steps, "last_losses": loss_history[-1], **split}
     if profile:
         import cProfile, pstats, io
@@ -71,9 +81,15 @@ def run(name="power_hint_8", steps=60, warmup=10, per_block=False, dev=None, pro
 
 
 if __name__ == "__main__":
-    args = [a for a in sys.argv[1:] if not a.startswith("--")]
-    r = run(args[0] if args else "power_hint_8", int(args[1]) if len(args) > 1 else 60, per_block="--per-block" in sys.argv,
-            profile="--profile" in sys.argv)
+    argv = sys.argv[1:]
+    optim_name = "adam"
+    if "--optim" in argv:
+        i = argv.index("--optim")
+        optim_name = argv[i + 1]
+        del argv[i:i + 2]
+    args = [a for a in argv if not a.startswith("--")]
+    r = run(args[0] if args else "power_hint_8", int(args[1]) if len(args) > 1 else 60, per_block="--per-block" in argv,
+            profile="--profile" in argv, optim_name=optim_name)
     cp = r.pop("cprofile", None)
     import json
     print(json.dumps(r))

@@ -25,7 +25,7 @@ import torch
 import torch.nn as nn
 
 from .flow import FixedOrthogonal
-from .hint import HierarchicalAffineCouplingBlock, HierarchicalAffineCouplingTree, HintAmdError
+from .hint import HierarchicalAffineCouplingBlock, HierarchicalAffineCouplingTree, HintAmdError, _as_input
 
 
 class F_fully_connected:          # marker for F_class=...; see the module docstring
@@ -607,9 +607,17 @@ class ConditionalFlowTrainer:
         import os
         return torch.distributed.get_backend(self.group) == "nccl" and os.environ.get("HINT_GRAPH_ALLREDUCE", "1") != "0"
 
+    def _inputs(self, x, y):
+        """the input contract (hint._as_input, as FlowTrainer): x [B, nx] and y [B, ny] as contiguous fp32 tensors on the trainer's
+        device - copies only where the arguments are not that already; raises HintAmdError before anything is launched"""
+        x = _as_input(x, "x", self.device, self.flow.ndim_x)
+        y = _as_input(y, "y", self.device, self.flow.ndim_y, rows=x.shape[:-1])
+        return x, y
+
     def step(self, x: torch.Tensor, y: torch.Tensor):
         """one iteration on this rank's rows; returns a pair that unpacks to the device scalars (0.5*|z|^2 mean, -log|det J| mean)
         - `l0, l1 = trainer.step(x, y)`; unpack it before the next step (its prologue clears the sums)"""
+        x, y = self._inputs(x, y)
         for e in self.engines:
             e.ensure_arena()
         if not self._graphable():
@@ -632,6 +640,7 @@ class ConditionalFlowTrainer:
 
     def input_buffers(self, x: torch.Tensor, y: torch.Tensor):
         """the captured step's own input tensors holding a copy of the arguments (FlowTrainer.input_buffers)"""
+        x, y = self._inputs(x, y)
         if not self._graphable():
             return x, y
         for e in self.engines:

@@ -631,6 +631,27 @@ def _as_f32_2d(t: torch.Tensor, what: str) -> torch.Tensor:
     return t.contiguous()
 
 
+def _as_input(t, what: str, device: torch.device, width: int, rank: int = 2, rows: Optional[tuple] = None) -> torch.Tensor:
+    """The trainers' input contract (FlowTrainer, ConditionalFlowTrainer): a floating tensor of `rank` dimensions with `width`
+    lanes on `device` (leading dimensions `rows`, when given) -> its contiguous fp32 form, which is `t` itself when `t` already
+    is one (a batch that is a captured graph's own input buffer stays that buffer).  Any strides and any floating dtype give
+    what the contiguous fp32 copy gives; everything else raises before a kernel sees a pointer."""
+    if not isinstance(t, torch.Tensor):
+        raise HintAmdError(f"hint_amd: {what} must be a tensor, got {type(t).__name__}")
+    if t.device != device:
+        raise HintAmdError(f"hint_amd: {what} is on {t.device}, the model on {device} (no CPU path, no implicit transfer)")
+    if not t.dtype.is_floating_point:
+        raise HintAmdError(f"hint_amd: {what} has dtype {t.dtype}; a floating dtype is needed (converted to fp32)")
+    if t.dim() != rank or t.shape[-1] != width:
+        lead = ", ".join("KB"[-(rank - 1):]) if rank <= 3 else "..."
+        raise HintAmdError(f"hint_amd: {what} must be [{lead}, {width}], got {tuple(t.shape)}")
+    if rows is not None and tuple(t.shape[:-1]) != tuple(rows):
+        raise HintAmdError(f"hint_amd: {what} has leading shape {tuple(t.shape[:-1])}, the batch {tuple(rows)}")
+    if t.dtype is not torch.float32:
+        t = t.to(torch.float32)
+    return t if t.is_contiguous() else t.contiguous()
+
+
 class NodePermutation(nn.Module):
     """Stand-in for FrEIA's `HouseholderPerm(fixed=True)` of reshuffle=True trees (hint.py:36-39): a
     fixed random orthogonal [D,D] matrix applied to the node's lanes on entry (x W) and undone on

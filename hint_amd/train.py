@@ -19,7 +19,7 @@ import torch
 
 from . import _lib, dp
 from .flow import HintFlow
-from .hint import HintAmdError
+from .hint import HintAmdError, _as_input
 
 
 class _LossPair:
@@ -131,6 +131,21 @@ class FlowTrainer:
             self._chains = {}
         except Exception:
             pass
+
+    def _inputs(self, x, c, many: bool = False, what: str = "x"):
+        """the input contract of every entry point (hint._as_input): x [B, d] (many: [K, B, d]) and c [B, dc] ([K, B, dc]) as
+        contiguous fp32 tensors on the trainer's device - copies only where the arguments are not that already; c is required
+        exactly when the flow is conditional.  Raises HintAmdError before anything is launched."""
+        rank = 3 if many else 2
+        x = _as_input(x, what, self.device, self.flow.ndim_x, rank)
+        dc = self.flow.ndim_c
+        if dc > 0:
+            if c is None:
+                raise HintAmdError(f"hint_amd: the flow is conditional (ndim_c = {dc}): c is missing")
+            c = _as_input(c, "c", self.device, dc, rank, rows=x.shape[:-1])
+        elif c is not None:
+            raise HintAmdError("hint_amd: the flow is unconditional (ndim_c = 0) but c was given")
+        return x, c
 
     def _chain_for(self, B: int):
         """the chain handle for batch size B: tapes and backward workspaces of all blocks are
@@ -306,6 +321,7 @@ class FlowTrainer:
     def step(self, x: torch.Tensor, c: Optional[torch.Tensor] = None):
         """one training iteration on this rank's shard; returns device scalars (l0, l1) =
         ('-log p(z)', '-log |det J|') of the LOCAL shard (train_unconditional.py:162)"""
+        x, c = self._inputs(x, c)
         self.loss_acc = self._loss_single
         if not self.use_graph:
             self._check_arenas()
@@ -369,13 +385,15 @@ class FlowTrainer:
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
             for k in range(K):
-                self.loss_acc = self._loss_all[k]             # every iteration its own loss sums
+                self.loss_acc = self._loss_all[k]             # every iteration its own loss sums (every capture sets its own
+                                                              # accumulator: _capture takes the single step's back)
                 self._fwd_bwd(sx[k], sc[k] if sc is not None else None, with_adam=True)
         self._graph_many, self._static_many = g, dict(x=sx, c=sc)
 
     def step_many(self, xs: torch.Tensor, cs: Optional[torch.Tensor] = None):
         """K = xs.shape[0] training iterations on the batches xs[k] ([K, B, d]; cs [K, B, dc]); with
         use_graph and one process they are ONE graph replay.  Per-iteration losses: step_losses()."""
+        xs, cs = self._inputs(xs, cs, many=True, what="xs")
         K, B = xs.shape[0], xs.shape[1]
         if not self._many_ok():
             out = []
@@ -409,6 +427,7 @@ class FlowTrainer:
 
     def input_buffers_many(self, xs: torch.Tensor, cs: Optional[torch.Tensor] = None):
         """step_many()'s own input tensors ([K, B, d], [K, B, dc]) holding a copy of the arguments (see input_buffers)"""
+        xs, cs = self._inputs(xs, cs, many=True, what="xs")
         if not self._many_ok():
             return xs, cs
         st = getattr(self, "_static_many", None)
@@ -424,7 +443,9 @@ class FlowTrainer:
         """the captured step's own input tensors (x, c) for this batch shape, holding a copy of the
         arguments: a data pipeline that writes its batches straight into them (index_select(..., out=),
         copy_ from pinned memory) and passes them to step() saves the device-to-device copy step()
-        otherwise makes per iteration.  Without use_graph the arguments are returned as they are."""
+        otherwise makes per iteration.  Without use_graph the arguments are returned in the form step() reads them (contiguous
+        fp32)."""
+        x, c = self._inputs(x, c)
         if not self.use_graph:
             return x, c
         if self._graph is None or self._static["x"].shape != x.shape:
@@ -441,6 +462,7 @@ class FlowTrainer:
         of a hot back-to-back loop."""
         if not self._chainable:
             raise HintAmdError("timed_step needs the chained launches (identical blocks)")
+        x, c = self._inputs(x, c)
         self._check_arenas()
         B = x.shape[0]
         chain = self._chain_for(B)
@@ -500,6 +522,9 @@ class FlowTrainer:
         return f"hint_apply_kernel<false, {'true' if info[7] else 'false'}>", bwd
 
     def _capture(self, x, c):
+        # the captured launches write the single step's loss sums: input_buffers() may capture right behind a step_many(), which
+        # left loss_acc pointing at its last iteration's (step() would then read sums the graph never writes)
+        self.loss_acc = self._loss_single
         self._check_arenas()
         sx = x.clone()
         sc = c.clone() if c is not None else None
@@ -566,10 +591,10 @@ class FlowTrainer:
         """x = f^-1(z) and the log-determinant of that map per row (train_unconditional.py:152-153,
         rev=True through the whole graph; hint.py:83 sign) - every block of the flow in ONE launch
         (hint_chain_inverse), on the weights as they are now."""
+        z, c = self._inputs(z, c, what="z")
         if not self._chainable:
             x = self.flow(z, c=c, rev=True)
             return x, self.flow.log_jacobian(rev=True, run_forward=False)
-        z = z.contiguous().float()
         B = z.shape[0]
         x = torch.empty_like(z)
         J = torch.empty(B, dtype=torch.float32, device=z.device)
@@ -588,6 +613,7 @@ class FlowTrainer:
     def nll(self, x: torch.Tensor, c: Optional[torch.Tensor] = None) -> float:
         """mean negative log-likelihood in nats incl. the Gaussian constant
         (run_uci_experiments.py:71-72)"""
+        x, c = self._inputs(x, c)
         z = self.flow(x, c=c)
         J = self.flow.log_jacobian(run_forward=False)
         return float(0.5 * torch.sum(z * z, dim=1).mean() - J.mean()) + 0.5 * self.flow.ndim_x * math.log(2 * math.pi)

@@ -36,6 +36,72 @@ def oracle_module(mod, x, c, rev=False):
     return orc.block_apply(nodes, P, x, c, rev=rev, clamp=mod.tree.clamp)
 
 
+class OracleComposition:
+    """the two-lane graph of conditional_hint_4_full.py:55-95 assembled from oracle blocks (oracle_nodes + orc.block_apply per
+    module) on CPU copies of a ConditionalHintFlow's weights in `dtype`, with the statements of train_conditional.py:120-150
+    (loss pair, gradient clamp, torch.optim.Adam) as `train_step`"""
+
+    def __init__(self, m, dtype=torch.float32):
+        ny, self.nb = m.ndim_y, m.n_blocks
+        self.mods = []
+        for i in range(self.nb):
+            self.mods += [(f"hac_x.{i}", m.hac_x[i], 0), (f"ac_y_to_x.{i}", m.ac_y_to_x[i], ny), (f"ac_y.{i}", m.ac_y[i], 0)]
+        self.P = {name: {k: v.detach().cpu().to(dtype).clone().requires_grad_(True) for k, v in sub.state_dict().items()}
+                  for name, sub, _ in self.mods}
+        self.nodes = {name: oracle_nodes(sub.tree, dc) for name, sub, dc in self.mods}
+        self.clamp = {name: sub.tree.clamp for name, sub, _ in self.mods}
+        self.Wy = [m.perm_y[i].W.cpu().to(dtype) if i > 0 else None for i in range(self.nb)]
+        self.Wx = [m.perm_x[i].W.cpu().to(dtype) if i > 0 else None for i in range(self.nb)]
+        self.plist = [p for d_ in self.P.values() for p in d_.values()]
+        self.dtype = dtype
+        self.opt = None
+
+    def _blk(self, n, x, c, rev=False):
+        return orc.block_apply(self.nodes[n], self.P[n], x, c, rev=rev, clamp=self.clamp[n])
+
+    def forward(self, x, y):
+        """-> z_x, z_y, x_jac, the y lane's log-det, the condition every block's ac_y_to_x saw"""
+        xo, yo = x.to(self.dtype), y.to(self.dtype)
+        jx = jy = 0
+        conds = []
+        for i in range(self.nb):
+            if i > 0:
+                yo = yo @ self.Wy[i]; xo = xo @ self.Wx[i]
+            conds.append(yo)
+            xo, j = self._blk(f"hac_x.{i}", xo, []); jx = jx + j
+            xo, j = self._blk(f"ac_y_to_x.{i}", xo, [yo]); jx = jx + j
+            yo, j = self._blk(f"ac_y.{i}", yo, []); jy = jy + j
+        return xo, yo, jx, jy, conds
+
+    def make_optimizer(self, lr, betas=(0.9, 0.95), eps=1e-4, weight_decay=1.86e-5):
+        self.opt = torch.optim.Adam(self.plist, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+        return self.opt
+
+    def train_step(self, x, y):
+        """-> the loss pair as floats, x_jac"""
+        self.opt.zero_grad()
+        xo, yo, jx, jy, _ = self.forward(x, y)
+        z = torch.cat([xo, yo], dim=-1)
+        batch_losses = [0.5 * torch.sum(z ** 2, dim=1).mean(), -(jx + jy).mean()]      # train_conditional.py:132-143
+        sum(batch_losses).backward()
+        for p in self.plist:
+            p.grad.data.clamp_(-5.00, 5.00)
+        self.opt.step()
+        return [float(l) for l in batch_losses], jx.detach().clone()
+
+    @torch.no_grad()
+    def sample_conditional(self, y, zx):
+        """the x lane inverted under the conditions the y lane's forward gives -> x, its log-det"""
+        conds = self.forward(torch.zeros(y.shape[0], zx.shape[1]), y)[4]
+        x, J = zx.to(self.dtype), 0
+        for i in reversed(range(self.nb)):
+            x, j = self._blk(f"ac_y_to_x.{i}", x, [conds[i]], rev=True); J = J + j
+            x, j = self._blk(f"hac_x.{i}", x, [], rev=True); J = J + j
+            if i > 0:
+                x = x @ self.Wx[i].T
+        return x, J
+
+
 @pytest.mark.parametrize("D,dc,h,B", [(5, 2, 16, 77), (100, 4, 224, 300), (1, 3, 8, 16)])
 def test_external_affine_coupling_matches_oracle(D, dc, h, B):
     torch.manual_seed(1)
@@ -204,38 +270,17 @@ def test_conditional_trainer_full_size_matches_oracle_training(use_graph):
     xs = [torch.randn(B, nx, generator=gx) for _ in range(steps)]
     ys = [torch.randn(B, ny, generator=gx) for _ in range(steps)]
 
-    mods = []
-    for i in range(nb):
-        mods += [(f"hac_x.{i}", m.hac_x[i], 0), (f"ac_y_to_x.{i}", m.ac_y_to_x[i], ny), (f"ac_y.{i}", m.ac_y[i], 0)]
-    Po = {name: {k: v.detach().cpu().clone().requires_grad_(True) for k, v in sub.state_dict().items()} for name, sub, _ in mods}
-    nodes = {name: oracle_nodes(sub.tree, dc) for name, sub, dc in mods}
-    clamp = {name: sub.tree.clamp for name, sub, _ in mods}
-    Wy = [m.perm_y[i].W.cpu() if i > 0 else None for i in range(nb)]
-    Wx = [m.perm_x[i].W.cpu() if i > 0 else None for i in range(nb)]
-    plist = [p for d_ in Po.values() for p in d_.values()]
-    optim = torch.optim.Adam(plist, lr=lr, betas=(0.9, 0.95), eps=1e-4, weight_decay=1.86e-5)
+    oc = OracleComposition(m)
+    oc.make_optimizer(lr)
+    mods, Po = oc.mods, oc.P
     ref_losses, ref_xjac = [], []
     nt = torch.get_num_threads()
     torch.set_num_threads(min(16, nt))
     try:
         for x, y in zip(xs, ys):
-            optim.zero_grad()
-            xo, yo = x, y
-            jx = jy = 0
-            for i in range(nb):
-                if i > 0:
-                    yo = yo @ Wy[i]; xo = xo @ Wx[i]
-                n = f"hac_x.{i}"; xo, j = orc.block_apply(nodes[n], Po[n], xo, [], clamp=clamp[n]); jx = jx + j
-                n = f"ac_y_to_x.{i}"; xo, j = orc.block_apply(nodes[n], Po[n], xo, [yo], clamp=clamp[n]); jx = jx + j
-                n = f"ac_y.{i}"; yo, j = orc.block_apply(nodes[n], Po[n], yo, [], clamp=clamp[n]); jy = jy + j
-            z = torch.cat([xo, yo], dim=-1)
-            batch_losses = [0.5 * torch.sum(z ** 2, dim=1).mean(), -(jx + jy).mean()]      # train_conditional.py:132-143
-            sum(batch_losses).backward()
-            for p in plist:
-                p.grad.data.clamp_(-5.00, 5.00)
-            optim.step()
-            ref_losses.append([float(l) for l in batch_losses])
-            ref_xjac.append(jx.detach().clone())
+            pair, jx = oc.train_step(x, y)
+            ref_losses.append(pair)
+            ref_xjac.append(jx)
     finally:
         torch.set_num_threads(nt)
 

@@ -178,6 +178,10 @@ struct hint_plan {
     std::mutex inv_mu;
     std::vector<hint_plan*> inv_levels;         // deepest level last
     uint8_t* d_inv_lower = nullptr;             // [levels][d]
+    // host-only plans: one digest per emitted table (hint_plan_check_digest).  A NEW FIELD above that a kernel or a launch site
+    // reads goes into digest_scalars (hint_plan.cpp), so that tests/test_plan_digest_cpu.py sees it move.
+    std::vector<uint64_t> digests;
+    ~hint_plan();                               // frees alt4, the level plans and the device tables (hint_plan.cpp)
 };
 
 namespace hint {

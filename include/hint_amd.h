@@ -131,6 +131,13 @@ int hint_plan_dispatch(const hint_plan* plan, int32_t B, int32_t* out, int32_t n
 /* The same for a host-only plan (as hint_plan_check builds it: no device needed) on a device of num_cu CUs. */
 int hint_plan_check_dispatch(const hint_node_desc* nodes, int32_t n_nodes, int32_t d, int32_t dc, float clamp, int32_t B,
                              int32_t num_cu, int32_t* out, int32_t n_out);
+/* Host-only as well: one 64-bit digest per table the planner emits, first for the plan, then for its 4-wavefront variant (zeros
+ * when there is none).  Per plan HINT_PLAN_DIGESTS values: meta blob, slot table, thin records, row records, bias map, real-element
+ * map, weight-gradient jobs, first-layer-gradient map, pack segments, pack tiles, unit_w23, the plan's scalar fields.  Writes the
+ * first n_out of the 2 * HINT_PLAN_DIGESTS values.  tests/test_plan_digest_cpu.py pins them: a planner change shows which table moved. */
+#define HINT_PLAN_DIGESTS 12
+int hint_plan_check_digest(const hint_node_desc* nodes, int32_t n_nodes, int32_t d, int32_t dc, float clamp, uint64_t* out,
+                           int32_t n_out);
 
 /* Re-pack the flat parameters into `packed` (hint_plan_packed_floats floats).  Must be called
  * after every change of the parameters and before the next forward / inverse / backward that

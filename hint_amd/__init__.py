@@ -11,5 +11,6 @@ from .train import FlowTrainer  # noqa: F401,E402
 from .conditional import (AffineCoupling, ConditionalFlowTrainer, ConditionalHintFlow,  # noqa: F401,E402
                           ExternalAffineCoupling, F_fully_connected)
 from .optim import ClampAdam  # noqa: F401,E402
+from .metrics import MultiMMD, multi_mmd  # noqa: F401,E402
 
 __version__ = "0.1.0"

@@ -29,6 +29,13 @@ class NodeDesc(C.Structure):
                 ("h", C.c_int32), ("depth", C.c_int32), ("p_off", C.c_int64 * 12)]
 
 
+class MmdDesc(C.Structure):
+    """mirror of `hint_mmd_desc` (include/hint_amd.h)"""
+    _fields_ = [("x", C.c_void_p), ("y", C.c_void_p), ("n_x", C.c_int32), ("n_y", C.c_int32), ("d", C.c_int32),
+                ("n_kernels", C.c_int32), ("width", C.c_float * 8), ("exponent", C.c_float * 8), ("yy", C.c_void_p),
+                ("out", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
+
+
 _lib = None
 
 _PROTOS = {
@@ -96,6 +103,9 @@ _PROTOS = {
     "hint_adam_multi_step": (C.c_int, [C.c_void_p, C.c_int32] + [C.c_float] * 7 + [C.c_int32, C.c_void_p]),
     "hint_adam_multi_destroy": (None, [C.c_void_p]),
     "hint_adam_multi_chunk": (C.c_int64, [C.POINTER(AdamSeg), C.c_int32, C.c_int64, C.c_int32]),
+    "hint_mmd_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "hint_mmd_run": (C.c_int, [C.POINTER(MmdDesc), C.c_void_p]),
+    "hint_mmd_job": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32]),
 }
 
 

@@ -1,0 +1,125 @@
+"""multi_mmd / MultiMMD: the sample-quality metric of the reference's evaluation loop on the fused kernels of hint_mmd.hip.
+
+    multi_mmd(sample, gt_sample)                                       rejection_sampling.py:56-73, called at :135-213
+
+costs three N x N GEMMs and about thirty passes over N x N temporaries there; here it is hint_mmd_run: four small launches,
+no N x N matrix in memory, a bit-reproducible result.  MultiMMD keeps one ground-truth set and its YY term, for loops that score
+many samples against it (compare_conditional: eight models per run).  No gradient is implemented and there is no CPU fallback.
+"""
+from __future__ import annotations
+
+import math
+from typing import Sequence, Tuple
+
+import torch
+
+from . import _lib
+from ._lib import HintAmdError
+
+__all__ = ["multi_mmd", "MultiMMD", "DEFAULT_WIDTHS_EXPONENTS", "mmd_jobs"]
+
+DEFAULT_WIDTHS_EXPONENTS = ((0.5, 1), (0.2, 1), (0.2, 0.5))      # rejection_sampling.py:56
+MAX_KERNELS = 8
+
+
+def _check_kernels(widths_exponents) -> Tuple[Tuple[float, float], ...]:
+    try:
+        ks = tuple((float(C), float(a)) for C, a in widths_exponents)
+    except (TypeError, ValueError) as e:
+        raise HintAmdError(f"multi_mmd: widths_exponents must be a sequence of (width, exponent) pairs: {e}") from e
+    if not 1 <= len(ks) <= MAX_KERNELS:
+        raise HintAmdError(f"multi_mmd: widths_exponents must hold 1..{MAX_KERNELS} kernels (got {len(ks)})")
+    for k, (C, a) in enumerate(ks):
+        if not (C > 0 and math.isfinite(C)):
+            raise HintAmdError(f"multi_mmd: width of kernel {k} must be positive and finite (got {C})")
+        if not (a > 0 and math.isfinite(a)):
+            raise HintAmdError(f"multi_mmd: exponent of kernel {k} must be positive and finite (got {a})")
+    return ks
+
+
+def _check_set(t, name: str) -> torch.Tensor:
+    if not isinstance(t, torch.Tensor):
+        raise HintAmdError(f"multi_mmd: {name} must be a tensor (got {type(t).__name__})")
+    if t.dim() != 2:
+        raise HintAmdError(f"multi_mmd: {name} must be 2-D [samples, features] (got shape {tuple(t.shape)})")
+    if not t.is_cuda:
+        raise HintAmdError(f"multi_mmd: {name} is on {t.device}; the metric is a GPU kernel and there is no CPU fallback")
+    if t.shape[0] < 1 or t.shape[1] < 1:
+        raise HintAmdError(f"multi_mmd: {name} is empty (shape {tuple(t.shape)})")
+    if not t.is_floating_point():
+        raise HintAmdError(f"multi_mmd: {name} is {t.dtype}; expected a floating-point tensor")
+    if t.requires_grad and torch.is_grad_enabled():
+        raise HintAmdError(f"multi_mmd: {name} requires grad, and no gradient of the metric is implemented; "
+                           "call it under torch.no_grad() or detach the input")
+    t = t.detach()
+    if t.dtype != torch.float32 or not t.is_contiguous():         # (copies only where needed)
+        t = t.to(torch.float32).contiguous()
+    return t
+
+
+def _check_pair(x: torch.Tensor, y: torch.Tensor):
+    if x.device != y.device:
+        raise HintAmdError(f"multi_mmd: x is on {x.device} and y on {y.device}")
+    if x.shape[1] != y.shape[1]:
+        raise HintAmdError(f"multi_mmd: x has {x.shape[1]} features and y has {y.shape[1]}")
+
+
+def _run(x: torch.Tensor, y: torch.Tensor, ks, yy=None) -> torch.Tensor:
+    """out = [MMD, mean XX, mean YY, mean XY] of checked fp32 sets on one device (yy: a device float, mean YY known)"""
+    lib = _lib.load()
+    n_x, n_y, d = x.shape[0], y.shape[0], x.shape[1]
+    nbytes = lib.hint_mmd_workspace_bytes(n_x, n_y, d)
+    if nbytes == 0:
+        _lib.check(1, "hint_mmd_workspace_bytes")
+    with torch.cuda.device(x.device):
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+        out = torch.empty(4, dtype=torch.float32, device=x.device)
+        desc = _lib.MmdDesc()
+        desc.x, desc.y, desc.n_x, desc.n_y, desc.d, desc.n_kernels = x.data_ptr(), y.data_ptr(), n_x, n_y, d, len(ks)
+        for k, (C, a) in enumerate(ks):
+            desc.width[k], desc.exponent[k] = C, a
+        desc.yy = None if yy is None else yy.data_ptr()
+        desc.out, desc.workspace, desc.workspace_bytes = out.data_ptr(), ws.data_ptr(), nbytes
+        st = lib.hint_mmd_run(desc, torch.cuda.current_stream(x.device).cuda_stream)
+    _lib.check(st, "hint_mmd_run")
+    return out
+
+
+def mmd_jobs(n_x: int, n_y: int, with_yy: bool = False):
+    """the pair launch's work items, (kind, tile row, tile column, weight) each, and the tile edge T.  Host only."""
+    lib = _lib.load()
+    n = lib.hint_mmd_job(n_x, n_y, int(with_yy), -1, 0)
+    _lib.check(1 if n < 0 else 0, "hint_mmd_job")
+    T = lib.hint_mmd_job(n_x, n_y, int(with_yy), -1, 1)
+    return [tuple(lib.hint_mmd_job(n_x, n_y, int(with_yy), j, f) for f in range(4)) for j in range(n)], T
+
+
+def multi_mmd(x: torch.Tensor, y: torch.Tensor, widths_exponents: Sequence = DEFAULT_WIDTHS_EXPONENTS) -> torch.Tensor:
+    """the reference's multi_mmd(x, y) (biased V-statistic, all pairs) as a 0-dim fp32 tensor on the inputs' device; sets of
+    different sizes take each term's own mean"""
+    ks = _check_kernels(widths_exponents)
+    x, y = _check_set(x, "x"), _check_set(y, "y")
+    _check_pair(x, y)
+    return _run(x, y, ks)[0]
+
+
+class MultiMMD:
+    """multi_mmd against one ground-truth set y: mmd(x) returns multi_mmd(x, y) bit for bit, with the YY term computed once
+    (when the object is made).  `terms` holds [mean XX, mean YY, mean XY] of the last call."""
+
+    def __init__(self, y: torch.Tensor, widths_exponents: Sequence = DEFAULT_WIDTHS_EXPONENTS):
+        self.kernels = _check_kernels(widths_exponents)
+        self.y = _check_set(y, "y")
+        # mean YY depends on y and the kernels alone (the common centre is y's mean): one row of y stands in for x
+        first = _run(self.y[:1], self.y, self.kernels)
+        self.yy = first[2:3].clone()
+        self.terms = first[1:4]
+
+    def mmd(self, x: torch.Tensor) -> torch.Tensor:
+        x = _check_set(x, "x")
+        _check_pair(x, self.y)
+        out = _run(x, self.y, self.kernels, yy=self.yy)
+        self.terms = out[1:4]
+        return out[0]
+
+    __call__ = mmd

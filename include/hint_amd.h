@@ -393,6 +393,37 @@ int hint_adam_multi_step(const hint_adam_multi* h, int32_t step, float lr, float
 void hint_adam_multi_destroy(const hint_adam_multi* h);
 int64_t hint_adam_multi_chunk(const hint_adam_seg* segs, int32_t n_segs, int64_t c, int32_t field);
 
+/* Multi-kernel MMD, the sample-quality metric of the reference's evaluation loop (rejection_sampling.py:56-73 multi_mmd, called on
+ * 4000 x 4000 pairs per model and run by compare_unconditional / compare_conditional).  For x [n_x, d], y [n_y, d] and kernels
+ * (C_k, a_k), k < n_kernels:
+ *   k(D) = sum_k C_k^a_k ((C_k + D) / a_k)^(-a_k),  D = max(|u - v|^2, 0)
+ *   MMD  = mean_ij k(D(x_i, x_j)) + mean_ij k(D(y_i, y_j)) - 2 mean_ij k(D(x_i, y_j))
+ * over all pairs, the diagonal included (the biased V-statistic; multi_mmd's value for n_x == n_y, each term's own mean otherwise).
+ * out = {MMD, mean XX, mean YY, mean XY}; the MMD is formed from the three means as stored, so every float of out is written and
+ * a run that is handed mean YY (yy: out[2] of an earlier run on the same y and kernels; no YY tile is computed then) returns the
+ * same bits.  Both sets are centred on y's mean before the Gram products; D is exactly 0 for a row against itself.  The result
+ * does not depend on what the workspace or out held, and two runs on the same inputs agree bit for bit (no atomics).
+ *   run              stream-ordered on the current device: four launches, no host synchronisation, no allocation (capturable).
+ *                    Rejects, before any device call and naming the field: a null x, y, out or workspace; n_x, n_y or d < 1;
+ *                    d > 4096; n_x or n_y > 1048576; n_kernels outside 1..8; a width or exponent that is not positive and finite;
+ *                    a pointer that is not 4-byte (workspace: 16-byte) aligned; a workspace smaller than workspace_bytes says.
+ *   workspace_bytes  0 (and an error message) for sizes run would reject.
+ *   job              host only: the work items of the pair launch, one T x T tile of a pair matrix each.  j == -1: field 0 is
+ *                    their number, field 1 is T.  0 <= j < number: field 0 kind (0 XX, 1 YY, 2 XY), 1 tile row, 2 tile column,
+ *                    3 weight (XX and YY run on tile columns >= tile rows only; off-diagonal tiles weigh 2).  -1 on an error.
+ * None of these has a caller's device buffer among its parameters: the buffers are named by the descriptor. */
+typedef struct hint_mmd_desc {
+    const float* x; const float* y;        /* [n_x, d], [n_y, d] row-major, 4-byte aligned */
+    int32_t n_x, n_y, d, n_kernels;        /* n_kernels 1..8 */
+    float width[8], exponent[8];           /* C_k > 0, a_k > 0 */
+    const float* yy;                       /* NULL, or device float: mean YY of an earlier run on the same y and kernels */
+    float* out;                            /* device float[4] */
+    void* workspace; size_t workspace_bytes;
+} hint_mmd_desc;
+size_t hint_mmd_workspace_bytes(int32_t n_x, int32_t n_y, int32_t d);
+int hint_mmd_run(const hint_mmd_desc* desc, void* stream);
+int64_t hint_mmd_job(int32_t n_x, int32_t n_y, int32_t with_yy, int64_t j, int32_t field);
+
 int hint_abi_version(void);
 const char* hint_last_error(void);
 /* what the library binary was built with and runs with: "libhint_amd abi N, gfx950, HIP x.y.z, clang ..., src <12 hex digits: hash

@@ -420,7 +420,9 @@ class _Engine:
         return (out, J, tape) if with_tape else (out, J)
 
     # ---- chained forms (flow container / trainer): permutation, J accumulation, loss fused ----
-    def forward_chain(self, x, c, perm, J_in, loss_acc, with_tape: bool):
+    def forward_chain(self, x, c, perm, J_in, loss_acc, with_tape: bool, noise: float = 0.0, rng_state=None, x_noisy=None):
+        """noise > 0: the block perturbs its input inside the kernel (hint_block_forward_noisy: Philox keyed by rng_state =
+        {seed, step}) and writes what it saw to x_noisy - the tensor the backward pass starts from"""
         B = x.shape[0]
         out = torch.empty_like(x)
         J = torch.empty(B, dtype=torch.float32, device=x.device)
@@ -430,10 +432,16 @@ class _Engine:
         if B > 0:
             ptr = lambda t: t.data_ptr() if t is not None else None
             with torch.cuda.device(self.device):
-                st = self.lib.hint_block_forward_ex(self.plan, self.arena.data_ptr(), self.packed.data_ptr(),
-                                                    x.data_ptr(), ptr(c), out.data_ptr(), J.data_ptr(), ptr(tape),
-                                                    ptr(perm), ptr(J_in), ptr(loss_acc), B, self._stream())
-            _lib.check(st, "hint_block_forward_ex")
+                if noise > 0:
+                    st = self.lib.hint_block_forward_noisy(self.plan, self.arena.data_ptr(), self.packed.data_ptr(),
+                                                           x.data_ptr(), ptr(c), out.data_ptr(), J.data_ptr(), ptr(tape),
+                                                           ptr(perm), ptr(J_in), ptr(loss_acc), float(noise),
+                                                           rng_state.data_ptr(), x_noisy.data_ptr(), B, self._stream())
+                else:
+                    st = self.lib.hint_block_forward_ex(self.plan, self.arena.data_ptr(), self.packed.data_ptr(),
+                                                        x.data_ptr(), ptr(c), out.data_ptr(), J.data_ptr(), ptr(tape),
+                                                        ptr(perm), ptr(J_in), ptr(loss_acc), B, self._stream())
+            _lib.check(st, "hint_block_forward_noisy" if noise > 0 else "hint_block_forward_ex")
         return out, J, tape
 
     def backward_chain(self, x, tape, c, gz, gz_scale, gJ_const, perm, g_params, accumulate=True):

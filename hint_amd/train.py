@@ -216,6 +216,7 @@ class FlowTrainer:
             cp = c.data_ptr() if c is not None else None
             noisy = self.noise > 0
             xn = torch.empty_like(x) if noisy else x          # the perturbed input, for the backward pass
+            self._xn = xn if noisy else None                  # (kept: a captured step's stays readable in _static["xn"])
             with torch.cuda.device(self.device):
                 stream = torch.cuda.current_stream(self.device).cuda_stream
                 _lib.check(self.lib.hint_chain_forward_noisy(
@@ -266,15 +267,28 @@ class FlowTrainer:
                 else:
                     self._adam_dev()
             return B
-        if self.noise > 0:
+        # block-by-block launches: the first block draws the noise inside its kernel, from the stream the chained launch
+        # draws from (Philox keyed by rng_state: seed, step counter) - one stream whatever route runs the step
+        self._xn = None
+        in_kernel = self.noise > 0 and B > 0
+        if in_kernel and self.engines[0].compose_perm(flow.perms[0].W if flow.has_perm(0) else None) is not None:
+            # (a matrix in front of the first block - perm_first / reshuffle=True: the kernel perturbs what it reads behind the
+            #  matrix, not x; no launch of its own exists for that, so this one shape keeps torch's generator)
             x = x.add(torch.randn_like(x), alpha=self.noise)
+            in_kernel = False
         inputs, tapes = [], []
         h, J = x, None
         n = len(self.engines)
         for i, eng in enumerate(self.engines):
             perm = eng.compose_perm(flow.perms[i].W if flow.has_perm(i) else None)
-            inputs.append(h if perm is None else None)
-            h, J, tape = eng.forward_chain(h, c, perm, J, self.loss_acc if i == n - 1 else None, with_tape=True)
+            if i == 0 and in_kernel:
+                self._xn = torch.empty_like(h)
+                inputs.append(self._xn)
+                h, J, tape = eng.forward_chain(h, c, perm, J, self.loss_acc if i == n - 1 else None, with_tape=True,
+                                               noise=float(self.noise), rng_state=self.rng_state, x_noisy=self._xn)
+            else:
+                inputs.append(h if perm is None else None)
+                h, J, tape = eng.forward_chain(h, c, perm, J, self.loss_acc if i == n - 1 else None, with_tape=True)
             tapes.append(tape)
         z = h
         g = z                                  # dL/dz = z / B : the scale is applied inside the kernel
@@ -577,7 +591,7 @@ class FlowTrainer:
             with torch.cuda.graph(g):
                 self._fwd_bwd(sx, sc, with_adam=False)
         self._graph = g
-        self._static = dict(x=sx, c=sc)
+        self._static = dict(x=sx, c=sc, xn=getattr(self, "_xn", None))     # xn: what the captured forward perturbs x into
 
     def last_losses(self):
         """(-log p(z), -log|det J|) of the most recent step's local shard as device scalars

@@ -34,6 +34,28 @@ tolerance; the smallest such multiple over the four flows:
     ragged_skipped    losses 9.6e+03   losses 1.3e+04   losses 2.0e+04
     stale_weights     losses 2.0e+04   losses 2.7e+04   losses 2.1e+04
     prev_loss         losses 1.8e+04   losses 2.6e+05   losses 4.7e+04
+
+NOISY SESSIONS (NOISY_SESSIONS: `epochs` on every flow, `mixed` on wl_d6 and gen_d43): the t-th training step trains on
+x + noise * normals(NOISE_SEED, t, B * d) of tests/noise_oracle.py, calibrated the same way (float32 oracle on the same draws
+against the float64 oracle, x 4, floor 4 ulp, the same caps).  Floors measured on the CPU at noise = 0.01:
+    floor     script   wl_d6     gen_d43   cond_d9   unchained_d8
+    losses    epochs   1.2e-07   9.4e-08   1.3e-07   4.3e-07
+              mixed    1.1e-07   1.8e-07
+    nll       epochs   1.9e-08   4.4e-08   9.6e-08   4.6e-08
+              mixed    3.3e-09   4.8e-10
+    update    epochs   3.7e-05   6.8e-05   8.5e-04   4.6e-05
+              mixed    1.2e-05   2.3e-05
+  (0 to 9 candidate rows per session give their position to a spare next to a ReLU kink.)
+Injected noise faults, each against the fault-free float64 run AT THE TRAINERS' DEFAULT noise = 0.01 - every one is seen there in
+every flow, so no session needed the higher levels 0.1 / 0.25 (noise_level() would find them): the quantity moved most, as a
+multiple of its tolerance
+    fault                   script   wl_d6            gen_d43          cond_d9          unchained_d8
+    noise_step_behind       epochs   losses 1.8e+04   losses 1.6e+03   losses 4.5e+03   losses 7.7e+02
+                            mixed    losses 5.7e+03   update 1.2e+03
+    noise_not_in_backward   epochs   losses 1.7e+04   update 1.2e+03   update 2.8e+02   update 1.2e+03
+                            mixed    losses 5.0e+03   update 2.8e+03
+    noise_tile_repeat       epochs   losses 4.2e+04   update 2.3e+03   losses 6.8e+03   update 1.6e+03
+                            mixed    losses 1.5e+04   update 2.7e+03
 """
 from __future__ import annotations
 
@@ -43,6 +65,7 @@ import math
 import numpy as np
 import torch
 
+import noise_oracle as no
 from oracle import hint_oracle as orc
 
 # ---- flows ------------------------------------------------------------------------------------------------------------------
@@ -83,6 +106,17 @@ SCRIPTS = {
 }
 
 FAULTS = ("bias_ahead", "lr_dropped", "ragged_skipped", "stale_weights", "prev_loss")
+# ---- sessions with the training noise on --------------------------------------------------------------------------------------
+# The t-th training step of a session (t = 1, 2, ...: the trainers' step prologue advances the device counter BEFORE the forward)
+# trains on x + noise * normals(NOISE_SEED, t, B * d) (tests/noise_oracle.py), the draw of flat element f on element f of the batch.
+NOISE_FAULTS = ("noise_step_behind", "noise_not_in_backward", "noise_tile_repeat")
+NOISE_SEED = 1234
+NOISE_LEVELS = (0.01, 0.1, 0.25)                                      # the trainers' default first; see noise_level()
+# the noisy sessions and the level each runs at: what noise_level() finds (tests/test_session_script_cpu.py asserts the table, so
+# that the GPU tests need not run the fault calibration) - every fault shows at the trainers' default in every one of them
+NOISY_SESSIONS = {("epochs", "wl_d6"): 0.01, ("epochs", "gen_d43"): 0.01, ("epochs", "cond_d9"): 0.01,
+                  ("epochs", "unchained_d8"): 0.01, ("mixed", "wl_d6"): 0.01, ("mixed", "gen_d43"): 0.01}
+TILE_ROWS = 16                                                        # the row kernels' tile (noise_tile_repeat)
 
 LR, BETAS, EPS, WD = 0.01 * 3e-2, (0.9, 0.95), 1e-4, 1.86e-5          # FlowTrainer's defaults (train_unconditional.py:174-176)
 CAPS = dict(losses=1e-4, nll=1e-4, update=5e-2)                       # test_trainer_reproduces_reference_adam_steps
@@ -174,8 +208,10 @@ def run_session(script: str, spec, backend, rows=None):
 class OracleBackend:
     """the session on an OracleFlow in `dtype`; `fault` injects one of FAULTS (the calibration's sensitivity check)"""
 
-    def __init__(self, spec, dtype=torch.float64, fault=None):
-        assert fault is None or fault in FAULTS
+    def __init__(self, spec, dtype=torch.float64, fault=None, noise=0.0, seed=NOISE_SEED):
+        assert fault is None or fault in FAULTS or (fault in NOISE_FAULTS and noise > 0)
+        self.noise, self.seed, self.t = float(noise), int(seed), 0     # t: training steps taken (the trainers' step counter)
+        self.behind = False                                            # noise_step_behind has set in
         dims_c = [(spec["dc"],)] if spec["dc"] > 0 else ()
         self.flow = orc.OracleFlow(spec["d"], spec["n_blocks"], list(spec["widths"]), dims_c=dims_c, dtype=dtype)
         params, perms = initial_weights(spec)
@@ -192,10 +228,24 @@ class OracleBackend:
     def _cast(self, x, c):
         return x.to(self.dtype), ([c.to(self.dtype)] if c is not None else ())
 
+    def draws(self, t, B, d, tile_repeat=False):
+        """[B, d] in the backend's dtype: the noise oracle's draws of step t, flat element f of the batch -> draw f"""
+        np_dt = np.float64 if self.dtype == torch.float64 else np.float32
+        N = torch.from_numpy(no.normals(self.seed, t, B * d, np_dt).reshape(B, d).copy())
+        if tile_repeat:                                     # every 16-row tile the draws of tile 0
+            N = N[torch.arange(B) % TILE_ROWS]
+        return N
+
+    def perturbed(self, xd, t, tile_repeat=False):
+        """x + noise * N(seed, t), multiplied and added in the backend's dtype (as the kernels do in fp32)"""
+        if self.noise == 0.0:
+            return xd
+        return xd + torch.tensor(self.noise, dtype=self.dtype) * self.draws(t, xd.shape[0], xd.shape[1], tile_repeat)
+
     @torch.no_grad()
-    def pick_rows(self, x, c, B):
-        """the first B candidate rows none of whose hidden pre-activations (whole chain, current weights) lies within KINK of
-        zero (rows_off_the_kinks of test_gpu_chain_workloads.py)"""
+    def kink_distance(self, x, c):
+        """per row: the smallest hidden pre-activation's distance from zero, of its layer's largest in that row (whole chain,
+        current weights)"""
         dist = torch.full((x.shape[0],), float("inf"), dtype=torch.float64)
         relu = torch.relu
 
@@ -207,13 +257,40 @@ class OracleBackend:
             return relu(t)
         torch.relu = spy
         try:
-            self.flow.forward(*self._cast(x, c))
+            xd, cd = self._cast(x, c)
+            self.flow.forward(xd, cd)
         finally:
             torch.relu = relu
+        return dist
+
+    @torch.no_grad()
+    def pick_rows(self, x, c, B):
+        """the first B candidate rows none of whose hidden pre-activations (whole chain, current weights) lies within KINK of
+        zero (rows_off_the_kinks of test_gpu_chain_workloads.py).
+        With noise the kinks are judged on the rows AS THE STEP SEES THEM, and a draw belongs to a position in the batch, not to a
+        candidate: the first B good candidates are perturbed by position with the draws of the step to come; a row that now lies
+        within KINK gives its position to the next unused candidate; again until the batch is clean."""
+        dist = self.kink_distance(x, c)
         idx = torch.nonzero(dist > KINK).flatten()[:B]
         assert idx.numel() == B, (idx.numel(), B)
-        self.dropped = getattr(self, "dropped", 0) + int(idx[-1]) + 1 - B
         self.picked = getattr(self, "picked", 0) + B
+        if self.noise == 0.0:
+            self.dropped = getattr(self, "dropped", 0) + int(idx[-1]) + 1 - B
+            return idx
+        idx = idx.clone()
+        used = set(idx.tolist())
+        spare = [j for j in range(x.shape[0]) if j not in used]        # (candidates next to a kink as drawn may do when perturbed)
+        dropped = 0
+        while True:
+            xn = self.perturbed(x[idx].to(self.dtype), self.t + 1)
+            bad = torch.nonzero(self.kink_distance(xn, _take(c, idx)) <= KINK).flatten().tolist()
+            if not bad:
+                break
+            for pos in bad:
+                assert spare, "no spare candidate row left"
+                idx[pos] = spare.pop(0)
+                dropped += 1
+        self.dropped = getattr(self, "dropped", 0) + dropped
         return idx
 
     def _fire(self, fault, when) -> bool:
@@ -230,6 +307,11 @@ class OracleBackend:
         self.last_B = B
         flow, opt = self.flow, self.flow.opt
         xd, cd = self._cast(x, c)
+        self.t += 1
+        x_clean = xd
+        if self.noise > 0:
+            self.behind = self.behind or (self.fault == "noise_step_behind" and changed)    # from the first shape change on
+            xd = self.perturbed(xd, self.t - 1 if self.behind else self.t, tile_repeat=self.fault == "noise_tile_repeat")
         if self._fire("bias_ahead", changed):               # the device step counter one ahead from the first shape change on
             for st in opt.state.values():
                 st["step"] += 1
@@ -255,6 +337,15 @@ class OracleBackend:
                 p.grad.data.clamp_(-5.0, 5.0)
             opt.step()
             pair = [float(l0), float(l1)]
+        elif self.fault == "noise_not_in_backward":          # the loss at x_noisy, the gradient at x
+            with torch.no_grad():
+                pair = [float(v) for v in flow.loss_terms(*flow.forward(xd, cd))]
+            opt.zero_grad()
+            l0, l1 = flow.loss_terms(*flow.forward(x_clean, cd))
+            (l0 + l1).backward()
+            for p in flow.parameters():
+                p.grad.data.clamp_(-5.0, 5.0)
+            opt.step()
         else:
             pair = list(flow.train_step(xd, cd))
         self.prev_weights = before
@@ -307,14 +398,15 @@ class OracleBackend:
                  for k, v in P.items()} for P in self.flow.params]
 
 
-def run_oracle(script: str, flow_name: str, dtype=torch.float64, fault=None):
+def run_oracle(script: str, flow_name: str, dtype=torch.float64, fault=None, noise=0.0):
+    """noise > 0: the session with the training noise on, at that level, keyed by NOISE_SEED"""
     spec = FLOWS[flow_name]
     author = dtype == torch.float64 and fault is None          # the reference run chooses the training rows for all others
-    rows = None if author else reference(script, flow_name)["rows"]
+    rows = None if author else reference(script, flow_name, noise)["rows"]
     nt = torch.get_num_threads()
     torch.set_num_threads(min(16, nt))
     try:
-        be = OracleBackend(spec, dtype, fault)
+        be = OracleBackend(spec, dtype, fault, noise)
         rec = run_session(script, spec, be, rows)
     finally:
         torch.set_num_threads(nt)
@@ -325,10 +417,14 @@ def run_oracle(script: str, flow_name: str, dtype=torch.float64, fault=None):
     return rec
 
 
-@functools.lru_cache(maxsize=None)
-def reference(script: str, flow_name: str):
+def reference(script: str, flow_name: str, noise=0.0):
     """the float64 oracle's record of a session (cached: the graph and the eager trainer are compared with the same one)"""
-    return run_oracle(script, flow_name, torch.float64)
+    return _reference(script, flow_name, float(noise))
+
+
+@functools.lru_cache(maxsize=None)
+def _reference(script, flow_name, noise):
+    return run_oracle(script, flow_name, torch.float64, noise=noise)
 
 
 # ---- deviations and tolerances ------------------------------------------------------------------------------------------------
@@ -357,14 +453,45 @@ def deviations(rec, ref):
                 update=max(update_devs(ref["initial"], rec["final"], ref["final"]).values()))
 
 
+def floors(script: str, flow_name: str, noise=0.0):
+    """(noise > 0: the float32 oracle on the same draws - the float32 evaluation of the same Philox outputs, added in float32)"""
+    return _floors(script, flow_name, float(noise))
+
+
 @functools.lru_cache(maxsize=None)
-def floors(script: str, flow_name: str):
-    return deviations(run_oracle(script, flow_name, torch.float32), reference(script, flow_name))
+def _floors(script, flow_name, noise):
+    return deviations(run_oracle(script, flow_name, torch.float32, noise=noise), reference(script, flow_name, noise))
 
 
-def tolerances(script: str, flow_name: str):
+def tolerances(script: str, flow_name: str, noise=0.0):
     """4 x the float32 oracle's own deviation from the float64 oracle; at least 4 ulp of fp32, at most the existing test's"""
-    return {k: min(CAPS[k], 4.0 * max(v, ULP)) for k, v in floors(script, flow_name).items()}
+    return {k: min(CAPS[k], 4.0 * max(v, ULP)) for k, v in floors(script, flow_name, noise).items()}
+
+
+DETECT = 5.0             # an injected fault must move a compared quantity by this many tolerances
+
+
+@functools.lru_cache(maxsize=None)
+def fault_ratios(script: str, flow_name: str, noise: float):
+    """{noise fault: (the quantity it moves most, by how many tolerances)} of a noisy session at one level"""
+    ref, tol = reference(script, flow_name, noise), tolerances(script, flow_name, noise)
+    out = {}
+    for fault in NOISE_FAULTS:
+        dev = deviations(run_oracle(script, flow_name, fault=fault, noise=noise), ref)
+        ratio = {k: dev[k] / tol[k] for k in tol}
+        worst = max(ratio, key=ratio.get)
+        out[fault] = (worst, ratio[worst])
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def noise_level(script: str, flow_name: str):
+    """the level a noisy session runs at: the first of NOISE_LEVELS (the trainers' default 0.01 first) at which every injected
+    noise fault moves a compared quantity by DETECT tolerances; None if none does (the CPU calibration test fails then)"""
+    for level in NOISE_LEVELS:
+        if all(r >= DETECT for _, r in fault_ratios(script, flow_name, level).values()):
+            return level
+    return None
 
 
 def adam_factors(lr: float, t: int):

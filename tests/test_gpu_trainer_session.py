@@ -118,9 +118,9 @@ def fwd_close(got, ref, what):
     return [] if d <= lim else [(what, d, lim)]
 
 
-def compare_session(tr, rec, script, flow_name):
+def compare_session(tr, rec, script, flow_name, noise=0.0):
     """every compared quantity of a finished session against the float64 oracle's; prints each figure, returns the misses"""
-    ref, tol = ss.reference(script, flow_name), ss.tolerances(script, flow_name)
+    ref, tol = ss.reference(script, flow_name, noise), ss.tolerances(script, flow_name, noise)
     bad = []
     assert ref["dropped"] <= ss.MAX_DROPPED * ref["picked"], (ref["dropped"], ref["picked"])     # the kink rule stays a rare exception
     step_dev = np.max(np.abs(rec["losses"] - ref["losses"]) / (0.1 + np.abs(ref["losses"])), axis=1)
@@ -169,6 +169,25 @@ def test_session_matches_float64_oracle_training(script, flow_name, use_graph):
     rec = ss.run_session(script, ss.FLOWS[flow_name], TrainerBackend(tr), ss.reference(script, flow_name)["rows"])
     assert tr.step_count == len(rec["losses"])
     bad = compare_session(tr, rec, script, flow_name)
+    assert not bad, bad
+
+
+NOISY = [(s, f, g) for (s, f) in ss.NOISY_SESSIONS for g in ((True, False) if s == "epochs" else (True,))]
+
+
+@pytest.mark.parametrize("script,flow_name,use_graph", NOISY, ids=[f"{s}-{f}-{'graph' if g else 'eager'}" for s, f, g in NOISY])
+def test_noisy_session_matches_float64_oracle_training(script, flow_name, use_graph):
+    """the sessions with the training noise ON (the trainers' default; every other oracle comparison turns it off): the oracle
+    trains step t on x + noise * normals(seed, t) of tests/noise_oracle.py, the trainer draws in its forward kernel - the same
+    comparisons as the noise-free sessions (loss pairs, NLLs, samples, forwards, update vectors, moments, the device counter and
+    Adam's factors after every event), at tolerances calibrated the same way.  `epochs` on every flow, captured and eager -
+    block-by-block launches included, where the first block's launch draws; `mixed` (step_many) on the captured trainer"""
+    noise = ss.NOISY_SESSIONS[(script, flow_name)]
+    tr = build_trainer(flow_name, use_graph, noise=noise, seed=ss.NOISE_SEED)
+    assert tr._chainable == ss.FLOWS[flow_name]["use_chain"] and int(tr.rng_state[0]) == ss.NOISE_SEED
+    rec = ss.run_session(script, ss.FLOWS[flow_name], TrainerBackend(tr), ss.reference(script, flow_name, noise)["rows"])
+    assert tr.step_count == len(rec["losses"])
+    bad = compare_session(tr, rec, script, flow_name, noise)
     assert not bad, bad
 
 

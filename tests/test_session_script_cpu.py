@@ -34,6 +34,64 @@ def test_float32_floor_and_injected_faults(script, flow_name):
         assert ratio[worst] >= 5.0, (fault, ratio)
 
 
+@pytest.mark.parametrize("script,flow_name", list(ss.NOISY_SESSIONS), ids=["-".join(k) for k in ss.NOISY_SESSIONS])
+def test_noisy_float32_floor_and_injected_noise_faults(script, flow_name):
+    """the sessions with the training noise on (x + noise * the noise oracle's draws of the step): calibrated as the noise-free
+    ones, and each injected noise fault - draws one step behind from the first shape change on, the gradient taken at x instead
+    of x_noisy, every 16-row tile with tile 0's draws - moves a compared quantity by 5 tolerances at the session's level"""
+    noise = ss.NOISY_SESSIONS[(script, flow_name)]
+    assert noise in ss.NOISE_LEVELS
+    assert ss.noise_level(script, flow_name) == noise      # the first level at which every fault is seen (0.01: the default)
+    ref = ss.reference(script, flow_name, noise)
+    floors = ss.floors(script, flow_name, noise)
+    tol = ss.tolerances(script, flow_name, noise)
+    print(f"\n{script}/{flow_name} noise={noise}: floors " + " ".join(f"{k}={v:.1e}" for k, v in floors.items())
+          + " | tolerances " + " ".join(f"{k}={v:.1e}" for k, v in tol.items()))
+    print(f"    training rows replaced next to a ReLU kink: {ref['dropped']} of {ref['picked']}")
+    assert 0 <= ref["dropped"] <= ss.MAX_DROPPED * ref["picked"], (ref["dropped"], ref["picked"])
+    assert len(ref["losses"]) >= 6 and np.all(np.isfinite(ref["losses"]))
+    assert np.abs(ref["losses"]).max() < 1e3
+    # the noise is on: the session is not the noise-free one
+    assert ss.scalar_dev(ref["losses"], ss.reference(script, flow_name)["losses"]) > 100 * tol["losses"]
+    for k in tol:
+        assert floors[k] <= tol[k] / 4.0 + 1e-30 or tol[k] == ss.CAPS[k], (k, floors[k], tol[k])
+        assert floors[k] < ss.CAPS[k] / 4.0, (k, floors[k])
+        assert 4.0 * ss.ULP <= tol[k] <= ss.CAPS[k], (k, tol[k])
+    ratios = ss.fault_ratios(script, flow_name, noise)
+    assert set(ratios) == set(ss.NOISE_FAULTS)
+    for fault, (worst, ratio) in ratios.items():
+        print(f"    {fault:22s} moves {worst} by {ratio:.1e} x its tolerance")
+        assert ratio >= ss.DETECT == 5.0, (fault, worst, ratio)
+
+
+def test_noisy_rows_are_judged_as_the_step_sees_them():
+    """pick_rows with noise on: the chosen rows, perturbed by POSITION with the draws of the step to come, keep KINK away from every
+    ReLU kink; a position is re-filled from the unused candidates; without noise the rule is the old one"""
+    spec = ss.FLOWS["wl_d6"]
+    be = ss.OracleBackend(spec, noise=0.25)
+    x, c = ss.draw("epochs", 0, spec, (ss.FULL,), ss.SPARE)
+    kink, ss.KINK = ss.KINK, 2e-6                # (a wider band, so that some rows do fall into it: as drawn, and when perturbed)
+    try:
+        idx = be.pick_rows(x, c, ss.FULL)
+        assert len(set(idx.tolist())) == ss.FULL
+        xn = be.perturbed(x[idx].double(), 1)
+        assert torch.equal(xn, x[idx].double() + 0.25 * be.draws(1, ss.FULL, spec["d"]))
+        assert float(be.kink_distance(xn, None).min()) > ss.KINK
+        assert be.dropped > 0 and be.picked == ss.FULL
+        plain = ss.OracleBackend(spec)
+        first = torch.nonzero(plain.kink_distance(x, c) > ss.KINK).flatten()[:ss.FULL]
+        assert torch.equal(plain.pick_rows(x, c, ss.FULL), first)
+    finally:
+        ss.KINK = kink
+    # the draws of a step: position-keyed, the oracle's stream, float32 for the float32 backend
+    import noise_oracle as no
+    N = be.draws(3, 40, spec["d"])
+    assert N.dtype == torch.float64 and np.array_equal(N.numpy().reshape(-1), no.normals(ss.NOISE_SEED, 3, 40 * spec["d"]))
+    T = be.draws(3, 40, spec["d"], tile_repeat=True)
+    assert torch.equal(T[:16], N[:16]) and torch.equal(T[16:32], N[:16]) and torch.equal(T[32:], N[:8])
+    assert ss.OracleBackend(spec, torch.float32, noise=0.25).draws(3, 40, spec["d"]).dtype == torch.float32
+
+
 def test_scripts_hold_what_the_sessions_are_about():
     ep = ss.SCRIPTS["epochs"]
     steps = [e for e in ep if e[0] == "step"]

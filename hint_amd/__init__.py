@@ -12,5 +12,6 @@ from .conditional import (AffineCoupling, ConditionalFlowTrainer, ConditionalHin
                           ExternalAffineCoupling, F_fully_connected)
 from .optim import ClampAdam  # noqa: F401,E402
 from .metrics import MultiMMD, multi_mmd  # noqa: F401,E402
+from .abc import nearest_rows, quantile_abc  # noqa: F401,E402
 
 __version__ = "0.1.0"

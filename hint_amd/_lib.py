@@ -36,6 +36,12 @@ class MmdDesc(C.Structure):
                 ("out", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
 
 
+class AbcDesc(C.Structure):
+    """mirror of `hint_abc_desc` (include/hint_amd.h)"""
+    _fields_ = [("y", C.c_void_p), ("target", C.c_void_p), ("n_rows", C.c_int64), ("ny", C.c_int32), ("k", C.c_int32),
+                ("idx", C.c_void_p), ("dist", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
+
+
 _lib = None
 
 _PROTOS = {
@@ -106,6 +112,9 @@ _PROTOS = {
     "hint_mmd_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "hint_mmd_run": (C.c_int, [C.POINTER(MmdDesc), C.c_void_p]),
     "hint_mmd_job": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32]),
+    "hint_abc_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32]),
+    "hint_abc_run": (C.c_int, [C.POINTER(AbcDesc), C.c_void_p]),
+    "hint_abc_geometry": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
 }
 
 

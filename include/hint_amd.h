@@ -424,6 +424,35 @@ size_t hint_mmd_workspace_bytes(int32_t n_x, int32_t n_y, int32_t d);
 int hint_mmd_run(const hint_mmd_desc* desc, void* stream);
 int64_t hint_mmd_job(int32_t n_x, int32_t n_y, int32_t with_yy, int64_t j, int32_t field);
 
+/* ABC selection, the ground-truth posterior sample of the reference's evaluation loop (rejection_sampling.py:88-96 quantile_ABC,
+ * called at :188 by compare_conditional on 1e8 prior observations per run).  For y [n_rows, ny], a target t [ny] and k:
+ *   D_i = sum_j (y_ij - t_j)^2 in fp32, j = 0, 1, .., ny - 1 in that order: the first term a rounded product, every later one a fused
+ *         multiply-add onto the sum; a D_i that is not a finite number (inf, NaN) counts as +inf
+ *   rows are totally ordered by (D_i, i); idx / dist = the first k rows of that order and sqrt(D) of each, ascending
+ * The selection is exact (a radix select over the bit pattern of D, y re-read on every pass: field 2 of geometry passes, nothing of
+ * size n_rows is stored), does not depend on what idx, dist or the workspace held, and two runs agree bit for bit (integer counts
+ * only, no float atomics, no global counters).
+ *   run              stream-ordered on the current device: no host synchronisation, no allocation (capturable).  Rejects, before
+ *                    any device call and naming the field: a null y, target, idx, dist or workspace; n_rows outside 1..2^30; ny
+ *                    outside 1..32; k outside 1..min(n_rows, 8192); a pointer that is not 4-byte (workspace: 16-byte) aligned; a
+ *                    workspace smaller than workspace_bytes says.
+ *   workspace_bytes  0 (and an error message) for sizes run would reject.  At most 8.5 MiB, whatever n_rows is.
+ *   geometry         host only: field 0 the workgroups of the streaming passes, 1 the rows each owns (workgroup w: rows
+ *                    [w rows, min(n_rows, (w + 1) rows))), 2 the passes over y.  -1 on an error.
+ * None of these has a caller's device buffer among its parameters: the buffers are named by the descriptor. */
+typedef struct hint_abc_desc {
+    const float* y;                        /* [n_rows, ny] row-major, 4-byte aligned */
+    const float* target;                   /* device float[ny] */
+    int64_t n_rows;
+    int32_t ny, k;
+    int32_t* idx;                          /* device int32[k] */
+    float* dist;                           /* device float[k] */
+    void* workspace; size_t workspace_bytes;
+} hint_abc_desc;
+size_t hint_abc_workspace_bytes(int64_t n_rows, int32_t ny, int32_t k);
+int hint_abc_run(const hint_abc_desc* desc, void* stream);
+int64_t hint_abc_geometry(int64_t n_rows, int32_t ny, int32_t field);
+
 int hint_abi_version(void);
 const char* hint_last_error(void);
 /* what the library binary was built with and runs with: "libhint_amd abi N, gfx950, HIP x.y.z, clang ..., src <12 hex digits: hash

@@ -135,8 +135,8 @@ CASES = [
 KNOBS_EXCLUDED = {
     "HINT_WL=0": "routes wave-local trees to the general kernels: instances the default cases run",
     "HINT_SUB=0 / HINT_LEAN=0 / HINT_LEANW=0": "remove subtree / lean / lean-wide groups: plans of instances the default cases run",
-    "HINT_NW / HINT_DW_SPLITS / HINT_LEANW_MAX / HINT_PF": "experiment sizes (wavefronts, part-B splits, thin-layer width, L2 warm-up), "
-                                                        "no instance of their own",
+    "HINT_NW / HINT_LEANW_MAX / HINT_PF": "experiment sizes (wavefronts, thin-layer width, L2 warm-up), no instance of their own "
+                                          "(HINT_DW_SPLITS: the `forced` targets of wgrad_geometry.py)",
 }
 
 
@@ -184,7 +184,7 @@ def mismatch(case: Case, disp: Dict[str, int]) -> Optional[str]:
 
 def knob_env(monkeypatch, lib, knobs):
     """set a case's knobs (or none) and make the library re-read its environment"""
-    for k in ("HINT_WL_NR", "HINT_NO_BWD_FLY", "HINT_FUSE_DW1", "HINT_DW_SMALL"):
+    for k in ("HINT_WL_NR", "HINT_NO_BWD_FLY", "HINT_FUSE_DW1", "HINT_DW_SMALL", "HINT_DW_SPLITS"):
         monkeypatch.delenv(k, raising=False)
     for k, v in knobs.items():
         monkeypatch.setenv(k, v)

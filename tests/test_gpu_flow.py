@@ -303,7 +303,10 @@ def test_module_copies_and_pickles_after_first_use(tmp_path):
         assert torch.equal(flow(x), z) and not torch.equal(twin(x), z)
 
 
-@pytest.mark.parametrize("d,widths,nb,B", [(6, [140, 70, 35, 17], 3, 1000), (43, [67, 33, 16, 8], 2, 300), (9, [19, 11, 3], 4, 4113)])
+# (the d = 100 tree: the thin branch of hint_wreduce_kernel with ad.p != nullptr on both sides of its unrolled loop - 57 slabs take
+#  the 8-wide pass for q = 0 alone, 65 slabs (one valid row in the last block) for every q, with a scalar tail behind it for q = 0)
+@pytest.mark.parametrize("d,widths,nb,B", [(6, [140, 70, 35, 17], 3, 1000), (43, [67, 33, 16, 8], 2, 300), (9, [19, 11, 3], 4, 4113),
+                                           (100, [32, 16, 8], 2, 16 * 57), (100, [32, 16, 8], 2, 16 * 65 - 15)])
 def test_optimizer_folded_into_the_reduction_takes_the_same_steps(d, widths, nb, B, monkeypatch):
     """hint_chain_backward_adam (the captured step of a one-process trainer) against the separate reduction + optimizer
     launches: the same weights and Adam moments bit for bit after five steps, the gradient arena left at zero"""

@@ -19,11 +19,15 @@ own Linear-ReLU-Linear-ReLU-Linear s and t nets with `internal_size` hidden unit
 """
 from __future__ import annotations
 
+import ctypes as C
+import os
 from typing import List, Optional, Sequence
 
 import torch
 import torch.nn as nn
 
+from . import _lib, dp
+from ._core import PackGroup, TrainerCore, _LossPair
 from .flow import FixedOrthogonal
 from .hint import HierarchicalAffineCouplingBlock, HierarchicalAffineCouplingTree, HintAmdError, _as_input
 
@@ -182,7 +186,7 @@ class ConditionalHintFlow(nn.Module):
 
     def _posterior(self) -> "_PosteriorSampler":
         dev = next(self.parameters()).device
-        ps = getattr(self, "_post", None)
+        ps = self._post
         if ps is None or ps.device != dev:
             if dev.type != "cuda":
                 raise HintAmdError("hint_amd: no CPU implementation; move the model and data to the GPU")
@@ -198,8 +202,7 @@ class _PosteriorSampler:
     perm_x_i fused in front, ac_y_to_x_i as the block's affine step behind it - and the coefficient buffer it reads."""
 
     def __init__(self, flow: "ConditionalHintFlow", device: torch.device):
-        from . import _lib
-        self._lib, self.lib = _lib, _lib.load()
+        self.lib = _lib.load()
         self.flow, self.device = flow, device
         nb = flow.n_blocks
         self.hx = [flow.hac_x[i].tree.engine(device) for i in range(nb)]
@@ -208,7 +211,7 @@ class _PosteriorSampler:
         self.engines = self.hx + self.ex + self.ey
         # the fused route needs one plan for every hac_x block and ExternalAffineCouplings without node permutations of their own
         self.fusable = all(e.shape_key == self.hx[0].shape_key for e in self.hx) and all(e.total_perm() is None for e in self.ex)
-        self._pack_group, self._pack_key = None, None
+        self._pack_group = PackGroup(self.engines, device)
         self._chains = {}            # (B, per_row) -> (handle, key, coef, perms)
 
     def __del__(self):
@@ -216,45 +219,26 @@ class _PosteriorSampler:
             for h, _, _, _ in self._chains.values():
                 self.lib.hint_chain_destroy(h)
             self._chains = {}
-            if self._pack_group:
-                self.lib.hint_pack_group_destroy(self._pack_group)
+            self._pack_group.close()
         except Exception:
             pass
 
     def _pack_all(self):
         """one launch re-packs the twelve modules from their arenas (the weights may have changed since the last call: a
         trainer step, load_state_dict, an optimizer on the parameters)"""
-        import ctypes as C
         for e in self.engines:
             e.ensure_arena()
             if e.packed is None or e.packed.device != self.device:
                 e.pack()
-        key = tuple((e.arena.data_ptr(), e.packed.data_ptr()) for e in self.engines)
-        if self._pack_key != key:
-            if self._pack_group:
-                self.lib.hint_pack_group_destroy(self._pack_group)
-                self._pack_group = None
-            n = len(self.engines)
-            plans = (C.c_void_p * n)(*[e.plan.value for e in self.engines])
-            params = (C.c_void_p * n)(*[e.arena.data_ptr() for e in self.engines])
-            packed = (C.c_void_p * n)(*[e.packed.data_ptr() for e in self.engines])
-            handle = C.c_void_p()
-            with torch.cuda.device(self.device):
-                self._lib.check(self.lib.hint_pack_group_create(plans, params, packed, n, C.byref(handle)), "hint_pack_group_create")
-            self._pack_group, self._pack_key = handle, key
-        with torch.cuda.device(self.device):
-            self._lib.check(self.lib.hint_pack_group_run(self._pack_group, torch.cuda.current_stream(self.device).cuda_stream),
-                            "hint_pack_group_run")
+        self._pack_group.run()
 
     def _wave_local(self, B: int) -> bool:
-        import ctypes as C
         out = (C.c_int32 * 20)()
-        self._lib.check(self.lib.hint_plan_dispatch(self.hx[0].plan, B, out, 20), "hint_plan_dispatch")
+        _lib.check(self.lib.hint_plan_dispatch(self.hx[0].plan, B, out, 20), "hint_plan_dispatch")
         return out[0] != 0
 
     def _chain(self, B: int, per_row: bool):
         """the inference chain of batch size B and its coefficient buffer [n_blocks, R, 2, nx] (R = B per row, else 1)"""
-        import ctypes as C
         flow, nb, dx = self.flow, self.flow.n_blocks, self.flow.ndim_x
         for i in range(1, nb):                          # (the kernels read W through its raw pointer, row-major)
             if not flow.perm_x[i].W.is_contiguous():
@@ -275,7 +259,7 @@ class _PosteriorSampler:
         R = B if per_row else 1
         coef = torch.empty(nb, R, 2, dx, dtype=torch.float32, device=self.device)
         handle = C.c_void_p()
-        chk = self._lib.check
+        chk = _lib.check
         with torch.cuda.device(self.device):
             chk(self.lib.hint_chain_create(self.hx[0].plan, nb, B, C.byref(handle)), "hint_chain_create")
             try:
@@ -350,7 +334,7 @@ class _PosteriorSampler:
         if not self.fusable or self._wave_local(B):
             return self._module_route(conds, x, rev)
         chain, coef = self._chain(B, per_row)
-        chk = self._lib.check
+        chk = _lib.check
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream(self.device).cuda_stream
             for i, e in enumerate(self.ex):
@@ -365,20 +349,7 @@ class _PosteriorSampler:
         return out, J
 
 
-class _LossPair:
-    """what step() returns on every path: unpacks to the two loss terms as DEVICE SCALARS (torch tensors: `l0 + l1`,
-    `sum(batch_losses)`, `torch.stack`, `.item()` all work), evaluated when it is unpacked so that no torch kernel runs inside the
-    step or its captured graph.  The sums live in a buffer the next step's prologue clears: unpack before stepping again
-    (FlowTrainer.step returns the same type)."""
-
-    def __init__(self, trainer):
-        self._t = trainer
-
-    def __iter__(self):
-        return iter(self._t.last_losses())
-
-
-class ConditionalFlowTrainer:
+class ConditionalFlowTrainer(TrainerCore):
     """Fast training step for a ConditionalHintFlow (what FlowTrainer is for a HintFlow): one
     iteration of /root/reference/train_conditional.py:120-150 -
 
@@ -407,72 +378,31 @@ class ConditionalFlowTrainer:
       * the weight gradients of the modules of one plan - hac_x x 4, ac_y_to_x x 4, ac_y x 4 - are ONE part B and ONE slab
         reduction per plan, with the clamp + Adam step in the reduction (hint_chain_wgrad_adam: 3 + 3 launches for 12 + 12 +
         the optimizer's): the modules are gathered in chains whose blocks carry their own input and condition pointers;
-      * every intermediate lives in a buffer allocated once per batch size, so the chains' tables are built once."""
+      * every intermediate lives in a buffer allocated once per batch size, so the chains' tables are built once.
+
+    seed: of the in-kernel noise, as FlowTrainer's: rank `rank` draws the stream of (seed + 0x9E3779B97F4A7C15 * rank) & (2 ** 63 - 1)
+    (_core.rank_seed)."""
 
     def __init__(self, flow: ConditionalHintFlow, lr: float = 0.01 * 3e-2, betas=(0.9, 0.95), eps: float = 1e-4,
                  weight_decay: float = 1.86e-5, grad_clamp: float = 5.0, noise: float = 0.01, group=None,
                  use_graph: bool = True, seed: Optional[int] = None):
-        from . import _lib, dp
-        self._lib, self._dp = _lib, dp
-        self.lib = _lib.load()
-        self.flow, self.group = flow, group
-        self._lr, self.betas, self.eps, self.wd = lr, betas, eps, weight_decay
-        self.grad_clamp, self.noise = grad_clamp, noise
-        self.step_count = 0
-        self.use_graph = use_graph
-        self._graph, self._static, self._out = None, None, None
         dev = next(flow.parameters()).device
         if dev.type != "cuda":
             raise HintAmdError("ConditionalFlowTrainer needs the model on a GPU (no CPU path)")
-        self.device = dev
         self.mods = []                                    # (kind, block index, module) in forward order
         for i in range(flow.n_blocks):
             self.mods += [("hac_x", i, flow.hac_x[i]), ("ac_y_to_x", i, flow.ac_y_to_x[i]), ("ac_y", i, flow.ac_y[i])]
-        self.engines = [m.tree.engine(dev) for _, _, m in self.mods]
-        self.slices, cursor = [], 0
-        for e in self.engines:
-            self.slices.append((cursor, cursor + e.total))
-            cursor += e.total
-        self.n_floats = cursor
-        self.P, self.G, self.M, self.V = (torch.zeros(cursor, dtype=torch.float32, device=dev) for _ in range(4))
-        for e, (a, b) in zip(self.engines, self.slices):
-            e.bind_external_arena(self.P[a:b])
-            e.ensure_arena()
-            e.pack()
-        if dp.world_info(group)[1] > 1:
-            # data-parallel replicas start from rank 0's weights AND buffers (the fixed permutations are drawn per process:
-            # replicas with different matrices would sum gradients of different functions) - as FlowTrainer does
-            src = torch.distributed.get_global_rank(group, 0) if group is not None else 0
-            torch.distributed.broadcast(self.P, src=src, group=group)
-            for buf in flow.buffers():
-                if buf.is_cuda and buf.numel() > 0:
-                    torch.distributed.broadcast(buf, src=src, group=group)
-            for e in self.engines:
-                e._perm_key = None          # (composed permutations are rebuilt from the received matrices)
-                e.pack()
-        self._pack_group, self._pack_key = None, None
-        self.last = None
-        # device-side step state (see FlowTrainer): opt_state = {lr, beta1, beta2, lr/(1-beta1^t),
-        # 1/sqrt(1-beta2^t), ...}, rng_state[1] = step count; the re-pack launch's prologue advances them
-        self.opt_state = torch.tensor([lr, betas[0], betas[1], 0.0, 0.0, 0.0, 0.0, 0.0], dtype=torch.float32, device=dev)
-        if seed is None:            # (not from torch's global generator: building a trainer must not shift the caller's random stream)
-            import os
-            seed = int.from_bytes(os.urandom(8), "little") >> 2
-        rank = dp.world_info(group)[0]
-        self.rng_state = torch.tensor([(seed + 0x9E3779B97F4A7C15 * rank) & (2 ** 63 - 1), 0], dtype=torch.int64, device=dev)
+        # model-wide arenas, every module's engine bound to its slice; step state (TrainerCore)
+        super().__init__(flow, [m.tree.engine(dev) for _, _, m in self.mods], dev, lr, betas, eps, weight_decay, grad_clamp,
+                         noise, use_graph, group, seed)
+        self._eng = dict(zip([(k, i) for k, i, _ in self.mods], self.engines))      # (kind, block index) -> engine
+        self._sl = dict(zip([(k, i) for k, i, _ in self.mods], self.slices))        # ... -> its slice of the arenas
+        self._pack_group = PackGroup(self.engines, dev)
+        self._graph, self._static, self._out = None, None, None
+        self._graph_failed = False   # a collective could not be captured: plain launches from then on
+        self.last = None             # (z_y, z_x, J_x, J_y) of the most recent step
         self._st = {}                # per batch size: static buffers and chains (_state_for)
-        import os
         self._legacy = os.environ.get("HINT_COND_LEGACY", "0") not in ("", "0")
-        self.loss_acc = torch.zeros(64, 2, dtype=torch.float32, device=dev)     # hint_block_forward_ex: the two loss sums
-
-    @property
-    def lr(self) -> float:
-        return self._lr
-
-    @lr.setter
-    def lr(self, v: float):
-        self._lr = float(v)
-        self.opt_state[0] = self._lr            # read by the optimizer launch on the device: no re-capture
 
     def __del__(self):
         try:
@@ -481,20 +411,21 @@ class ConditionalFlowTrainer:
                 for h in st["chains"].values():
                     self.lib.hint_chain_destroy(h)
             self._st = {}
-            if getattr(self, "_pack_group", None):
-                self.lib.hint_pack_group_destroy(self._pack_group)
+            self._pack_group.close()
         except Exception:
             pass
 
     # ---- static buffers and chains of a batch size ----------------------------------------------------
     KINDS = ("hac_x", "ac_y_to_x", "ac_y")
 
+    def _state_key(self):
+        """what a batch size's chains (and a graph captured on them) hold raw pointers to"""
+        return tuple((e.arena.data_ptr(), e.packed.data_ptr()) for e in self.engines) + (self.G.data_ptr(),)
+
     def _state_for(self, B: int):
-        import ctypes as C
         flow, dev, nb = self.flow, self.device, self.flow.n_blocks
-        eng = dict(zip([(k, i) for k, i, _ in self.mods], self.engines))
-        sl = dict(zip([(k, i) for k, i, _ in self.mods], self.slices))
-        key = tuple((e.arena.data_ptr(), e.packed.data_ptr()) for e in self.engines) + (self.G.data_ptr(),)
+        eng, sl = self._eng, self._sl
+        key = self._state_key()
         st = self._st.get(B)
         if st is not None and st["key"] == key:
             return st
@@ -538,12 +469,12 @@ class ConditionalFlowTrainer:
                 st["ws"][kind] = torch.empty(nb, max(wb, 256), dtype=torch.uint8, device=dev)
                 st["wsb"][kind] = wb
                 h = C.c_void_p()
-                self._lib.check(self.lib.hint_chain_create(e0.plan, nb, B, C.byref(h)), "hint_chain_create")
+                _lib.check(self.lib.hint_chain_create(e0.plan, nb, B, C.byref(h)), "hint_chain_create")
                 st["chains"][kind] = h
                 for i in range(nb):
                     e = eng[(kind, i)]
                     a, _ = sl[(kind, i)]
-                    self._lib.check(self.lib.hint_chain_set_block(
+                    _lib.check(self.lib.hint_chain_set_block(
                         h, i, e.arena.data_ptr(), e.packed.data_ptr(), ptr(st["perm"][(kind, i)]), st["tapes"][kind][i].data_ptr(),
                         st["ws"][kind][i].data_ptr(), wb, self.G.data_ptr() + 4 * a), "hint_chain_set_block")
             # the y lane after its permutation = the x lane's condition: block i's tape TOP slice - the kernels keep a block's permuted
@@ -553,58 +484,41 @@ class ConditionalFlowTrainer:
             st["yp"] = [st["y_in"]] + [st["tapes"]["ac_y"][i][top:top + B * dy].view(B, dy) for i in range(1, nb)]
             st["hx0_in"] = st["xn"]
             for i in range(nb):
-                self._lib.check(self.lib.hint_chain_set_block_io(st["chains"]["ac_y"], i, None, None, st["gc"][i].data_ptr()),
-                                "hint_chain_set_block_io")
+                _lib.check(self.lib.hint_chain_set_block_io(st["chains"]["ac_y"], i, None, None, st["gc"][i].data_ptr()),
+                           "hint_chain_set_block_io")
                 hx_in = None if st["perm"][("hac_x", i)] is not None else (st["xn"] if i == 0 else st["xb"][i - 1])     # (block 0: _iteration keeps it in step with `noise`)
-                self._lib.check(self.lib.hint_chain_set_block_io(st["chains"]["hac_x"], i, ptr(hx_in), None, None),
-                                "hint_chain_set_block_io")
-                self._lib.check(self.lib.hint_chain_set_block_io(st["chains"]["ac_y_to_x"], i, st["xa"][i].data_ptr(),
-                                                                 st["yp"][i].data_ptr(), None), "hint_chain_set_block_io")
+                _lib.check(self.lib.hint_chain_set_block_io(st["chains"]["hac_x"], i, ptr(hx_in), None, None),
+                           "hint_chain_set_block_io")
+                _lib.check(self.lib.hint_chain_set_block_io(st["chains"]["ac_y_to_x"], i, st["xa"][i].data_ptr(),
+                                                            st["yp"][i].data_ptr(), None), "hint_chain_set_block_io")
             for kind in self.KINDS:
-                self._lib.check(self.lib.hint_chain_commit(st["chains"][kind]), "hint_chain_commit")
+                _lib.check(self.lib.hint_chain_commit(st["chains"][kind]), "hint_chain_commit")
         self._st[B] = st
         return st
 
     def _pack_all(self, prologue: bool = False):
-        import ctypes as C
-        key = tuple((e.arena.data_ptr(), e.packed.data_ptr()) for e in self.engines)
-        if self._pack_key != key:
-            if self._pack_group:
-                self.lib.hint_pack_group_destroy(self._pack_group)
-            n = len(self.engines)
-            plans = (C.c_void_p * n)(*[e.plan.value for e in self.engines])
-            params = (C.c_void_p * n)(*[e.arena.data_ptr() for e in self.engines])
-            packed = (C.c_void_p * n)(*[e.packed.data_ptr() for e in self.engines])
-            handle = C.c_void_p()
-            with torch.cuda.device(self.device):
-                self._lib.check(self.lib.hint_pack_group_create(plans, params, packed, n, C.byref(handle)),
-                                "hint_pack_group_create")
-            self._pack_group, self._pack_key = handle, key
-        with torch.cuda.device(self.device):
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-            if prologue:      # also: step counter += 1, Adam's bias corrections of that step -> opt_state
-                st = self.lib.hint_pack_group_run_ex(self._pack_group, self.loss_acc.data_ptr(), self.loss_acc.numel(),
-                                                     self.rng_state.data_ptr(), self.opt_state.data_ptr(), stream)
-            else:
-                st = self.lib.hint_pack_group_run(self._pack_group, stream)
-        self._lib.check(st, "hint_pack_group_run")
+        """one launch re-packs the twelve modules.  prologue: the launch also clears the loss sums, advances the step / noise
+        counter and writes Adam's factors of that step to opt_state"""
+        if prologue:
+            self._pack_group.run(self.loss_acc, self.rng_state, self.opt_state)
+        else:
+            self._pack_group.run()
 
     def allreduce_plan(self) -> str:
         """what the step does with the gradient arena between backward and optimizer (for bench.py's config line)"""
-        if not (torch.distributed.is_available() and torch.distributed.is_initialized()):
+        if not self._dist_on():
             return "none (one process)"
-        world = self._dp.world_info(self.group)[1]
+        world = dp.world_info(self.group)[1]
         where = "captured in the step's hipGraph" if self._graph is not None else "issued from the host"
         return (f"one all-reduce (sum) of the flat fp32 gradient arena ({self.n_floats} floats) over {world} ranks "
                 f"({torch.distributed.get_backend(self.group)}); {where}")
 
     def _graphable(self) -> bool:
         """one process, or a data-parallel job over RCCL (whose all-reduce is captured with the step)"""
-        if not self.use_graph or getattr(self, "_graph_failed", False):
+        if not self.use_graph or self._graph_failed:
             return False
-        if not (torch.distributed.is_available() and torch.distributed.is_initialized()):
+        if not self._dist_on():
             return True
-        import os
         return torch.distributed.get_backend(self.group) == "nccl" and os.environ.get("HINT_GRAPH_ALLREDUCE", "1") != "0"
 
     def _inputs(self, x, y):
@@ -625,7 +539,7 @@ class ConditionalFlowTrainer:
         if self._graph is not None and not self._legacy:
             # an arena or packed buffer that moved after the capture (ensure_arena above re-gathers): the graph holds the old addresses
             st = self._st.get(self._static[0].shape[0])
-            if st is None or st["key"] != tuple((e.arena.data_ptr(), e.packed.data_ptr()) for e in self.engines) + (self.G.data_ptr(),):
+            if st is None or st["key"] != self._state_key():
                 self._graph = None
         if self._graph is None or self._static[0].shape != x.shape or self._static[1].shape != y.shape:
             if not self._capture(x, y):
@@ -658,21 +572,24 @@ class ConditionalFlowTrainer:
             st = self._state_for(x.shape[0])
             sx, sy = st["x_in"], st["y_in"]
             sx.copy_(x); sy.copy_(y)
-        snap = [t.clone() for t in (self.P, self.M, self.V)]
-        state = (self.opt_state.clone(), self.rng_state.clone())
+        state = (self.P, self.M, self.V, self.opt_state, self.rng_state)
+        snap = [t.clone() for t in state]
+
+        def take_back():                       # the warm-up's (or a failed capture's) optimizer step
+            for t, s0 in zip(state, snap):
+                t.copy_(s0)
+            self.G.zero_()
+
         side = torch.cuda.Stream(device=self.device)
         side.wait_stream(torch.cuda.current_stream(self.device))
         with torch.cuda.stream(side):          # warm-up on a side stream (allocator, kernel loading) ...
             self._iteration(sx, sy, on_device_adam=True)
         torch.cuda.current_stream(self.device).wait_stream(side)
-        for t, s0 in zip((self.P, self.M, self.V), snap):      # ... whose optimizer step is taken back
-            t.copy_(s0)
-        self.opt_state.copy_(state[0]); self.rng_state.copy_(state[1])
-        self.G.zero_()
+        take_back()                            # ... whose optimizer step is taken back
         self.rng_state[1] = self.step_count
         torch.cuda.synchronize(self.device)
         g = torch.cuda.CUDAGraph()
-        dist_on = torch.distributed.is_available() and torch.distributed.is_initialized()
+        dist_on = self._dist_on()
         try:
             with torch.cuda.graph(g, capture_error_mode="thread_local" if dist_on else "global"):
                 self._out = self._iteration(sx, sy, on_device_adam=True)
@@ -681,10 +598,7 @@ class ConditionalFlowTrainer:
                 raise
             self._graph_failed = True           # the collective could not be captured: plain launches from now on
             torch.cuda.synchronize(self.device)
-            for t, s0 in zip((self.P, self.M, self.V), snap):
-                t.copy_(s0)
-            self.opt_state.copy_(state[0]); self.rng_state.copy_(state[1])
-            self.G.zero_()
+            take_back()
             return False
         self._graph, self._static = g, (sx, sy)
         return True
@@ -696,7 +610,7 @@ class ConditionalFlowTrainer:
         optimizer keep part B, the all-reduce and the optimizer launch apart."""
         if self._legacy:
             return self._iteration_legacy(x, y, on_device_adam)
-        flow, B, lib, chk = self.flow, x.shape[0], self.lib, self._lib.check
+        flow, B, lib, chk = self.flow, x.shape[0], self.lib, _lib.check
         if B == 0:
             raise HintAmdError("ConditionalFlowTrainer: empty batch")
         st = self._state_for(B)
@@ -708,7 +622,7 @@ class ConditionalFlowTrainer:
         if not on_device_adam:
             self.loss_acc.zero_()
             self.rng_state[1] += 1
-        eng = dict(zip([(k, i) for k, i, _ in self.mods], self.engines))
+        eng = self._eng
         nb = flow.n_blocks
         ptr = lambda t: t.data_ptr() if t is not None else None
         noisy = self.noise > 0
@@ -726,10 +640,9 @@ class ConditionalFlowTrainer:
             st["hx0_in"] = x0
         tape = lambda kind, i: st["tapes"][kind][i].data_ptr()
         ws = lambda kind, i: st["ws"][kind][i].data_ptr()
-        dist_on = torch.distributed.is_available() and torch.distributed.is_initialized()
-        fuse = on_device_adam and not dist_on
+        fuse = on_device_adam and not self._dist_on()
         with torch.cuda.device(self.device):
-            stream = torch.cuda.current_stream(self.device).cuda_stream
+            stream = self._stream()
             # ---- forward: the y lane (one launch), then the x lane's modules ----
             chk(lib.hint_chain_forward(st["chains"]["ac_y"], st["y_in"].data_ptr(), None, st["zy"].data_ptr(), st["Jy"].data_ptr(), None,
                                        self.loss_acc.data_ptr(), stream), "hint_chain_forward")
@@ -773,30 +686,19 @@ class ConditionalFlowTrainer:
                 else:
                     chk(lib.hint_chain_wgrad_range(st["chains"][kind], xk, None, 0, 0, nb, stream), "hint_chain_wgrad_range")
         if not fuse:
-            scale = self._dp.allreduce_sum_(self.G, self.group)       # (no-op without a process group)
-            with torch.cuda.device(self.device):
-                stream = torch.cuda.current_stream(self.device).cuda_stream
-                if on_device_adam:
-                    stt = lib.hint_adam_step_dev(self.P.data_ptr(), self.G.data_ptr(), self.M.data_ptr(), self.V.data_ptr(), self.n_floats,
-                                                 self.opt_state.data_ptr(), self.betas[0], self.betas[1], self.eps, self.wd, scale,
-                                                 self.grad_clamp, 1, stream)
-                else:
-                    self.step_count += 1
-                    stt = lib.hint_adam_step(self.P.data_ptr(), self.G.data_ptr(), self.M.data_ptr(), self.V.data_ptr(), self.n_floats,
-                                             self.step_count, self.lr, self.betas[0], self.betas[1], self.eps, self.wd, scale,
-                                             self.grad_clamp, 1, stream)
-            chk(stt, "hint_adam_step")
-            if not on_device_adam:
-                self.rng_state[1] = self.step_count          # keep the device counter in step for a later capture
+            self._optimizer(on_device_adam)
         self.last = (st["zy"], st["xb"][nb - 1], st["Jxb"][nb - 1], st["Jy"])
         self._last_B = B
         return _LossPair(self)
 
-    def last_losses(self):
-        """(0.5 |z|^2 mean, -log|det J| mean) of the most recent step as device scalars, from the launches' loss sums (read
-        them before the next step: its re-pack launch clears the sums)"""
-        s = self.loss_acc.sum(dim=0)
-        return s[0] / self._last_B, -s[1] / self._last_B
+    def _optimizer(self, on_device_adam: bool):
+        """gradient all-reduce (no-op without a process group), then the clamp + Adam launch"""
+        scale = dp.allreduce_sum_(self.G, self.group)
+        if on_device_adam:                      # step factors come from opt_state (the re-pack launch's prologue): capturable
+            self._adam_dev(scale)
+        else:
+            self._adam_host(scale)
+            self.rng_state[1] = self.step_count          # keep the device counter in step for a later capture
 
     def _iteration_legacy(self, x: torch.Tensor, y: torch.Tensor, on_device_adam: bool):
         """Round 4's iteration (HINT_COND_LEGACY=1; kept for A/B runs): both lanes forward and backward as direct launches.  What FrEIA's graph does between the couplings is folded
@@ -810,8 +712,7 @@ class ConditionalFlowTrainer:
             self.loss_acc.zero_()
         if self.noise > 0:
             x = x.add(torch.randn_like(x), alpha=self.noise)
-        eng = dict(zip([(k, i) for k, i, _ in self.mods], self.engines))
-        sl = dict(zip([(k, i) for k, i, _ in self.mods], self.slices))
+        eng, sl = self._eng, self._sl
         saved = {}
         nb = flow.n_blocks
         Jx = Jy = None
@@ -849,24 +750,7 @@ class ConditionalFlowTrainer:
             gx, _ = bwd("hac_x", gx)                                # (comes back through the x lane's permutation)
             if i > 0:
                 gy = gy @ flow.perm_y[i].W.t()
-        if on_device_adam:                      # step factors come from opt_state (prologue above): capturable
-            scale = self._dp.allreduce_sum_(self.G, self.group)       # (no-op without a process group)
-            with torch.cuda.device(self.device):
-                st = self.lib.hint_adam_step_dev(self.P.data_ptr(), self.G.data_ptr(), self.M.data_ptr(), self.V.data_ptr(),
-                                                 self.n_floats, self.opt_state.data_ptr(), self.betas[0], self.betas[1],
-                                                 self.eps, self.wd, scale, self.grad_clamp, 1,
-                                                 torch.cuda.current_stream(self.device).cuda_stream)
-            self._lib.check(st, "hint_adam_step_dev")
-        else:
-            scale = self._dp.allreduce_sum_(self.G, self.group)
-            self.step_count += 1
-            with torch.cuda.device(self.device):
-                st = self.lib.hint_adam_step(self.P.data_ptr(), self.G.data_ptr(), self.M.data_ptr(), self.V.data_ptr(),
-                                             self.n_floats, self.step_count, self.lr, self.betas[0], self.betas[1], self.eps,
-                                             self.wd, scale, self.grad_clamp, 1,
-                                             torch.cuda.current_stream(self.device).cuda_stream)
-            self._lib.check(st, "hint_adam_step")
-            self.rng_state[1] = self.step_count          # keep the device counter in step for a later capture
+        self._optimizer(on_device_adam)
         self.last = (zy, zx, Jx, Jy)
         self._last_B = B
         return _LossPair(self)

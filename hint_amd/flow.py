@@ -21,6 +21,7 @@ import torch.nn as nn
 
 from . import _lib
 from . import hint as _hint
+from ._core import PackGroup, slice_layout
 from .hint import HierarchicalAffineCouplingBlock, HintAmdError, _Lease, _Region, _mark_launch, _NONES
 
 
@@ -64,13 +65,9 @@ class ChainRunner:
         self.flow, self.device = flow, device
         self.engines = [blk.tree.engine(device) for blk in flow.blocks]
         self.chainable = len(self.engines) > 0 and all(e.shape_key == self.engines[0].shape_key for e in self.engines)
-        self.slices, cursor = [], 0
-        for e in self.engines:
-            self.slices.append((cursor, cursor + e.total))
-            cursor += e.total
-        self.n_floats = cursor
+        self.slices, self.n_floats = slice_layout([e.total for e in self.engines])
         self.params = [p for e in self.engines for p in e.params]
-        self._pack_group, self._pack_key = None, None
+        self._pack_group = PackGroup(self.engines, device)
         self._pool = {}             # module route: (B, stream) -> free chain instances (handle, key, keep-alive)
         self._infer = {}            # B -> inference chain (no tape, no workspace)
         self._wsbuf = {}            # (B, stream) -> the backward workspaces (scratch inside one stream-ordered call)
@@ -87,9 +84,7 @@ class ChainRunner:
             for handle, _, _ in self._infer.values():
                 self.lib.hint_chain_destroy(handle)
             self._infer = {}
-            if self._pack_group:
-                self.lib.hint_pack_group_destroy(self._pack_group)
-                self._pack_group = None
+            self._pack_group.close()
         except Exception:
             pass
 
@@ -115,30 +110,8 @@ class ChainRunner:
     def pack_all(self, zero_buf=None, rng_state=None, opt_state=None):
         """one launch re-packs every block (hint_pack_group_*); the group is rebuilt whenever an arena or packed buffer
         moved.  With zero_buf / rng_state / opt_state the launch is a training step's prologue (hint_pack_group_run_ex)."""
-        key = tuple((e.arena.data_ptr(), e.packed.data_ptr()) for e in self.engines)
         _mark_launch()
-        if self._pack_key != key:
-            if self._pack_group:
-                self.lib.hint_pack_group_destroy(self._pack_group)
-            n = len(self.engines)
-            plans = (C.c_void_p * n)(*[e.plan.value for e in self.engines])
-            params = (C.c_void_p * n)(*[e.arena.data_ptr() for e in self.engines])
-            packed = (C.c_void_p * n)(*[e.packed.data_ptr() for e in self.engines])
-            handle = C.c_void_p()
-            with torch.cuda.device(self.device):
-                _lib.check(self.lib.hint_pack_group_create(plans, params, packed, n, C.byref(handle)),
-                           "hint_pack_group_create")
-            self._pack_group, self._pack_key = handle, key
-        with torch.cuda.device(self.device):
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-            if zero_buf is not None or rng_state is not None:
-                st = self.lib.hint_pack_group_run_ex(self._pack_group, zero_buf.data_ptr() if zero_buf is not None else None,
-                                                     zero_buf.numel() if zero_buf is not None else 0,
-                                                     rng_state.data_ptr() if rng_state is not None else None,
-                                                     opt_state.data_ptr() if opt_state is not None else None, stream)
-            else:
-                st = self.lib.hint_pack_group_run(self._pack_group, stream)
-        _lib.check(st, "hint_pack_group_run")
+        self._pack_group.run(zero_buf, rng_state, opt_state)
 
     # ---- chains ----------------------------------------------------------------------------------
     def chain_key(self, B: int, perms, G: Optional[torch.Tensor]):

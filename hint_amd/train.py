@@ -11,6 +11,7 @@ ONE all-reduce of the gradient arena (hint_amd/dp.py) and ONE fused clamp+Adam l
 """
 from __future__ import annotations
 
+import ctypes as C
 import math
 import os
 from typing import Optional
@@ -18,91 +19,44 @@ from typing import Optional
 import torch
 
 from . import _lib, dp
+from ._core import TrainerCore, _LossPair
 from .flow import HintFlow
 from .hint import HintAmdError, _as_input
 
 
-class _LossPair:
-    """what step() returns: unpacks to the two loss terms, evaluated lazily so that no kernel
-    is launched for them unless somebody looks"""
+class FlowTrainer(TrainerCore):
+    """seed: of the in-kernel dequantisation noise (None: drawn from os.urandom); rank `rank` of a data-parallel job draws the
+    stream of (seed + 0x9E3779B97F4A7C15 * rank) & (2 ** 63 - 1) (_core.rank_seed), so a seeded job is reproducible rank by rank"""
 
-    def __init__(self, trainer):
-        self._t = trainer
-
-    def __iter__(self):
-        return iter(self._t.last_losses())
-
-
-class FlowTrainer:
     def __init__(self, flow: HintFlow, lr: float = 0.01 * 3e-2, betas=(0.9, 0.95), eps: float = 1e-4,
                  weight_decay: float = 1.86e-5, grad_clamp: float = 5.0, noise: float = 0.01,
                  use_graph: bool = True, group=None, use_chain: bool = True, seed: Optional[int] = None):
-        self.lib = _lib.load()
-        self.flow = flow
-        self._lr, self.betas, self.eps, self.wd = lr, betas, eps, weight_decay
-        self.grad_clamp, self.noise = grad_clamp, noise
-        self.use_graph = use_graph
-        self.group = group
-        self.step_count = 0
         dev = next(flow.parameters()).device
         if dev.type != "cuda":
             raise HintAmdError("FlowTrainer needs the flow on a GPU (no CPU path)")
-        self.device = dev
-        # model-wide arenas; every block's engine is bound to its slice
-        self.engines = [blk.tree.engine(dev) for blk in flow.blocks]
-        self.slices = []
-        cursor = 0
-        for e in self.engines:
-            self.slices.append((cursor, cursor + e.total))
-            cursor += e.total
-        self.n_floats = cursor
-        self.P = torch.zeros(cursor, dtype=torch.float32, device=dev)
-        self.G = torch.zeros(cursor, dtype=torch.float32, device=dev)
-        self.M = torch.zeros(cursor, dtype=torch.float32, device=dev)
-        self.V = torch.zeros(cursor, dtype=torch.float32, device=dev)
-        for e, (a, b) in zip(self.engines, self.slices):
-            e.bind_external_arena(self.P[a:b])
-            e.ensure_arena()
-            e.pack()
-        if dp.world_info(group)[1] > 1:
-            # data-parallel replicas must start from the same weights (the reference idiom
-            # p.data = init_scale*randn_like(p) draws per-process values): rank 0's win; M and V are zero
-            src = torch.distributed.get_global_rank(group, 0) if group is not None else 0
-            torch.distributed.broadcast(self.P, src=src, group=group)
-            # ... and from the same buffers: the fixed permutations between the blocks and the node permutations of
-            # reshuffle=True trees are drawn per process as well (hint.py:36-39 / power_hint_8.py:59-62), and the
-            # kernels read them - replicas with different matrices would sum gradients of different functions
-            for buf in flow.buffers():
-                if buf.is_cuda and buf.numel() > 0:
-                    torch.distributed.broadcast(buf, src=src, group=group)
-            for e in self.engines:
-                e._perm_key = None         # (composed permutations are rebuilt from the received matrices)
-                e.pack()
-        self.loss_acc = torch.zeros(64, 2, dtype=torch.float32, device=dev)   # per-slot partial loss sums
+        # model-wide arenas, every block's engine bound to its slice; step state (TrainerCore)
+        super().__init__(flow, [blk.tree.engine(dev) for blk in flow.blocks], dev, lr, betas, eps, weight_decay, grad_clamp,
+                         noise, use_graph, group, seed)
         self._loss_single = self.loss_acc      # (step_many points loss_acc at its last iteration's sums)
         # chain handles, the one-launch re-pack and the inference chains (sample()) are the flow's ChainRunner's
         self._runner = flow.runner(dev)
         self._runner.perms()                    # (makes the permutation matrices contiguous: the kernels read raw pointers)
         self._graph = None
-        self._static = None
+        self._static = None                     # the captured step's own tensors: x, c, and xn (what its forward perturbs x into)
+        self._graph_many = None                 # step_many: K iterations in one graph, ...
+        self._static_many = None                # ... its inputs x, c [K, B, .] ...
+        self._loss_all = None                   # ... its loss sums [K, 64, 2] ...
+        self._many_losses = None                # ... or, where it runs as K single steps, their loss pairs [K, 2]
+        self._xn = None                         # the perturbed input of the latest un-captured forward
+        self._reduced = False                   # the latest backward pass issued the bucket all-reduces itself
         # identical blocks (the configs stack copies of one block) run as ONE forward launch and
         # TWO backward launches for the whole flow (hint_chain_*)
         self._chainable = use_chain and self._runner.chainable
         # one chain (handle, tapes, workspaces) per batch size: a captured graph keeps raw pointers into
         # its chain's buffers, so a chain is never destroyed while a graph that used it is alive
         self._chains = {}
-        # state of the in-kernel noise generator (hint_chain_forward_noisy): {seed, step}; every rank
-        # of a data-parallel job draws its own stream
-        if seed is None:            # (not from torch's global generator: building a trainer must not shift the caller's random stream)
-            seed = int.from_bytes(os.urandom(8), "little") >> 2
-        rank = dp.world_info(group)[0] if hasattr(dp, "world_info") else 0
-        self.rng_state = torch.tensor([(seed + 0x9E3779B97F4A7C15 * rank) & (2 ** 63 - 1), 0], dtype=torch.int64,
-                                      device=dev)
-        # Adam's hyper-parameters and per-step factors in device memory: with one process (no
-        # all-reduce between backward and optimizer) the fused clamp+Adam launch is captured in the
-        # step's graph and reads them there (hint_adam_step_dev); rng_state[1] is the step count
-        self.opt_state = torch.tensor([lr, betas[0], betas[1], 0.0, 0.0, 0.0, 0.0, 0.0], dtype=torch.float32,
-                                      device=dev)
+        # with one process (no all-reduce between backward and optimizer) the fused clamp+Adam launch is captured in the
+        # step's graph and reads its factors from opt_state
         self._adam_in_graph = False
         self._allreduce_in_graph = False
         # data-parallel jobs all-reduce the gradient arena in ONE bucket behind the backward pass (SURVEY §8e, north_star: "a
@@ -113,15 +67,6 @@ class FlowTrainer:
         self._split = nb // 2 if (self._chainable and nb >= 2 and os.environ.get("HINT_DP_BUCKETS", "1") == "2") else 0
         self._side = None
         self._warming = False       # _capture's warm-up passes issue no collectives (a re-capture on one rank must not hang the others)
-
-    @property
-    def lr(self) -> float:
-        return self._lr
-
-    @lr.setter
-    def lr(self, value: float):          # learning-rate schedules (train_unconditional.py:191-199) need no re-capture
-        self._lr = float(value)
-        self.opt_state[0] = self._lr
 
     def __del__(self):
         try:
@@ -167,9 +112,8 @@ class FlowTrainer:
         elif len(self._chains) >= 8:
             # many batch sizes (ragged data): forget the chains no live graph was captured on
             keep = {self._static["x"].shape[0]} if self._graph is not None and self._static is not None else set()
-            st = getattr(self, "_static_many", None)
-            if getattr(self, "_graph_many", None) is not None and st is not None:
-                keep.add(st["x"].shape[1])
+            if self._graph_many is not None and self._static_many is not None:
+                keep.add(self._static_many["x"].shape[1])
             torch.cuda.synchronize(self.device)
             for b in [b for b in self._chains if b not in keep]:
                 self.lib.hint_chain_destroy(self._chains[b][0])
@@ -185,20 +129,10 @@ class FlowTrainer:
     def _dp_overlap(self) -> bool:
         """the bucket all-reduces are issued from inside the backward pass (side stream) when the backend is RCCL
         (stream-ordered, capturable); with gloo (CPU tests, two ranks on one GPU) they follow the backward pass"""
-        return torch.distributed.is_available() and torch.distributed.is_initialized() and self.P.is_cuda and \
+        return self._dist_on() and self.P.is_cuda and \
             torch.distributed.get_backend(self.group) == "nccl" and os.environ.get("HINT_DP_OVERLAP", "1") != "0"
 
     # ---- the un-captured step body ----------------------------------------------------
-    def _adam_dev(self, scale: float = 1.0):
-        """the fused clamp+Adam launch with its step factors read from opt_state (capturable: nothing in
-        it depends on the host's step count); scale = 1/world turns the all-reduced sum into the mean"""
-        with torch.cuda.device(self.device):
-            st = self.lib.hint_adam_step_dev(self.P.data_ptr(), self.G.data_ptr(), self.M.data_ptr(), self.V.data_ptr(),
-                                             self.n_floats, self.opt_state.data_ptr(), self.betas[0], self.betas[1],
-                                             self.eps, self.wd, scale, self.grad_clamp, 1,
-                                             torch.cuda.current_stream(self.device).cuda_stream)
-        _lib.check(st, "hint_adam_step_dev")
-
     def _fwd_bwd(self, x: torch.Tensor, c: Optional[torch.Tensor], with_adam: bool = False):
         """pack -> forward chain -> backward chain, every piece a direct C-ABI launch: the fixed
         permutations, the running log-det, the two loss sums and the loss gradient are folded
@@ -218,14 +152,13 @@ class FlowTrainer:
             xn = torch.empty_like(x) if noisy else x          # the perturbed input, for the backward pass
             self._xn = xn if noisy else None                  # (kept: a captured step's stays readable in _static["xn"])
             with torch.cuda.device(self.device):
-                stream = torch.cuda.current_stream(self.device).cuda_stream
+                stream = self._stream()
                 _lib.check(self.lib.hint_chain_forward_noisy(
                     chain, x.data_ptr(), cp, z.data_ptr(), J.data_ptr(), None, self.loss_acc.data_ptr(),
                     float(self.noise), self.rng_state.data_ptr() if noisy else None, xn.data_ptr() if noisy else None,
                     stream), "hint_chain_forward_noisy")
                 # dL/dz = z / B and dL/dJ = -1/B: applied inside the kernel
-                dist_on = torch.distributed.is_available() and torch.distributed.is_initialized()
-                if dist_on and self._split > 0:
+                if self._split > 0 and self._dist_on():
                     # part A, then part B in two launches: blocks [h, n) first - their slice of G is final behind it and its
                     # all-reduce starts on a side stream (overlap: RCCL only; gloo blocks the host) - then blocks [0, h)
                     h, n = self._split, len(self.engines)
@@ -261,7 +194,7 @@ class FlowTrainer:
                                                             None, 1.0 / B, -1.0 / B, 1, stream), "hint_chain_backward")
             if with_adam:
                 if self._allreduce_in_graph:      # data-parallel job: the RCCL all-reduces are captured as well
-                    if not getattr(self, "_reduced", False):
+                    if not self._reduced:
                         torch.distributed.all_reduce(self.G, op=torch.distributed.ReduceOp.SUM, group=self.group)
                     self._adam_dev(1.0 / dp.world_info(self.group)[1])
                 else:
@@ -323,14 +256,17 @@ class FlowTrainer:
             e.ensure_arena()
             e.pack()
 
-    def _optimizer(self, grad_scale: float):
-        self.step_count += 1
-        with torch.cuda.device(self.device):
-            st = self.lib.hint_adam_step(self.P.data_ptr(), self.G.data_ptr(), self.M.data_ptr(), self.V.data_ptr(),
-                                         self.n_floats, self.step_count, self.lr, self.betas[0], self.betas[1],
-                                         self.eps, self.wd, grad_scale, self.grad_clamp, 1,
-                                         torch.cuda.current_stream(self.device).cuda_stream)
-        _lib.check(st, "hint_adam_step")
+    def _static_for(self, x, c):
+        """the captured step's own input tensors for this batch shape (captured first where no graph is), holding x and c"""
+        if self._graph is None or self._static["x"].shape != x.shape:
+            self._capture(x, c)
+        st = self._static
+        # (a batch that already sits in the graph's input buffers - input_buffers() - is not copied again)
+        if x.data_ptr() != st["x"].data_ptr():
+            st["x"].copy_(x)
+        if c is not None and c.data_ptr() != st["c"].data_ptr():
+            st["c"].copy_(c)
+        return st
 
     def step(self, x: torch.Tensor, c: Optional[torch.Tensor] = None):
         """one training iteration on this rank's shard; returns device scalars (l0, l1) =
@@ -343,13 +279,7 @@ class FlowTrainer:
         else:
             if self._graph is not None and any(e.params[0].data_ptr() != e._ptrs[0] for e in self.engines):
                 self._graph = None             # parameters were rebound from outside (p.data = ..., .to()): re-capture
-            if self._graph is None or self._static["x"].shape != x.shape:
-                self._capture(x, c)
-            # (a batch that already sits in the graph's input buffers - input_buffers() - is not copied again)
-            if x.data_ptr() != self._static["x"].data_ptr():
-                self._static["x"].copy_(x)
-            if c is not None and c.data_ptr() != self._static["c"].data_ptr():
-                self._static["c"].copy_(c)
+            self._static_for(x, c)
             self._graph.replay()
         self._last_B = x.shape[0]
         for e in self.engines:                 # the step's kernels changed the weights in place: packed copies are stale
@@ -357,21 +287,49 @@ class FlowTrainer:
         if self.use_graph and self._adam_in_graph:
             self.step_count += 1               # the optimizer ran inside the graph
         else:
-            if getattr(self, "_reduced", False) and not self.use_graph:
+            if self._reduced and not self.use_graph:
                 scale = 1.0 / dp.world_info(self.group)[1]     # (the eager backward pass issued the bucket all-reduces itself)
-            elif self._split > 0 and torch.distributed.is_available() and torch.distributed.is_initialized():
+            elif self._split > 0 and self._dist_on():
                 cut = self.slices[self._split][0]              # the same two buckets, one after the other
                 dp.allreduce_sum_(self.G[cut:], self.group)
                 scale = dp.allreduce_sum_(self.G[:cut], self.group)
             else:
                 scale = dp.allreduce_sum_(self.G, self.group)
-            self._optimizer(scale)
+            self._adam_host(scale)
         return _LossPair(self)
 
     # ---- several iterations per graph replay ----------------------------------------------------
     def _many_ok(self) -> bool:
-        return self.use_graph and self._chainable and dp.world_info(self.group)[1] == 1 and \
-            not (torch.distributed.is_available() and torch.distributed.is_initialized())
+        return self.use_graph and self._chainable and dp.world_info(self.group)[1] == 1 and not self._dist_on()
+
+    def _warm_passes(self, x, c):
+        """in front of a capture: two un-captured passes on a side stream (allocator, plan LDS attrs), no optimizer"""
+        side = torch.cuda.Stream(device=self.device)
+        side.wait_stream(torch.cuda.current_stream(self.device))
+        with torch.cuda.stream(side):
+            for _ in range(2):
+                self._fwd_bwd(x, c)
+        torch.cuda.current_stream(self.device).wait_stream(side)
+        self.G.zero_()                         # the warm-up runs accumulated into the gradient arena
+
+    def _ready_to_capture(self, load_adam: bool):
+        """the last thing before a capture: the optimizer kernel loaded (where the graph will hold it), the device step
+        counter aligned with the host's, the device idle"""
+        if load_adam:
+            self._adam_warm_load()
+        self.rng_state[1] = self.step_count
+        torch.cuda.synchronize(self.device)
+
+    def _static_many_for(self, xs, cs):
+        """step_many's own input tensors for this shape (captured first where no graph is), holding xs and cs"""
+        if self._graph_many is None or self._static_many["x"].shape != xs.shape:
+            self._capture_many(xs, cs)
+        st = self._static_many
+        if xs.data_ptr() != st["x"].data_ptr():
+            st["x"].copy_(xs)
+        if cs is not None and cs.data_ptr() != st["c"].data_ptr():
+            st["c"].copy_(cs)
+        return st
 
     def _capture_many(self, xs: torch.Tensor, cs: Optional[torch.Tensor]):
         """K = xs.shape[0] consecutive iterations (re-pack, forward, backward, clamp+Adam each) in ONE
@@ -381,21 +339,9 @@ class FlowTrainer:
         self._check_arenas()
         sx = xs.clone()
         sc = cs.clone() if cs is not None else None
-        side = torch.cuda.Stream(device=self.device)
-        side.wait_stream(torch.cuda.current_stream(self.device))
-        with torch.cuda.stream(side):          # warm-up on a side stream (allocator, plan LDS attrs); no optimizer
-            for _ in range(2):
-                self._fwd_bwd(sx[0], sc[0] if sc is not None else None)
-        torch.cuda.current_stream(self.device).wait_stream(side)
-        self.G.zero_()
-        scratch = torch.zeros(4, 4, dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):   # load the optimizer kernel outside the capture
-            self.lib.hint_adam_step(scratch[0].data_ptr(), scratch[1].data_ptr(), scratch[2].data_ptr(),
-                                    scratch[3].data_ptr(), 4, 1, 0.0, 0.9, 0.95, 1e-4, 0.0, 1.0, 0.0, 0,
-                                    torch.cuda.current_stream(self.device).cuda_stream)
-        self.rng_state[1] = self.step_count
+        self._warm_passes(sx[0], sc[0] if sc is not None else None)
         self._loss_all = torch.zeros(K, 64, 2, dtype=torch.float32, device=self.device)
-        torch.cuda.synchronize(self.device)
+        self._ready_to_capture(load_adam=True)
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
             for k in range(K):
@@ -416,14 +362,7 @@ class FlowTrainer:
                 out.append(torch.stack(self.last_losses()))
             self._many_losses = torch.stack(out)
             return
-        st = getattr(self, "_static_many", None)
-        if getattr(self, "_graph_many", None) is None or st["x"].shape != xs.shape:
-            self._capture_many(xs, cs)
-            st = self._static_many
-        if xs.data_ptr() != st["x"].data_ptr():
-            st["x"].copy_(xs)
-        if cs is not None and cs.data_ptr() != st["c"].data_ptr():
-            st["c"].copy_(cs)
+        self._static_many_for(xs, cs)
         self._graph_many.replay()
         for e in self.engines:
             e._pack_key = None
@@ -434,7 +373,7 @@ class FlowTrainer:
 
     def step_losses(self) -> torch.Tensor:
         """[K, 2] device tensor: (-log p(z), -log|det J|) of every iteration of the last step_many()"""
-        if getattr(self, "_many_losses", None) is not None:
+        if self._many_losses is not None:
             return self._many_losses
         s = self._loss_all.sum(dim=1)
         return torch.stack([s[:, 0] / self._last_B, -s[:, 1] / self._last_B], dim=1)
@@ -444,13 +383,7 @@ class FlowTrainer:
         xs, cs = self._inputs(xs, cs, many=True, what="xs")
         if not self._many_ok():
             return xs, cs
-        st = getattr(self, "_static_many", None)
-        if getattr(self, "_graph_many", None) is None or st["x"].shape != xs.shape:
-            self._capture_many(xs, cs)
-            st = self._static_many
-        st["x"].copy_(xs)
-        if cs is not None:
-            st["c"].copy_(cs)
+        st = self._static_many_for(xs, cs)
         return st["x"], st["c"]
 
     def input_buffers(self, x: torch.Tensor, c: Optional[torch.Tensor] = None):
@@ -462,12 +395,8 @@ class FlowTrainer:
         x, c = self._inputs(x, c)
         if not self.use_graph:
             return x, c
-        if self._graph is None or self._static["x"].shape != x.shape:
-            self._capture(x, c)
-        self._static["x"].copy_(x)
-        if c is not None:
-            self._static["c"].copy_(c)
-        return self._static["x"], self._static["c"]
+        st = self._static_for(x, c)
+        return st["x"], st["c"]
 
     def timed_step(self, x: torch.Tensor, c: Optional[torch.Tensor] = None):
         """one un-captured training step with HIP events between the launches (on the stream they
@@ -486,7 +415,7 @@ class FlowTrainer:
         cp = c.data_ptr() if c is not None else None
         noisy = self.noise > 0
         with torch.cuda.device(self.device):
-            stream = torch.cuda.current_stream(self.device).cuda_stream
+            stream = self._stream()
             ev[0].record()
             self._pack_all(step_prologue=True)
             ev[1].record()
@@ -501,7 +430,7 @@ class FlowTrainer:
                 ev[k].record()
             self._last_B = B
             scale = dp.allreduce_sum_(self.G, self.group)
-            self._optimizer(scale)
+            self._adam_host(scale)
             ev[5].record()
         torch.cuda.synchronize(self.device)
         fwd, bwd = self.kernel_names(B)
@@ -511,8 +440,7 @@ class FlowTrainer:
     def allreduce_plan(self) -> str:
         """what the step does with the gradient arena between backward and optimizer (for bench.py's config line)"""
         world = dp.world_info(self.group)[1]
-        dist_on = torch.distributed.is_available() and torch.distributed.is_initialized()
-        if not dist_on:
+        if not self._dist_on():
             return "none (one process: clamp + Adam ride in the weight gradients' final reduction)"
         backend = torch.distributed.get_backend(self.group)
         where = "captured in the step's hipGraph" if self._allreduce_in_graph else "issued from the host after the graph replay"
@@ -524,7 +452,6 @@ class FlowTrainer:
     def kernel_names(self, B: int):
         """(forward, backward part A) kernel of a batch of B rows as rocprof prints them: the wave-local kernels for narrow
         trees (template arguments: direction / row tiles per workgroup), the general ones otherwise"""
-        import ctypes as C
         info = (C.c_int32 * 8)()
         _lib.check(self.lib.hint_plan_describe(self.engines[0].plan, B, info), "hint_plan_describe")
         if info[0]:     # (third template argument: a chained launch - the trainer's)
@@ -542,22 +469,16 @@ class FlowTrainer:
         self._check_arenas()
         sx = x.clone()
         sc = c.clone() if c is not None else None
-        side = torch.cuda.Stream(device=self.device)
-        side.wait_stream(torch.cuda.current_stream(self.device))
-        self._warming = True
+        self._warming = True                   # no collectives in the warm-up passes
         try:
-            with torch.cuda.stream(side):      # warm-up on a side stream (allocator, plan LDS attrs); no collectives
-                for _ in range(2):
-                    self._fwd_bwd(sx, sc)
+            self._warm_passes(sx, sc)
         finally:
             self._warming = False
-        torch.cuda.current_stream(self.device).wait_stream(side)
-        self.G.zero_()                         # the warm-up runs accumulated into the gradient arena
         torch.cuda.synchronize(self.device)
         # one process, identical blocks: the optimizer launch goes into the graph as well (no host
         # gap between the weight-gradient kernel and Adam).  Its kernel has been loaded by a launch
         # outside the capture; the device step counter is aligned with the host's.
-        dist_on = torch.distributed.is_available() and torch.distributed.is_initialized()
+        dist_on = self._dist_on()
         # RCCL collectives can be captured (backend "nccl"): the whole data-parallel iteration - backward,
         # gradient all-reduce, clamp+Adam - is then one graph replay per rank (HINT_GRAPH_ALLREDUCE=0: off)
         self._allreduce_in_graph = self._chainable and dist_on and self.P.is_cuda and \
@@ -567,14 +488,7 @@ class FlowTrainer:
             warm = torch.zeros(8, dtype=torch.float32, device=self.device)
             torch.distributed.all_reduce(warm, group=self.group)
             torch.cuda.synchronize(self.device)
-        if self._adam_in_graph:
-            scratch = torch.zeros(4, 4, dtype=torch.float32, device=self.device)
-            with torch.cuda.device(self.device):
-                self.lib.hint_adam_step(scratch[0].data_ptr(), scratch[1].data_ptr(), scratch[2].data_ptr(),
-                                        scratch[3].data_ptr(), 4, 1, 0.0, 0.9, 0.95, 1e-4, 0.0, 1.0, 0.0, 0,
-                                        torch.cuda.current_stream(self.device).cuda_stream)
-        self.rng_state[1] = self.step_count
-        torch.cuda.synchronize(self.device)
+        self._ready_to_capture(load_adam=self._adam_in_graph)
         g = torch.cuda.CUDAGraph()
         try:
             # (thread_local: the process group's watchdog thread may touch the HIP runtime meanwhile)
@@ -591,14 +505,7 @@ class FlowTrainer:
             with torch.cuda.graph(g):
                 self._fwd_bwd(sx, sc, with_adam=False)
         self._graph = g
-        self._static = dict(x=sx, c=sc, xn=getattr(self, "_xn", None))     # xn: what the captured forward perturbs x into
-
-    def last_losses(self):
-        """(-log p(z), -log|det J|) of the most recent step's local shard as device scalars
-        (train_unconditional.py:162 labels).  The sums live in a buffer the next step overwrites:
-        read them before stepping again."""
-        s = self.loss_acc.sum(dim=0)
-        return s[0] / self._last_B, -s[1] / self._last_B
+        self._static = dict(x=sx, c=sc, xn=self._xn)     # xn: what the captured forward perturbs x into
 
     @torch.no_grad()
     def sample(self, z: torch.Tensor, c: Optional[torch.Tensor] = None):
@@ -619,7 +526,7 @@ class FlowTrainer:
         chain = self._chain_infer(B)
         with torch.cuda.device(self.device):
             _lib.check(self.lib.hint_chain_inverse(chain, z.data_ptr(), c.data_ptr() if c is not None else None, x.data_ptr(),
-                                                   J.data_ptr(), None, torch.cuda.current_stream(self.device).cuda_stream),
+                                                   J.data_ptr(), None, self._stream()),
                        "hint_chain_inverse")
         return x, J
 

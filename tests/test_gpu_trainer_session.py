@@ -358,7 +358,9 @@ def test_refused_inputs_launch_nothing():
     ctr.step(cx, cy)
     torch.cuda.synchronize()
     before = (tr.step_count, tr.P.clone(), ctr.step_count, ctr.P.clone())
-    libs = [(o, o.lib) for o in (tr, tr._runner, trc, trc._runner, ctr)]
+    # (every object that holds a library handle of its own: the trainers, their runners, and the re-pack groups of both)
+    libs = [(o, o.lib) for o in (tr, tr._runner, tr._runner._pack_group, trc, trc._runner, trc._runner._pack_group,
+                                 ctr, ctr._pack_group)]
     for o, _ in libs:
         o.lib = _NoLaunch()
     try:

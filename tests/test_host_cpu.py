@@ -161,3 +161,31 @@ def test_data_alias_edits_do_not_advance_the_version_counter():
     assert p._version == v0 + 1
     p.data = torch.randn(8)
     assert p.data_ptr() != a0
+
+
+# ---- the trainers' pure helpers (hint_amd/_core.py) ----
+@pytest.mark.parametrize("sizes, slices, total", [
+    ([], [], 0),                                               # no engines
+    ([5], [(0, 5)], 5),
+    ([3, 0, 4], [(0, 3), (3, 3), (3, 7)], 7),                  # a zero-size entry takes an empty slice and moves nothing
+    ([0], [(0, 0)], 0),
+    ([7, 7, 7, 1], [(0, 7), (7, 14), (14, 21), (21, 22)], 22),
+])
+def test_slice_layout(sizes, slices, total):
+    from hint_amd._core import slice_layout
+    assert slice_layout(sizes) == (slices, total)
+    assert slice_layout(iter(sizes)) == (slices, total)        # (the trainers pass a list; anything iterable once will do)
+
+
+@pytest.mark.parametrize("seed", [0, 1, 1234, 2 ** 62 - 1, 2 ** 62 + 12345, 2 ** 63 - 1])
+def test_rank_seed(seed):
+    import noise_oracle
+    from hint_amd._core import rank_seed
+    for rank in (0, 1, 7):
+        got = rank_seed(seed, rank)
+        assert got == noise_oracle.rank_seed(seed, rank)                  # the rule the noise tests' oracle keys its ranks by
+        assert got == (seed + 0x9E3779B97F4A7C15 * rank) & (2 ** 63 - 1)
+        assert 0 <= got < 2 ** 63
+        assert torch.tensor([got], dtype=torch.int64).item() == got       # fits the int64 rng_state
+    assert rank_seed(seed, 0) == seed                                     # rank 0 (and a single process) keeps the seed
+    assert len({rank_seed(seed, r) for r in (0, 1, 7)}) == 3              # every rank its own stream

@@ -42,6 +42,13 @@ class AbcDesc(C.Structure):
                 ("idx", C.c_void_p), ("dist", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
 
 
+class CurveDesc(C.Structure):
+    """mirror of `hint_curve_desc` (include/hint_amd.h)"""
+    _fields_ = [("x", C.c_void_p), ("n_rows", C.c_int64), ("n_coeffs", C.c_int32), ("n_points", C.c_int32),
+                ("eps", C.c_void_p), ("noise", C.c_float), ("target", C.c_void_p), ("y", C.c_void_p), ("dist", C.c_void_p),
+                ("mean", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("max_groups", C.c_int32)]
+
+
 _lib = None
 
 _PROTOS = {
@@ -115,6 +122,9 @@ _PROTOS = {
     "hint_abc_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32]),
     "hint_abc_run": (C.c_int, [C.POINTER(AbcDesc), C.c_void_p]),
     "hint_abc_geometry": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
+    "hint_curve_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32]),
+    "hint_curve_run": (C.c_int, [C.POINTER(CurveDesc), C.c_void_p]),
+    "hint_curve_geometry": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32, C.c_int32]),
 }
 
 

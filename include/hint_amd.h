@@ -453,6 +453,51 @@ size_t hint_abc_workspace_bytes(int64_t n_rows, int32_t ny, int32_t k);
 int hint_abc_run(const hint_abc_desc* desc, void* stream);
 int64_t hint_abc_geometry(int64_t n_rows, int32_t ny, int32_t field);
 
+/* The lens-shape simulator and the target distance of the reference's evaluation loop (data.py:127-139 LensShapeModel.forward_process
+ * over data.py:51-57 trace_fourier_curves, a Python loop with a 100 x 100 pdist matrix per row; rejection_sampling.py:99-102
+ * mean_target_distance, called at :204 on 4000 samples per model and run; rejection_sampling.py:76-85 prepare_samples runs the
+ * simulator over 1e8 prior rows).  For x [n_rows, 4 K], K = n_coeffs odd, laid out as data.py:30-40 flatten_coeffs does (x[:, :2K]
+ * real parts as [2 axes, K], x[:, 2K:] imaginary parts; coefficient k belongs to frequency m = k - K/2), and P = n_points:
+ *   p[t, axis] = sum_k re[axis,k] cos(2 pi m t / (P-1)) - im[axis,k] sin(2 pi m t / (P-1)), t = 0 .. P-1: fp32 fused multiply-adds
+ *         onto the sum over k ascending (real term, then imaginary term); each twiddle the true value rounded to fp32, the angle
+ *         reduced exactly ((|m| t) mod (P-1) in integers, sincospi in double), so point P-1 repeats point 0 bit for bit
+ *   D(i,j) = fma(dy, dy, dx dx) of p_i - p_j in fp32, i < j; the chosen pair is the first maximum in row-major (i, j) order, a NaN
+ *         D never wins, the start value is pair (0, 1)
+ *   y[row] = (p_j.y - p_i.y, p_j.x - p_i.x), each fma(noise, eps[row], .) when eps is given
+ *   dist[row] = sqrt(fma(d1, d1, d0 d0)), d = y[row] - target;  mean = (sum of dist in double) / n_rows as fp32, summed in a fixed
+ *         order: per wavefront over its consecutive rows, then over the wavefronts in row order (no float atomics, no counters)
+ * A row's y and dist do not depend on n_rows, on where the row stands, on max_groups or on what y, dist, mean or the workspace
+ * held; two runs agree bit for bit.  Rows with non-finite x give unspecified values and disturb no other row.
+ *   run              stream-ordered on the current device: one launch (two with mean), no host synchronisation, no allocation
+ *                    (capturable).  eps, target, dist, mean may be NULL; the workspace is used (and checked) only with mean.
+ *                    max_groups: 0 = the default grid, otherwise the workgroups at most (values above the cap mean the cap).
+ *                    Rejects, before any device call and naming the field: a null x or y; n_rows outside 1..2^30; n_coeffs even
+ *                    or outside 1..25; n_points outside 2..128; dist or mean without target; max_groups < 0; a noise that is not
+ *                    finite; a pointer that is not 4-byte (workspace: 16-byte) aligned; with mean, a null workspace or one smaller
+ *                    than workspace_bytes says.
+ *   workspace_bytes  0 (and an error message) for sizes run would reject.  64 KiB whatever n_rows is (one double per wavefront
+ *                    of the largest grid).
+ *   geometry         host only, for the default grid: field 0 the workgroups, 1 the rows a workgroup has in flight (a tile: one per
+ *                    wavefront), 2 the consecutive rows each wavefront owns (wavefront q: rows [q R, min(n_rows, (q + 1) R)),
+ *                    R = ceil(n_rows / (tile x workgroups))), 3 the grid cap.  -1 on an error.
+ * None of these has a caller's device buffer among its parameters: the buffers are named by the descriptor. */
+typedef struct hint_curve_desc {
+    const float* x;                        /* [n_rows, 4 n_coeffs] row-major, 4-byte aligned */
+    int64_t n_rows;
+    int32_t n_coeffs, n_points;            /* K odd 1..25, P 2..128 */
+    const float* eps;                      /* NULL, or device float[n_rows, 2] */
+    float noise;
+    const float* target;                   /* NULL, or device float[2] */
+    float* y;                              /* device float[n_rows, 2] */
+    float* dist;                           /* NULL, or device float[n_rows] */
+    float* mean;                           /* NULL, or device float */
+    void* workspace; size_t workspace_bytes;
+    int32_t max_groups;
+} hint_curve_desc;
+size_t hint_curve_workspace_bytes(int64_t n_rows, int32_t n_coeffs, int32_t n_points);
+int hint_curve_run(const hint_curve_desc* desc, void* stream);
+int64_t hint_curve_geometry(int64_t n_rows, int32_t n_coeffs, int32_t n_points, int32_t field);
+
 int hint_abi_version(void);
 const char* hint_last_error(void);
 /* what the library binary was built with and runs with: "libhint_amd abi N, gfx950, HIP x.y.z, clang ..., src <12 hex digits: hash

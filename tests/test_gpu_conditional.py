@@ -102,6 +102,30 @@ class OracleComposition:
         return x, J
 
 
+def assert_step_matches_oracle(tr, mods, Po, got, l0, l1, jx):
+    """one ConditionalFlowTrainer step (beta1 = 0, lr = 0, no clamp, no decay: exp_avg = g) against a float64 oracle whose
+    parameters Po[module name][tensor name] carry .grad of the same loss: the loss pair and x_jac (train_conditional.py:50-55)
+    to 1e-4, every parameter tensor's gradient - read out of the optimizer's first moment - to 1e-4 of its norm (+ 1e-6 of the
+    largest gradient entry per element), and all of them together to 1e-4.  mods: (name, module, dc) in the trainer's order"""
+    import math
+    g0, g1 = got
+    assert abs(float(g0) - float(l0)) <= 1e-4 * abs(float(l0)) and abs(float(g1) - float(l1)) <= 1e-4 * max(1.0, abs(float(l1)))
+    Jx = tr.last[2].detach().double().cpu()
+    assert float((Jx - jx.detach()).abs().max()) <= 1e-4 * max(1.0, float(jx.detach().abs().max()))
+    gmax = max(float(p.grad.abs().max()) for d_ in Po.values() for p in d_.values())
+    num = den = 0.0
+    for (name, sub, _), (a, b), eng in zip(mods, tr.slices, tr.engines):
+        named = {id(q): k for k, q in sub.named_parameters()}
+        for p, g in zip(eng.params, eng.split_flat(tr.M[a:b])):
+            r = Po[name][named[id(p)]].grad
+            gg = g.detach().double().cpu()
+            tn, tr_ = float(((gg - r) ** 2).sum()) ** 0.5, float((r ** 2).sum()) ** 0.5
+            num += tn * tn; den += tr_ * tr_
+            assert tn <= 1e-4 * tr_ + 1e-6 * gmax * math.sqrt(r.numel()), (name, named[id(p)], tn, tr_)
+    assert math.sqrt(num / den) <= 1e-4
+    return math.sqrt(num / den)
+
+
 @pytest.mark.parametrize("D,dc,h,B", [(5, 2, 16, 77), (100, 4, 224, 300), (1, 3, 8, 16)])
 def test_external_affine_coupling_matches_oracle(D, dc, h, B):
     torch.manual_seed(1)
@@ -343,7 +367,6 @@ def test_conditional_trainer_gradient_at_4096_rows():
     lr = 0 the fused clamp + Adam epilogue leaves exp_avg = g and the weights where they were.  The 4096 rows are the first
     4096 of a pool whose float64 pre-activations all keep 5e-7 away from a ReLU kink (either subgradient is right there);
     the pool's remaining rows - the ones next to a kink included - are checked on the forward results (z_x, z_y, x_jac)."""
-    import math
     from test_gpu_chain_workloads import KINK
     torch.manual_seed(5)
     nx, ny, nb, hidden, B, POOL = 100, 4, 4, 224, 4096, 4608
@@ -410,21 +433,8 @@ def test_conditional_trainer_gradient_at_4096_rows():
     w0 = tr.P.clone()
     g0, g1 = tr.step(x.to(DEV), y.to(DEV))
     assert tr._graph is not None
-    assert abs(float(g0) - float(l0)) <= 1e-4 * abs(float(l0)) and abs(float(g1) - float(l1)) <= 1e-4 * max(1.0, abs(float(l1)))
-    Jx = tr.last[2].detach().double().cpu()
-    assert float((Jx - jx.detach()).abs().max()) <= 1e-4 * max(1.0, float(jx.detach().abs().max()))
+    assert_step_matches_oracle(tr, mods, Po, (g0, g1), l0, l1, jx)
     assert torch.equal(tr.P, w0)                          # lr = 0: the weights did not move
-    gmax = max(float(p.grad.abs().max()) for d_ in Po.values() for p in d_.values())
-    num = den = 0.0
-    for (name, sub, _), (a, b), eng in zip(mods, tr.slices, tr.engines):
-        named = {id(q): k for k, q in sub.named_parameters()}
-        for p, g in zip(eng.params, eng.split_flat(tr.M[a:b])):
-            r = Po[name][named[id(p)]].grad
-            gg = g.detach().double().cpu()
-            tn, tr_ = float(((gg - r) ** 2).sum()) ** 0.5, float((r ** 2).sum()) ** 0.5
-            num += tn * tn; den += tr_ * tr_
-            assert tn <= 1e-4 * tr_ + 1e-6 * gmax * math.sqrt(r.numel()), (name, named[id(p)], tn, tr_)
-    assert math.sqrt(num / den) <= 1e-4
 
     # the rest of the pool (kink rows included), forward only: z_x, z_y and x_jac of every row on the same fast path
     rest = torch.ones(POOL, dtype=torch.bool); rest[idx] = False

@@ -590,7 +590,7 @@ int hint_adam_step(float* params, float* grads, float* exp_avg, float* exp_avg_s
     const double bc2 = 1.0 - std::pow((double)beta2, (double)step);
     HIP_TRY(launch_adam(params, grads, exp_avg, exp_avg_sq, (long)n, (float)((double)lr / bc1), beta1, beta2,
                         (float)(1.0 / std::sqrt(bc2)), eps, weight_decay, grad_scale,
-                        grad_clamp > 0.f ? grad_clamp : 3.0e38f, zero_grads ? 1 : 0, adam_num_cu(), nullptr,
+                        grad_clamp > 0.f ? grad_clamp : HINT_NO_CLAMP, zero_grads ? 1 : 0, adam_num_cu(), nullptr,
                         (hipStream_t)stream));
     return 0;
 }
@@ -604,7 +604,7 @@ int hint_adam_step_dev(float* params, float* grads, float* exp_avg, float* exp_a
     if ((((uintptr_t)params | (uintptr_t)grads | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & 15) != 0)
         return fail("hint_adam_step_dev: buffers must be 16-byte aligned");
     HIP_TRY(launch_adam(params, grads, exp_avg, exp_avg_sq, (long)n, 0.f, beta1, beta2, 0.f, eps, weight_decay,
-                        grad_scale, grad_clamp > 0.f ? grad_clamp : 3.0e38f, zero_grads ? 1 : 0, adam_num_cu(),
+                        grad_scale, grad_clamp > 0.f ? grad_clamp : HINT_NO_CLAMP, zero_grads ? 1 : 0, adam_num_cu(),
                         opt_state, (hipStream_t)stream));
     return 0;
 }
@@ -706,7 +706,7 @@ int hint_adam_multi_step(const hint_adam_multi* h, int32_t step, float lr, float
     const double bc2 = 1.0 - std::pow((double)beta2, (double)step);
     HIP_TRY(launch_adam_multi(h->segs, h->chunks, (long)h->n_chunks, (float)((double)lr / bc1), beta1, beta2,
                               (float)(1.0 / std::sqrt(bc2)), eps, weight_decay, grad_scale,
-                              grad_clamp > 0.f ? grad_clamp : 3.0e38f, zero_grads ? 1 : 0, h->num_cu, (hipStream_t)stream));
+                              grad_clamp > 0.f ? grad_clamp : HINT_NO_CLAMP, zero_grads ? 1 : 0, h->num_cu, (hipStream_t)stream));
     return 0;
 }
 

@@ -20,11 +20,15 @@ struct AdamFuse {
 struct AdamSeg { float* p; float* g; float* m; float* v; int64_t n; };
 struct AdamChunk { int32_t seg; int32_t len; int64_t off; };
 constexpr int ADAM_CHUNK = 1024;    // floats: one f32x4 per lane of a 256-thread workgroup
+// the bound the entry points pass for grad_clamp <= 0: no finite gradient and no inf is beyond it, so nothing is clamped
+#define HINT_NO_CLAMP (__builtin_huge_valf())
 
 __device__ __forceinline__ void adam_update(float& p, float& m, float& v, float g, float lr_t, float b1, float b2,
                                             float inv_sqrt_bc2, float eps, float wd, float gscale, float gclamp) {
     float gj = g * gscale;
-    gj = fminf(fmaxf(gj, -gclamp), gclamp);
+    // torch.clamp's semantics: a NaN gradient fails both comparisons and stays NaN (fminf / fmaxf would return the bound), and
+    // gclamp = HINT_NO_CLAMP (+inf) clamps nothing, inf included.  Finite gradients get the bits min / max gave them.
+    gj = gj < -gclamp ? -gclamp : (gj > gclamp ? gclamp : gj);
     gj = gj + wd * p;
     m = b1 * m + (1.f - b1) * gj;
     v = b2 * v + (1.f - b2) * gj * gj;

@@ -215,7 +215,7 @@ int hint_chain_backward_adam(const hint_chain* C, const float* x, const float* c
             return fail("hint_chain_backward_adam: block %d's parameters are not a 16-byte aligned slice of the arena [params, params + n)", i);
     }
     AdamFuse ad{params, exp_avg, exp_avg_sq, opt_state, beta1, beta2, eps, weight_decay, grad_scale,
-                grad_clamp > 0.f ? grad_clamp : 3.0e38f};
+                grad_clamp > 0.f ? grad_clamp : HINT_NO_CLAMP};
     return run_backward(P, C->host[0], C->d_table, C->host.data(), C->n, 0, C->n, x, c, g_z, g_J, g_x, g_c, gz_scale, gJ_const, C->B, 1, 3,
                         (hipStream_t)stream, &ad);
 }
@@ -238,7 +238,7 @@ int hint_chain_wgrad_adam(const hint_chain* C, const float* x, const float* c, f
             return fail("hint_chain_wgrad_adam: block %d's parameters are not a 16-byte aligned slice of the arena [params, params + n)", i);
     }
     AdamFuse ad{params, exp_avg, exp_avg_sq, opt_state, beta1, beta2, eps, weight_decay, grad_scale,
-                grad_clamp > 0.f ? grad_clamp : 3.0e38f};
+                grad_clamp > 0.f ? grad_clamp : HINT_NO_CLAMP};
     return run_backward(P, C->host[0], C->d_table, C->host.data(), C->n, 0, C->n, x, c, nullptr, nullptr, nullptr, nullptr, 1.f, 0.f, C->B, 1, 2,
                         (hipStream_t)stream, &ad);
 }

@@ -71,7 +71,12 @@ __global__ __launch_bounds__(64 * EXT_NW) void hint_ext_coeff_kernel(ExtArgs a) 
         }
     }
     __syncthreads();
-    // third layer (h -> r) on the matrix pipe, then the clamp of the s net (hint.py:56-60)
+    // third layer (h -> r) on the matrix pipe, then the clamp of the s net (hint.py:56-60).  The ReLUs above return 0 for a NaN
+    // pre-activation, so a NaN or inf in a condition row would leave finite coefficients where the reference has NaN: pz is +0
+    // for a finite row and NaN for any other (hint_fwd.hip poisons its rows the same way)
+    float pz = 0.f;
+    for (int k = 0; k < a.dc; ++k) pz += cs[m * a.dc + k];
+    pz = pz - pz;
     for (int nt = wave; nt < a.RT; nt += EXT_NW) {
         f32x4 acc;
         ext_gemm(acc, (const GLOBAL_AS float*)a.packed + (size_t)(a.f3[net] + nt * a.NT) * 256, a.NT, a2, ld, lane);
@@ -81,7 +86,7 @@ __global__ __launch_bounds__(64 * EXT_NW) void hint_ext_coeff_kernel(ExtArgs a) 
             for (int i = 0; i < 4; ++i) {
                 const int f = nt * 16 + fq + i;
                 if (f < a.r) {
-                    const float v = acc[i] + B3[f];
+                    const float v = (acc[i] + B3[f]) + pz;
                     out[f] = net == 0 ? a.alpha * atanf(v) : v;
                 }
             }

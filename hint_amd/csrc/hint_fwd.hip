@@ -104,6 +104,20 @@ __global__ __launch_bounds__(64 * MAX_NW) void hint_apply_kernel(
         if (a.dc > 0) load_tile(cs, a.cld, c, a.dc, row0, a.B, tid, nthreads);
         if (tid < 2 * ROWS) jac[tid] = 0.f;
         __syncthreads();                      // meta and the lane tile visible
+        if (a.dc > 0) {
+            // A NaN or inf in a row's condition reaches every subnet of that row in the reference and makes the row's z and J
+            // NaN.  Here the ReLU of the first layer is fmaxf(v, 0), which returns 0 for a NaN pre-activation: s and t of the
+            // row would come out finite.  So the row is poisoned where it is loaded: csum - csum is +0 for a finite condition
+            // (x + 0 keeps the bits of every x but -0) and NaN for any other.
+            for (int i = tid; i < ROWS * (a.d + 1); i += nthreads) {
+                const int r = fdiv(i, frcp(a.d + 1)), j = i - r * (a.d + 1);
+                float csum = 0.f;
+                for (int k = 0; k < a.dc; ++k) csum += cs[r * a.cld + k];
+                const float pz = csum - csum;
+                if (j < a.d) XS[r * a.xld + j] += pz; else jac[r] = pz;
+            }
+            __syncthreads();
+        }
         if (!REV && rng_state != nullptr) {
             // x += noise * N(0,1), four values per Philox call, keyed by (seed, step, element group)
             const unsigned long long seed = rng_state[0], step = rng_state[1];

@@ -101,6 +101,11 @@ class ClampAdam(torch.optim.Optimizer):
     """torch.optim.Adam (L2 weight decay, no AMSGrad) with the gradient scaled by `grad_scale`, then clamped to
     +-`grad_clamp` (0: no clamp), for all parameters of a group in one kernel launch.
 
+    Non-finite gradients take the step `p.grad.data.clamp_(-c, c)` + `torch.optim.Adam.step()` take: the clamp is torch.clamp's,
+    so a NaN gradient stays NaN and makes that element of p, exp_avg and exp_avg_sq NaN for good (a diverged run shows, it does
+    not keep "training"), +-inf becomes +-grad_clamp, and with grad_clamp = 0 nothing at all is clamped: an inf gradient makes
+    both moments inf and the parameter NaN, as torch.optim.Adam alone does (tests/test_gpu_nonfinite.py).
+
     state[p] holds torch's keys (`step`, `exp_avg`, `exp_avg_sq`) with torch's shapes; the moments are views into flat buffers
     this object owns.  state_dict() returns copies, load_state_dict() copies into the flat buffers, and both exchange with
     torch.optim.Adam over the same parameters.  `table_builds` counts how often the device tables were rebuilt (parameters or

@@ -162,7 +162,10 @@ void hint_pack_group_destroy(hint_pack_group* group);
 
 /* z, J = block(x | c), rev=False (hint.py:62-80,90,97-99).  c may be NULL iff dc == 0.
  * params: flat parameters (biases are read from here); packed: output of hint_block_pack.
- * tape: NULL for inference, else hint_plan_tape_floats(plan, B) floats (training). */
+ * tape: NULL for inference, else hint_plan_tape_floats(plan, B) floats (training).
+ * Non-finite data (every forward / inverse entry point, block and chain): a row with a NaN or inf in x or c changes no bit of
+ * any other row, and its objective 0.5 |z|^2 - J (the inverse's x row) is non-finite where the reference's is; which lanes,
+ * and whether J alone, are non-finite is not specified. */
 int hint_block_forward(const hint_plan* plan, const float* params, const float* packed,
                        const float* x, const float* c, float* z, float* J, float* tape, int32_t B,
                        void* stream);
@@ -333,7 +336,8 @@ int hint_block_backward_rows(const hint_plan* plan, const float* params, const f
  *   hint_block_ext_coeffs: plan = a one-node plan whose upper half is empty (node k = 0, dc > 0: an ExternalAffineCoupling);
  *     params / packed as for hint_block_forward (packed must be current: hint_block_pack); c [R, dc] condition rows.  Writes
  *     coef_out [R][2][d] = (clamp * 0.636 * atan(s), t) per row (hint.py:56-60, the plan's clamp), what the coupling's forward
- *     applies as x' = x e^a + t, J += sum a.  No argument may be NULL; R = 0 does nothing.
+ *     applies as x' = x e^a + t, J += sum a.  No argument may be NULL; R = 0 does nothing.  A row of c that holds a NaN or an
+ *     inf gets NaN coefficients (as the reference's subnets give it), and changes no other row.
  *   hint_chain_set_block_affine: block i of an INFERENCE chain (set without tape) gets an element-wise affine step behind its
  *     tree: forward x' = x exp(a) + b, J += sum a; hint_chain_inverse undoes it in front of the tree's inverse, J -= sum a.
  *     Row r of the batch reads a = coef + r * row_stride, b = a + d (row_stride = 0: one row of coefficients for every row of
@@ -352,7 +356,12 @@ int hint_chain_set_block_affine(hint_chain* chain, int32_t i, const float* coef,
  * with bias correction for the 1-based `step`.  grad_scale = 1/world_size turns the summed
  * all-reduce into the mean BEFORE the clamp; grad_clamp <= 0 disables clamping.  With
  * zero_grads != 0 the gradient arena is cleared after it has been consumed.  All four buffers
- * must be 16-byte aligned. */
+ * must be 16-byte aligned.
+ * Non-finite gradients take the step those statements take: the clamp is torch.clamp's, so a NaN
+ * gradient stays NaN (p, exp_avg and exp_avg_sq of that element become NaN and stay so) and +-inf
+ * becomes +-grad_clamp; with grad_clamp <= 0 nothing is clamped at all, so an inf gradient makes both
+ * moments inf and p NaN, as torch.optim.Adam alone does.  Every route that takes this step
+ * (hint_adam_step_dev, hint_adam_multi_step, hint_chain_backward_adam, hint_chain_wgrad_adam) shares it. */
 int hint_adam_step(float* params, float* grads, float* exp_avg, float* exp_avg_sq, int64_t n,
                    int32_t step, float lr, float beta1, float beta2, float eps, float weight_decay,
                    float grad_scale, float grad_clamp, int32_t zero_grads, void* stream);

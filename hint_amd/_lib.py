@@ -49,6 +49,14 @@ class CurveDesc(C.Structure):
                 ("mean", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("max_groups", C.c_int32)]
 
 
+class HausdorffDesc(C.Structure):
+    """mirror of `hint_hausdorff_desc` (include/hint_amd.h)"""
+    _fields_ = [("x", C.c_void_p), ("b_points", C.c_void_p), ("n_rows", C.c_int64), ("n_coeffs", C.c_int32),
+                ("n_points", C.c_int32), ("a_points", C.c_void_p), ("a_offsets", C.c_void_p), ("a_params", C.c_void_p),
+                ("n_template", C.c_int64), ("max_h", C.c_void_p), ("avg_h", C.c_void_p), ("chamfer", C.c_void_p),
+                ("points", C.c_void_p), ("max_groups", C.c_int32)]
+
+
 _lib = None
 
 _PROTOS = {
@@ -125,6 +133,9 @@ _PROTOS = {
     "hint_curve_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32]),
     "hint_curve_run": (C.c_int, [C.POINTER(CurveDesc), C.c_void_p]),
     "hint_curve_geometry": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32, C.c_int32]),
+    "hint_hausdorff_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32, C.c_int64]),
+    "hint_hausdorff_run": (C.c_int, [C.POINTER(HausdorffDesc), C.c_void_p]),
+    "hint_hausdorff_geometry": (C.c_int64, [C.c_int64, C.c_int32, C.c_int64, C.c_int32]),
 }
 
 

@@ -1,5 +1,6 @@
 """curve_features / lens_forward_process / target_distances / mean_target_distance: the lens-shape simulator of the reference's
-evaluation loop on the kernel of hint_curve.hip.
+evaluation loop on the kernel of hint_curve.hip; trace_fourier_curves / hausdorff_distances / chamfer_distances / lens_fit_loss:
+its shape-quality side on the kernel of hint_hausdorff.hip (below, after the simulator).
 
     LensShapeModel.forward_process(x, noise=0.05)                      data.py:127-139 (over trace_fourier_curves, data.py:51-57)
     mean_target_distance(model, y_target, x)                           rejection_sampling.py:99-102, called at :204
@@ -20,7 +21,8 @@ import torch
 from . import _lib
 from ._lib import HintAmdError
 
-__all__ = ["curve_features", "lens_forward_process", "target_distances", "mean_target_distance"]
+__all__ = ["curve_features", "lens_forward_process", "target_distances", "mean_target_distance",
+           "trace_fourier_curves", "hausdorff_distances", "chamfer_distances", "lens_fit_loss"]
 
 MAX_COEFFS = 25
 MIN_POINTS, MAX_POINTS = 2, 128
@@ -52,11 +54,11 @@ def _check_shape(shape, who: str) -> int:
     return c // 4
 
 
-def _check_points(v, who: str) -> int:
+def _check_points(v, who: str, most: int = MAX_POINTS) -> int:
     if isinstance(v, bool) or not isinstance(v, int):
         raise HintAmdError(f"{who}: n_points must be an int (got {type(v).__name__})")
-    if v < MIN_POINTS or v > MAX_POINTS:
-        raise HintAmdError(f"{who}: n_points must be {MIN_POINTS}..{MAX_POINTS} (got {v})")
+    if v < MIN_POINTS or v > most:
+        raise HintAmdError(f"{who}: n_points must be {MIN_POINTS}..{most} (got {v})")
     return v
 
 
@@ -173,3 +175,189 @@ def mean_target_distance(x: torch.Tensor, y_target, noise: float = 0.05, *, eps:
     t = _check_target(y_target, x.shape[0], x.device, who)
     noise, eps = _noise_args(x, noise, eps, generator, who)
     return _run(x, n_points, eps, noise, t, want_mean=True)[2]
+
+
+# ---- dense tracing and the distances of a curve to a template (hint_hausdorff.hip) ----
+#     trace_fourier_curves(coeffs, n_points)                             data.py:51-57
+#     max_and_avg_hausdorff_distance(template, dense_curve)              best_shape_fit.py:143-149, per row at run_experiments.py:147-159
+#     lens_points_from_params(prototype, params)                         best_shape_fit.py:195-199
+#     points_to_lens_loss(prototype, points, params, lens_fit_weight)    best_shape_fit.py:203-209
+# One launch of hint_hausdorff_run per call: no [N, P, M] tensor, no host synchronisation, the arithmetic and the order of the sums
+# fixed (include/hint_amd.h).  The shape fits, IoU / DICE and the template generators stay on the host.
+MAX_DENSE_POINTS = 1024
+MAX_TEMPLATE_POINTS = 4096
+
+
+def _check_dense_points(v, who: str) -> int:
+    return _check_points(v, who, MAX_DENSE_POINTS)
+
+
+def _check_dev_tensor(t, name: str, who: str, device=None) -> torch.Tensor:
+    """a floating-point tensor on the GPU (on `device`, if given) that no gradient is asked of -> detached, fp32, contiguous"""
+    if not isinstance(t, torch.Tensor):
+        raise HintAmdError(f"{who}: {name} must be a tensor (got {type(t).__name__})")
+    if not t.is_cuda:
+        raise HintAmdError(f"{who}: {name} is on {t.device}; the distances are a GPU kernel and there is no CPU fallback")
+    if device is not None and t.device != device:
+        raise HintAmdError(f"{who}: {name} is on {t.device} and curve on {device}")
+    if not t.is_floating_point():
+        raise HintAmdError(f"{who}: {name} is {t.dtype}; expected a floating-point tensor")
+    if t.requires_grad and torch.is_grad_enabled():
+        raise HintAmdError(f"{who}: {name} requires grad, and no gradient is implemented; call it under torch.no_grad() or "
+                           "detach the input")
+    t = t.detach()
+    if t.dtype != torch.float32 or not t.is_contiguous():              # (copies only where needed)
+        t = t.to(torch.float32).contiguous()
+    return t
+
+
+def _check_curve_shape(shape, n_points, who: str):
+    """(rows, K or 0, P) of curve [N, 4K] (coefficients, traced at n_points) or [N, P, 2] (points; n_points is not looked at)"""
+    if len(shape) == 2:
+        return shape[0], _check_shape(tuple(shape), who), _check_dense_points(n_points, who)
+    if len(shape) != 3 or shape[2] != 2:
+        raise HintAmdError(f"{who}: curve must be [rows, 4 K] coefficients or [rows, P, 2] points (got shape {tuple(shape)})")
+    n, p = shape[0], shape[1]
+    if n < 1 or n > MAX_ROWS:
+        raise HintAmdError(f"{who}: curve must hold 1..{MAX_ROWS} rows (got shape {tuple(shape)})")
+    if p < MIN_POINTS or p > MAX_DENSE_POINTS:
+        raise HintAmdError(f"{who}: curve must hold {MIN_POINTS}..{MAX_DENSE_POINTS} points a row (got shape {tuple(shape)})")
+    return n, 0, p
+
+
+def _check_template_shape(shape, ragged: bool, who: str) -> int:
+    if len(shape) != 2 or shape[1] != 2:
+        raise HintAmdError(f"{who}: template must be [points, 2] (got shape {tuple(shape)})")
+    if shape[0] < 1:
+        raise HintAmdError(f"{who}: template is empty (shape {tuple(shape)})")
+    if not ragged and shape[0] > MAX_TEMPLATE_POINTS:
+        raise HintAmdError(f"{who}: a shared template must hold 1..{MAX_TEMPLATE_POINTS} points (got {shape[0]}); per-row "
+                           "templates go through offsets")
+    return shape[0]
+
+
+def _check_offsets(offsets, n_rows: int, n_template: int, who: str) -> torch.Tensor:
+    """offsets as int64 [n_rows + 1].  Values on the host (a CPU tensor, an array, a list) are checked here: ascending from 0 to
+    the template's points, 1..4096 points a row.  A tensor that is on the GPU already is not read back - the kernel gives a row
+    with a bad range NaN."""
+    try:
+        o = offsets if isinstance(offsets, torch.Tensor) else torch.as_tensor(offsets)
+    except (TypeError, ValueError, RuntimeError) as e:
+        raise HintAmdError(f"{who}: offsets must be a tensor or an array-like of integers: {e}") from e
+    if o.is_floating_point() or o.is_complex() or o.dtype == torch.bool:
+        raise HintAmdError(f"{who}: offsets is {o.dtype}; expected an integer tensor")
+    if tuple(o.shape) != (n_rows + 1,):
+        raise HintAmdError(f"{who}: offsets must have shape [{n_rows + 1}] (rows + 1; got {tuple(o.shape)})")
+    if o.is_cuda:
+        return o.detach().to(torch.int64).contiguous()
+    o = o.detach().to(torch.int64).contiguous()
+    if int(o[0]) != 0 or int(o[-1]) != n_template:
+        raise HintAmdError(f"{who}: offsets must ascend from 0 to the template's {n_template} points "
+                           f"(got {int(o[0])} .. {int(o[-1])})")
+    d = o[1:] - o[:-1]
+    if int(d.min()) < 1 or int(d.max()) > MAX_TEMPLATE_POINTS:
+        r = int(((d < 1) | (d > MAX_TEMPLATE_POINTS)).nonzero()[0])
+        raise HintAmdError(f"{who}: offsets must ascend by 1..{MAX_TEMPLATE_POINTS} points a row (row {r}: {int(d[r])})")
+    return o
+
+
+def _check_params_shape(shape, n_rows: int, who: str):
+    if tuple(shape) not in ((4,), (1, 4), (n_rows, 4)):
+        raise HintAmdError(f"{who}: params must have shape [4], [1, 4] or [{n_rows}, 4]: x, y, scale, angle "
+                           f"(got {tuple(shape)})")
+
+
+def _distance_args(curve, template, params, offsets, n_points, who: str):
+    if not isinstance(curve, torch.Tensor):
+        raise HintAmdError(f"{who}: curve must be a tensor (got {type(curve).__name__})")
+    if curve.dim() not in (2, 3):
+        raise HintAmdError(f"{who}: curve must be [rows, 4 K] coefficients or [rows, P, 2] points (got shape {tuple(curve.shape)})")
+    curve = _check_dev_tensor(curve, "curve", who)
+    n, k, p = _check_curve_shape(tuple(curve.shape), n_points, who)
+    template = _check_dev_tensor(template, "template", who, curve.device)
+    t_pts = _check_template_shape(tuple(template.shape), offsets is not None, who)
+    if offsets is not None:
+        offsets = _check_offsets(offsets, n, t_pts, who).to(curve.device)
+    if params is not None:
+        params = _check_dev_tensor(params, "params", who, curve.device)
+        _check_params_shape(tuple(params.shape), n, who)
+        params = params.reshape(-1, 4).expand(n, 4).contiguous()
+    return curve, k, p, template, offsets, params
+
+
+def _hd_run(curve: torch.Tensor, k: int, p: int, template: Optional[torch.Tensor], offsets: Optional[torch.Tensor] = None,
+            params: Optional[torch.Tensor] = None, want_h: bool = False, want_chamfer: bool = False, want_points: bool = False,
+            max_groups: int = 0):
+    """one hint_hausdorff_run on checked arguments: (max_h [N], avg_h [N], chamfer [N, 2], points [N, P, 2]), None where not asked.
+    k = 0: curve is [N, P, 2] points.  template None (points alone): the kernel then reads no template, and the descriptor names
+    the first two floats of curve as one"""
+    lib = _lib.load()
+    n, dev = curve.shape[0], curve.device
+    with torch.cuda.device(dev):
+        new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)     # noqa: E731
+        max_h, avg_h = (new(n), new(n)) if want_h else (None, None)
+        chamfer = new(n, 2) if want_chamfer else None
+        points = new(n, p, 2) if want_points else None
+        desc = _lib.HausdorffDesc()
+        desc.x, desc.b_points = (curve.data_ptr(), None) if k else (None, curve.data_ptr())
+        desc.n_rows, desc.n_coeffs, desc.n_points = n, k, p
+        desc.a_points = template.data_ptr() if template is not None else curve.data_ptr()
+        desc.n_template = template.shape[0] if template is not None else 1
+        desc.a_offsets = offsets.data_ptr() if offsets is not None else None
+        desc.a_params = params.data_ptr() if params is not None else None
+        desc.max_h, desc.avg_h = (max_h.data_ptr(), avg_h.data_ptr()) if want_h else (None, None)
+        desc.chamfer = chamfer.data_ptr() if want_chamfer else None
+        desc.points = points.data_ptr() if want_points else None
+        desc.max_groups = max_groups
+        st = lib.hint_hausdorff_run(desc, torch.cuda.current_stream(dev).cuda_stream)
+    _lib.check(st, "hint_hausdorff_run")
+    return max_h, avg_h, chamfer, points
+
+
+def trace_fourier_curves(x: torch.Tensor, n_points: int = 100) -> torch.Tensor:
+    """the reference's data_model.trace_fourier_curves(unflatten_coeffs(x), n_points) on flat x [N, 4K]: the curve's points
+    [N, n_points, 2] fp32 on x's device, 2 <= n_points <= 1024; the last point repeats the first bit for bit.  Up to 128 points
+    these are the points curve_features measures"""
+    who = "trace_fourier_curves"
+    if isinstance(x, torch.Tensor) and x.requires_grad and torch.is_grad_enabled():
+        raise HintAmdError(f"{who}: x requires grad, and no gradient is implemented; call it under torch.no_grad() or detach "
+                           "the input")
+    x = _check_x(x, who)
+    return _hd_run(x, x.shape[1] // 4, _check_dense_points(n_points, who), None, want_points=True)[3]
+
+
+def hausdorff_distances(curve: torch.Tensor, template: torch.Tensor, params: Optional[torch.Tensor] = None, *, offsets=None,
+                        n_points: int = 1000):
+    """the reference's max_and_avg_hausdorff_distance(template, dense curve) for every row: (max_h [N], avg_h [N]) fp32.
+
+    curve     [N, 4K] coefficients, traced at n_points here, or [N, P, 2] points (n_points is then ignored)
+    template  [M, 2], M <= 4096, shared by all rows; or, with offsets (int64 [N + 1], ascending from 0 to T, on the host or the
+              device), [T, 2] of which row n owns template[offsets[n]:offsets[n + 1]], 1..4096 points
+    params    None, or [N, 4] (or [4]) = x, y, scale, angle: the template is first moved as lens_points_from_params does"""
+    who = "hausdorff_distances"
+    curve, k, p, template, offsets, params = _distance_args(curve, template, params, offsets, n_points, who)
+    return _hd_run(curve, k, p, template, offsets, params, want_h=True)[:2]
+
+
+def chamfer_distances(curve: torch.Tensor, template: torch.Tensor, params: Optional[torch.Tensor] = None, *, offsets=None,
+                      n_points: int = 1000) -> torch.Tensor:
+    """[N, 2] fp32: per row (the mean over the curve's points of the squared distance to the nearest template point, the mean
+    over the template's points of the squared distance to the nearest curve point).  Arguments as hausdorff_distances (n_points
+    is ignored when curve holds points)"""
+    who = "chamfer_distances"
+    curve, k, p, template, offsets, params = _distance_args(curve, template, params, offsets, n_points, who)
+    return _hd_run(curve, k, p, template, offsets, params, want_chamfer=True)[2]
+
+
+def lens_fit_loss(curve: torch.Tensor, prototype: torch.Tensor, params: torch.Tensor, lens_fit_weight: float = 1.0) -> torch.Tensor:
+    """the reference's points_to_lens_loss(prototype, points, params, lens_fit_weight) for every row, [N] fp32:
+    chamfer[:, 0] + lens_fit_weight * chamfer[:, 1] of chamfer_distances(curve, prototype, params).  curve as in
+    hausdorff_distances; coefficients are traced at 100 points, as the fit's points are"""
+    who = "lens_fit_loss"
+    if isinstance(lens_fit_weight, bool) or not isinstance(lens_fit_weight, (int, float)) or lens_fit_weight != lens_fit_weight:
+        raise HintAmdError(f"{who}: lens_fit_weight must be a number (got {lens_fit_weight!r})")
+    if params is None:
+        raise HintAmdError(f"{who}: params must be a tensor (got None)")
+    curve, k, p, prototype, _, params = _distance_args(curve, prototype, params, None, 100, who)
+    ch = _hd_run(curve, k, p, prototype, None, params, want_chamfer=True)[2]
+    return ch[:, 0] + float(lens_fit_weight) * ch[:, 1]

@@ -507,6 +507,72 @@ size_t hint_curve_workspace_bytes(int64_t n_rows, int32_t n_coeffs, int32_t n_po
 int hint_curve_run(const hint_curve_desc* desc, void* stream);
 int64_t hint_curve_geometry(int64_t n_rows, int32_t n_coeffs, int32_t n_points, int32_t field);
 
+/* Dense curve tracing and the distances of a curve to a template: the shape-quality columns of the reference's evaluation
+ * (run_experiments.py:147-159 and eval_shapes.py:82-95 trace every sample with data.py:51-57 trace_fourier_curves at 100 and at 1000
+ * points and call best_shape_fit.py:143-149 max_and_avg_hausdorff_distance per row, a [P, M, 2] numpy tensor each; the template is
+ * best_shape_fit.py:195-199 lens_points_from_params, reached through :275-277, or the densified plus outline of :153-156;
+ * best_shape_fit.py:203-209 points_to_lens_loss is the same two-sided minimum over squared distances).  Per row n of n_rows two
+ * point sets are compared.
+ *   B, the curve, P = n_points points, from exactly one source:
+ *     traced  x [n_rows, 4 K] as hint_curve_desc's x: p[t, axis] by hint_curve_run's own rule - fp32 fused multiply-adds onto the
+ *             sum over k ascending (real term, then imaginary term), each twiddle the true value rounded to fp32 after the exact
+ *             reduction r = (|m| t) mod (P - 1) in integers (sincospi in double), so point P - 1 repeats point 0 bit for bit.  For
+ *             P <= 128 the points are the bits hint_curve_run computes internally.
+ *     given   b_points [n_rows, P, 2]: curves the caller traced already.
+ *   A, the template, M_n points, 1 <= M_n <= 4096, taken from a_points [n_template, 2]: with a_offsets (int64 [n_rows + 1],
+ *     ascending from 0 to n_template) row n owns a_points[a_offsets[n] : a_offsets[n + 1]] (ragged); without, every row shares all
+ *     n_template points.  a_params [n_rows, 4] = (x, y, scale, angle), if given, applies lens_points_from_params - prototype times
+ *     [[cos, sin], [-sin, cos]] (row vectors), times scale, plus (x, y) - in this order: cs, sn = sincos in double of the fp32 angle,
+ *     rounded to fp32; qx = fma(-a.y, sn, a.x cs), qy = fma(a.y, cs, a.x sn); A = (fma(qx, scale, x), fma(qy, scale, y)).
+ *     Without a_params the template is used as given.
+ *   D(i, j) = fma(dy, dy, dx dx) of A_i - B_j in fp32;  mA_i = min_j D(i, j), mB_j = min_i D(i, j): exact functions of the points,
+ *     whatever the order the minima are taken in.
+ *   max_h [n_rows]      sqrt, correctly rounded, of the largest of all M_n + P minima
+ *   avg_h [n_rows]      ((sum of the fp32 values sqrt(mA_i)) + (sum of sqrt(mB_j))) / (M_n + P), the sums and the division in
+ *                       double, the result rounded to fp32
+ *   chamfer [n_rows, 2] (sum_j mB_j / P, sum_i mA_i / M_n) the same way; points_to_lens_loss(prototype, points, params, w) is
+ *                       chamfer[:, 0] + w chamfer[:, 1]
+ *   points [n_rows, P, 2]  the traced curve (traced source only).  When points is the only output, neither the template nor
+ *                       a_offsets nor a_params is read (a_points must still be non-NULL).
+ *   The association of each of the four sums is fixed: lane l of wavefront v = thread 64 v + l first adds the values of its own
+ *   points i = 256 c + 64 v + l (c ascending) to 0; the 64 lanes of a wavefront are added by a butterfly (lane distances 32, 16,
+ *   8, 4, 2, 1); the four wavefronts are added in order.  No float atomics, no counters.
+ * A row's outputs do not depend on n_rows, on where the row stands, on max_groups or on what the outputs held; two runs agree bit
+ * for bit.  Rows with non-finite inputs give unspecified values, fault nothing and disturb no other row.  A ragged row whose range
+ * is not 1..4096 points inside a_points (the offsets are on the device, so the host cannot check them) gets NaN in max_h, avg_h
+ * and chamfer, and nothing outside a_points is read; its points, which do not depend on the template, are traced as usual.
+ *   run              stream-ordered on the current device: one launch, no host synchronisation, no allocation (capturable).  Each
+ *                    output may be NULL, not all four.  max_groups: 0 = the default grid, otherwise the workgroups at most.
+ *                    Rejects, before any device call and naming the field: a null a_points; both or neither of x and b_points;
+ *                    points with b_points; no output; n_rows outside 1..2^30; with x, n_coeffs even or outside 1..25 (ignored
+ *                    with b_points); n_points outside 2..1024; n_template < 1; a shared template of more than 4096 points, ragged
+ *                    ones of more than 4096 n_rows in all; max_groups < 0; a pointer that is not 4-byte (a_offsets: 8-byte) aligned.
+ *   workspace_bytes  0: no workspace is needed, so the descriptor names none.  For sizes run would reject (n_coeffs = 0 stands
+ *                    for the given source; max_template_points is the largest M_n) hint_last_error() says why, otherwise it is
+ *                    left empty.
+ *   geometry         host only, for the default grid: field 0 the workgroups, 1 the rows a workgroup has in flight (one), 2 the
+ *                    template points of an LDS tile, 3 the grid cap, 4 the tiles of max_template_points.  Workgroup w of G takes
+ *                    rows w, w + G, ...  -1 on an error.
+ * None of these has a caller's device buffer among its parameters: the buffers are named by the descriptor. */
+typedef struct hint_hausdorff_desc {
+    const float* x;                        /* NULL, or [n_rows, 4 n_coeffs] row-major: the traced source */
+    const float* b_points;                 /* NULL, or device float[n_rows, n_points, 2]: the given source */
+    int64_t n_rows;
+    int32_t n_coeffs, n_points;            /* K odd 1..25 (traced source), P 2..1024 */
+    const float* a_points;                 /* device float[n_template, 2] */
+    const int64_t* a_offsets;              /* NULL (shared template), or device int64[n_rows + 1], 8-byte aligned */
+    const float* a_params;                 /* NULL, or device float[n_rows, 4]: x, y, scale, angle */
+    int64_t n_template;                    /* T: points in a_points */
+    float* max_h;                          /* NULL, or device float[n_rows] */
+    float* avg_h;                          /* NULL, or device float[n_rows] */
+    float* chamfer;                        /* NULL, or device float[n_rows, 2] */
+    float* points;                         /* NULL, or device float[n_rows, n_points, 2] */
+    int32_t max_groups;
+} hint_hausdorff_desc;
+size_t hint_hausdorff_workspace_bytes(int64_t n_rows, int32_t n_coeffs, int32_t n_points, int64_t max_template_points);
+int hint_hausdorff_run(const hint_hausdorff_desc* desc, void* stream);
+int64_t hint_hausdorff_geometry(int64_t n_rows, int32_t n_points, int64_t max_template_points, int32_t field);
+
 int hint_abi_version(void);
 const char* hint_last_error(void);
 /* what the library binary was built with and runs with: "libhint_amd abi N, gfx950, HIP x.y.z, clang ..., src <12 hex digits: hash

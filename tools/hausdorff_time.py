@@ -1,0 +1,153 @@
+#!/usr/bin/env python3
+"""Time hint_amd.hausdorff_distances on coefficients (one launch of hint_hausdorff_run) against the formulation a user would
+otherwise write on the same device,
+
+    points = einsum(re, cos) - einsum(im, sin);  lens = (prototype @ R) * scale + (x, y);  d = torch.cdist(lens, points)
+    minima = cat(d.min(2), d.min(1));  max_h = minima.max(1);  avg_h = minima.mean(1)
+
+chunked over rows so that the [chunk, M, P] matrix stays under 1 GiB, alternating the two in one process.
+
+    python tools/hausdorff_time.py [--out profiles/hausdorff_time.json] [--commit <hash>]
+
+Shapes: K = 5, P = 1000, M = 1000 at N = 1000 (the evaluation loop's call) and 2^16 rows.  Every size runs in a child process of
+its own under a time limit, and a size that fails ends the run: nothing more is started on the device after it.  Both routes are
+warmed up, every repetition is bracketed by HIP events on the current stream, and the medians, quartiles and extremes are
+printed and written, with the library's build string and the commit.
+"""
+import argparse
+import json
+import math
+import os
+import statistics
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SIZES = ((1000, 20), (1 << 16, 5))          # (rows, repetitions)
+K, P, M = 5, 1000, 1000
+CHUNK = 256             # rows of the torch formulation's [chunk, M, P] matrix: 1.02 GB in fp32, just under 1 GiB
+LIMIT_S = 300           # per size
+
+
+def stats(us):
+    q = statistics.quantiles(us, n=4) if len(us) > 1 else [us[0]] * 3
+    return {"median_us": statistics.median(us), "q1_us": q[0], "q3_us": q[2], "min_us": min(us), "max_us": max(us), "reps": len(us)}
+
+
+def one_size(n, reps, warmup):
+    import torch
+    sys.path.insert(0, ROOT)
+    import hint_amd
+    from hint_amd import _lib
+
+    assert torch.cuda.is_available(), "hausdorff_time.py needs a GPU"
+    dev = torch.device("cuda:0")
+    g = torch.Generator(device=dev).manual_seed(n % 1000003)
+    w = torch.tensor([.1, .3, 1, .6, .2], device=dev).repeat(4)
+    x = torch.randn(n, 4 * K, generator=g, device=dev) * w
+    # a two-arc lens of M points, and params around the identity
+    th = torch.linspace(0.0, 2 * math.pi, M + 1, device=dev)[:M]
+    proto = torch.stack([torch.cos(th), 0.4 * torch.sin(th) * torch.sin(th).abs()], 1).contiguous()
+    params = torch.cat([0.3 * torch.randn(n, 2, generator=g, device=dev), 0.5 + 2 * torch.rand(n, 1, generator=g, device=dev),
+                        math.pi * (2 * torch.rand(n, 1, generator=g, device=dev) - 1)], 1).contiguous()
+    m = torch.arange(K, device=dev) - K // 2
+    ang = 2 * math.pi * (m[None, :] * torch.arange(P, device=dev)[:, None]).double() / (P - 1)
+    cos, sin = ang.cos().float(), ang.sin().float()
+
+    def torch_route():
+        max_h, avg_h = torch.empty(n, device=dev), torch.empty(n, device=dev)
+        for a in range(0, n, CHUNK):
+            xc, pc = x[a:a + CHUNK], params[a:a + CHUNK]
+            c = xc.shape[0]
+            re, im = xc[:, :2 * K].reshape(c, 2, K), xc[:, 2 * K:].reshape(c, 2, K)
+            pts = torch.einsum("nak,tk->nta", re, cos) - torch.einsum("nak,tk->nta", im, sin)
+            cs, sn = pc[:, 3].cos(), pc[:, 3].sin()
+            R = torch.stack([torch.stack([cs, sn], 1), torch.stack([-sn, cs], 1)], 1)             # [c, 2, 2]
+            lens = torch.matmul(proto[None], R) * pc[:, 2, None, None] + pc[:, None, :2]
+            d = torch.cdist(lens, pts)                                                            # [c, M, P]
+            minima = torch.cat([d.min(2).values, d.min(1).values], 1)
+            max_h[a:a + c], avg_h[a:a + c] = minima.max(1).values, minima.mean(1)
+        return max_h, avg_h
+
+    routes = {"fused": lambda: hint_amd.hausdorff_distances(x, proto, params, n_points=P), "torch": torch_route}
+
+    def timed(fn):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        out = fn()
+        b.record()
+        b.synchronize()
+        return a.elapsed_time(b) * 1e3, out          # microseconds
+
+    for _ in range(warmup):
+        for fn in routes.values():
+            fn()
+    torch.cuda.synchronize()
+    us = {name: [] for name in routes}
+    outs = {}
+    for _ in range(reps):                            # alternate: clocks and caches drift for both routes alike
+        for name, fn in routes.items():
+            dt, out = timed(fn)
+            us[name].append(dt)
+            outs[name] = out
+    lib = _lib.load()
+    row = {name: stats(v) for name, v in us.items()}
+    row["max_abs_difference_max_h"] = float((outs["fused"][0] - outs["torch"][0]).abs().max())
+    row["max_abs_difference_avg_h"] = float((outs["fused"][1] - outs["torch"][1]).abs().max())
+    row["workgroups"] = int(lib.hint_hausdorff_geometry(n, P, M, 0))
+    row["fused_pairs_per_second"] = 2.0 * n * P * M / (row["fused"]["median_us"] * 1e-6)      # each pair is met in both passes
+    row["torch_over_fused"] = row["torch"]["median_us"] / row["fused"]["median_us"]
+    row["torch_peak_bytes"] = int(torch.cuda.max_memory_allocated())
+    row["device"] = torch.cuda.get_device_name(0)
+    row["build"] = lib.hint_build_info().decode()
+    return row
+
+
+def commit_of_tree():
+    try:
+        return subprocess.run(["git", "-C", ROOT, "rev-parse", "HEAD"], capture_output=True, text=True, check=True).stdout.strip()
+    except (OSError, subprocess.CalledProcessError):
+        return "unknown"
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "hausdorff_time.json"))
+    ap.add_argument("--commit", default=None, help="the commit the tree was built from (default: git rev-parse HEAD)")
+    ap.add_argument("--one", type=int, default=0, help="(internal) time this N and print its JSON row")
+    ap.add_argument("--reps", type=int, default=0, help="(internal) repetitions of --one")
+    args = ap.parse_args()
+    if args.one:
+        print("ROW " + json.dumps(one_size(args.one, args.reps, args.warmup)))
+        return 0
+    res = {"n_coeffs": K, "n_points": P, "template_points": M, "torch_chunk_rows": CHUNK, "commit": args.commit or commit_of_tree(), "shapes": {}}
+    for n, reps in SIZES:
+        try:
+            p = subprocess.run([sys.executable, os.path.abspath(__file__), "--one", str(n), "--reps", str(reps), "--warmup",
+                                str(args.warmup)], capture_output=True, text=True, timeout=LIMIT_S)
+        except subprocess.TimeoutExpired:
+            print(f"N={n}: no result within {LIMIT_S} s; stopping")
+            return 1
+        rows = [ln[4:] for ln in p.stdout.splitlines() if ln.startswith("ROW ")]
+        if p.returncode != 0 or not rows:
+            print(f"N={n}: exit status {p.returncode}; stopping\n{p.stdout[-2000:]}\n{p.stderr[-2000:]}")
+            return 1
+        row = json.loads(rows[-1])
+        res["device"], res["build"] = row.pop("device"), row.pop("build")
+        res["shapes"][str(n)] = row
+        for name in ("fused", "torch"):
+            s = row[name]
+            print(f"N={n} {name:6s} median {s['median_us']:12.1f} us  quartiles {s['q1_us']:.1f} .. {s['q3_us']:.1f}  "
+                  f"range {s['min_us']:.1f} .. {s['max_us']:.1f}  ({s['reps']} repetitions)")
+        print(f"N={n} torch / fused = {row['torch_over_fused']:.2f}; fused {row['fused_pairs_per_second'] / 1e12:.3f} T pair visits/s on "
+              f"{row['workgroups']} workgroups; max_h differs from torch's by at most {row['max_abs_difference_max_h']:.3g}, avg_h by "
+              f"{row['max_abs_difference_avg_h']:.3g}")
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        json.dump(res, open(args.out, "w"), indent=1)
+    print("wrote", args.out)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

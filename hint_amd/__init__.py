@@ -15,5 +15,7 @@ from .metrics import MultiMMD, multi_mmd  # noqa: F401,E402
 from .abc import nearest_rows, quantile_abc  # noqa: F401,E402
 from .curves import curve_features, lens_forward_process, mean_target_distance, target_distances  # noqa: F401,E402
 from .curves import chamfer_distances, hausdorff_distances, lens_fit_loss, trace_fourier_curves  # noqa: F401,E402
+from .curves import (plus_fit_loss, plus_fit_terms, plus_hausdorff_distances, plus_outline_counts,  # noqa: F401,E402
+                     plus_segments)
 
 __version__ = "0.1.0"

@@ -57,6 +57,14 @@ class HausdorffDesc(C.Structure):
                 ("points", C.c_void_p), ("max_groups", C.c_int32)]
 
 
+class PlusDesc(C.Structure):
+    """mirror of `hint_plus_desc` (include/hint_amd.h)"""
+    _fields_ = [("x", C.c_void_p), ("b_points", C.c_void_p), ("n_rows", C.c_int64), ("n_coeffs", C.c_int32),
+                ("n_points", C.c_int32), ("params", C.c_void_p), ("max_dist", C.c_float), ("max_groups", C.c_int32),
+                ("segments", C.c_void_p), ("keep", C.c_void_p), ("counts", C.c_void_p), ("loss", C.c_void_p),
+                ("max_h", C.c_void_p), ("avg_h", C.c_void_p)]
+
+
 _lib = None
 
 _PROTOS = {
@@ -136,6 +144,9 @@ _PROTOS = {
     "hint_hausdorff_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32, C.c_int64]),
     "hint_hausdorff_run": (C.c_int, [C.POINTER(HausdorffDesc), C.c_void_p]),
     "hint_hausdorff_geometry": (C.c_int64, [C.c_int64, C.c_int32, C.c_int64, C.c_int32]),
+    "hint_plus_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32]),
+    "hint_plus_run": (C.c_int, [C.POINTER(PlusDesc), C.c_void_p]),
+    "hint_plus_geometry": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
 }
 
 

@@ -1,6 +1,7 @@
 """curve_features / lens_forward_process / target_distances / mean_target_distance: the lens-shape simulator of the reference's
 evaluation loop on the kernel of hint_curve.hip; trace_fourier_curves / hausdorff_distances / chamfer_distances / lens_fit_loss:
-its shape-quality side on the kernel of hint_hausdorff.hip (below, after the simulator).
+its shape-quality side on the kernel of hint_hausdorff.hip (below, after the simulator); plus_segments / plus_outline_counts /
+plus_fit_terms / plus_fit_loss / plus_hausdorff_distances: the plus shape's side on the kernel of hint_plus.hip (at the end).
 
     LensShapeModel.forward_process(x, noise=0.05)                      data.py:127-139 (over trace_fourier_curves, data.py:51-57)
     mean_target_distance(model, y_target, x)                           rejection_sampling.py:99-102, called at :204
@@ -22,7 +23,8 @@ from . import _lib
 from ._lib import HintAmdError
 
 __all__ = ["curve_features", "lens_forward_process", "target_distances", "mean_target_distance",
-           "trace_fourier_curves", "hausdorff_distances", "chamfer_distances", "lens_fit_loss"]
+           "trace_fourier_curves", "hausdorff_distances", "chamfer_distances", "lens_fit_loss",
+           "plus_segments", "plus_outline_counts", "plus_fit_terms", "plus_fit_loss", "plus_hausdorff_distances"]
 
 MAX_COEFFS = 25
 MIN_POINTS, MAX_POINTS = 2, 128
@@ -361,3 +363,130 @@ def lens_fit_loss(curve: torch.Tensor, prototype: torch.Tensor, params: torch.Te
     curve, k, p, prototype, _, params = _distance_args(curve, prototype, params, None, 100, who)
     ch = _hd_run(curve, k, p, prototype, None, params, want_chamfer=True)[2]
     return ch[:, 0] + float(lens_fit_weight) * ch[:, 1]
+
+
+# ---- the plus shape: outline, fit loss and distances to the densified outline (hint_plus.hip) ----
+#     plus_segments_from_params(params)                                  best_shape_fit.py:26-50
+#     points_to_plus_loss(points, params, corner_weight)                 best_shape_fit.py:54-65 (over :15-22)
+#     max_and_avg_hausdorff_distance_plus_shape(params, points)          best_shape_fit.py:153-156, per row at eval_shapes.py:82-95
+#     PlusShapeModel.densify_polyline(coords, max_dist)                  data.py:176-186
+# One launch of hint_plus_run per call.  The outline's points are generated inside the kernel: no template is built or uploaded
+# and there is no per-row host work.  The fits themselves (fit_plus_shape_to_points) and IoU / DICE stay on the host.
+PLUS_PARAMS = 9
+MAX_OUTLINE_POINTS = 4096
+
+
+def _check_max_dist(v, who: str) -> float:
+    if isinstance(v, bool) or not isinstance(v, (int, float)):
+        raise HintAmdError(f"{who}: max_dist must be a number (got {type(v).__name__})")
+    v = float(v)
+    if not (v > 0.0) or v == float("inf"):
+        raise HintAmdError(f"{who}: max_dist must be finite and > 0 (got {v})")
+    return v
+
+
+def _check_plus_params_shape(shape, n_rows: Optional[int], who: str) -> None:
+    """[9], [1, 9] or [n_rows, 9]; n_rows None: the params alone decide the rows ([9] or [N, 9], N >= 1)"""
+    shape = tuple(shape)
+    if n_rows is None:
+        if shape == (PLUS_PARAMS,) or (len(shape) == 2 and shape[1] == PLUS_PARAMS and 1 <= shape[0] <= MAX_ROWS):
+            return
+        raise HintAmdError(f"{who}: params must have shape [9] or [rows, 9]: xlength, ylength, xwidth, ywidth, xshift, yshift, "
+                           f"xoffset, yoffset, angle (got {shape})")
+    if shape not in ((PLUS_PARAMS,), (1, PLUS_PARAMS), (n_rows, PLUS_PARAMS)):
+        raise HintAmdError(f"{who}: params must have shape [9], [1, 9] or [{n_rows}, 9]: xlength, ylength, xwidth, ywidth, "
+                           f"xshift, yshift, xoffset, yoffset, angle (got {shape})")
+
+
+def _plus_params(params, n_rows: Optional[int], who: str, device=None) -> torch.Tensor:
+    params = _check_dev_tensor(params, "params", who, device)
+    _check_plus_params_shape(tuple(params.shape), n_rows, who)
+    params = params.reshape(-1, PLUS_PARAMS)
+    if n_rows is not None and params.shape[0] != n_rows:
+        params = params.expand(n_rows, PLUS_PARAMS)
+    return params.contiguous()
+
+
+def _plus_args(curve, params, n_points, who: str):
+    if not isinstance(curve, torch.Tensor):
+        raise HintAmdError(f"{who}: curve must be a tensor (got {type(curve).__name__})")
+    if curve.dim() not in (2, 3):
+        raise HintAmdError(f"{who}: curve must be [rows, 4 K] coefficients or [rows, P, 2] points (got shape {tuple(curve.shape)})")
+    curve = _check_dev_tensor(curve, "curve", who)
+    n, k, p = _check_curve_shape(tuple(curve.shape), n_points, who)
+    return curve, k, p, _plus_params(params, n, who, curve.device)
+
+
+def _plus_run(params: torch.Tensor, curve: Optional[torch.Tensor] = None, k: int = 0, p: int = 0, max_dist: float = 0.02,
+              want=("segments", "keep", "counts", "loss", "max_h", "avg_h"), max_groups: int = 0, out=None):
+    """one hint_plus_run on checked arguments: a dict of the outputs named in `want` (segments [N, 12, 2, 2], keep [N] int32,
+    counts [N, 12] int32, loss [N, 2], max_h [N], avg_h [N]).  k = 0: curve is [N, P, 2] points; curve None: no curve output.
+    out: tensors to write into instead of new ones (the tests' guarded buffers)"""
+    lib = _lib.load()
+    n, dev = params.shape[0], params.device
+    shapes = dict(segments=((n, 12, 2, 2), torch.float32), keep=((n,), torch.int32), counts=((n, 12), torch.int32),
+                  loss=((n, 2), torch.float32), max_h=((n,), torch.float32), avg_h=((n,), torch.float32))
+    with torch.cuda.device(dev):
+        res = {}
+        for name in want:
+            shape, dtype = shapes[name]
+            res[name] = out[name] if out is not None and name in out else torch.empty(shape, dtype=dtype, device=dev)
+        desc = _lib.PlusDesc()
+        if curve is not None:
+            desc.x, desc.b_points = (curve.data_ptr(), None) if k else (None, curve.data_ptr())
+        desc.n_rows, desc.n_coeffs, desc.n_points = n, k, p
+        desc.params, desc.max_dist, desc.max_groups = params.data_ptr(), max_dist, max_groups
+        for name in shapes:
+            setattr(desc, name, res[name].data_ptr() if name in res else None)
+        st = lib.hint_plus_run(desc, torch.cuda.current_stream(dev).cuda_stream)
+    _lib.check(st, "hint_plus_run")
+    return res
+
+
+def plus_segments(params: torch.Tensor):
+    """the reference's plus_segments_from_params(params) for every row of params [N, 9] (or [9]) = xlength, ylength, xwidth,
+    ywidth, xshift, yshift, xoffset, yoffset, angle: (segments [N, 12, 2, 2] fp32 - all twelve, placed - and keep [N] int32, whose
+    bit s says that the reference keeps segment s; it drops those of zero length, which only a zero width gives)"""
+    who = "plus_segments"
+    res = _plus_run(_plus_params(params, None, who), want=("segments", "keep"))
+    return res["segments"], res["keep"]
+
+
+def plus_outline_counts(params: torch.Tensor, max_dist: float = 0.02) -> torch.Tensor:
+    """[N, 12] int32: the points densify_polyline(outline, max_dist) puts on each edge - 0 for a dropped segment; -1 in every
+    column of a row whose outline cannot be served (more than 4096 points, parameters that are not finite)"""
+    who = "plus_outline_counts"
+    max_dist = _check_max_dist(max_dist, who)
+    return _plus_run(_plus_params(params, None, who), max_dist=max_dist, want=("counts",))["counts"]
+
+
+def plus_fit_terms(curve: torch.Tensor, params: torch.Tensor, *, n_points: int = 100) -> torch.Tensor:
+    """[N, 2] fp32: the two terms of the reference's points_to_plus_loss per row - the mean over the curve's points of the squared
+    distance to the nearest outline segment, and the mean over the outline's corners of the squared distance to the nearest curve
+    point.  curve is [N, 4K] coefficients, traced at n_points here, or [N, P, 2] points (n_points is then ignored); params [N, 9],
+    [1, 9] or [9]"""
+    who = "plus_fit_terms"
+    curve, k, p, params = _plus_args(curve, params, n_points, who)
+    return _plus_run(params, curve, k, p, want=("loss",))["loss"]
+
+
+def plus_fit_loss(curve: torch.Tensor, params: torch.Tensor, corner_weight: float = 1.0) -> torch.Tensor:
+    """the reference's points_to_plus_loss(points, params, corner_weight) for every row, [N] fp32: terms[:, 0] + corner_weight *
+    terms[:, 1] of plus_fit_terms.  Coefficients are traced at 100 points, as the fit's points are"""
+    who = "plus_fit_loss"
+    if isinstance(corner_weight, bool) or not isinstance(corner_weight, (int, float)) or corner_weight != corner_weight:
+        raise HintAmdError(f"{who}: corner_weight must be a number (got {corner_weight!r})")
+    curve, k, p, params = _plus_args(curve, params, 100, who)
+    terms = _plus_run(params, curve, k, p, want=("loss",))["loss"]
+    return terms[:, 0] + float(corner_weight) * terms[:, 1]
+
+
+def plus_hausdorff_distances(curve: torch.Tensor, params: torch.Tensor, *, max_dist: float = 0.02, n_points: int = 1000):
+    """the reference's max_and_avg_hausdorff_distance_plus_shape(params, dense curve) for every row: (max_h [N], avg_h [N]) fp32
+    between the curve and the outline densified at max_dist.  curve and params as in plus_fit_terms.  A row whose outline would
+    hold more than 4096 points, or whose parameters are not finite, gets NaN in both"""
+    who = "plus_hausdorff_distances"
+    max_dist = _check_max_dist(max_dist, who)
+    curve, k, p, params = _plus_args(curve, params, n_points, who)
+    res = _plus_run(params, curve, k, p, max_dist, want=("max_h", "avg_h"))
+    return res["max_h"], res["avg_h"]

@@ -573,6 +573,80 @@ size_t hint_hausdorff_workspace_bytes(int64_t n_rows, int32_t n_coeffs, int32_t 
 int hint_hausdorff_run(const hint_hausdorff_desc* desc, void* stream);
 int64_t hint_hausdorff_geometry(int64_t n_rows, int32_t n_points, int64_t max_template_points, int32_t field);
 
+/* The plus shape's fit loss and its Hausdorff distances to a curve: the plus columns of the reference's shape evaluation
+ * (eval_shapes.py:82-95 calls, per row, best_shape_fit.py:54-65 points_to_plus_loss - over best_shape_fit.py:26-50
+ * plus_segments_from_params and best_shape_fit.py:15-22 squared_dists_points_to_line_segment - and best_shape_fit.py:153-156
+ * max_and_avg_hausdorff_distance_plus_shape, whose template is data.py:176-186 densify_polyline of the outline).  Per row n the 9
+ * fitted parameters params[n] = (xlength, ylength, xwidth, ywidth, xshift, yshift, xoffset, yoffset, angle) give the 12 outline
+ * segments, the two terms of the fit loss and the distances of the curve B (as hint_hausdorff_desc's: traced from x [n_rows, 4 K]
+ * by the same rule and the same bits, or given as b_points [n_rows, P, 2]) to the densified outline A, whose points are generated
+ * inside the kernel and exist nowhere in memory.  All arithmetic is fp32, each operation rounded once, unless said otherwise.
+ *   1. local vertices.  h(v) = 0.5 v (exact);  xleft = xshift - h(xlength), xright = xshift + h(xlength), xtop = h(xwidth),
+ *      xbottom = -xtop, yright = h(ywidth), yleft = -yright, ybottom = yshift - h(ylength), ytop = yshift + h(ylength); then, with
+ *      c = 0.01f and each clamp taken from the unclamped partner, xleft = min(xleft, yleft - c), xright = max(xright, yright + c),
+ *      ytop = max(ytop, xtop + c), ybottom = min(ybottom, xbottom - c).  V0..V11 = (xleft, xtop), (yleft, xtop), (yleft, ytop),
+ *      (yright, ytop), (yright, xtop), (xright, xtop), (xright, xbottom), (yright, xbottom), (yright, ybottom), (yleft, ybottom),
+ *      (yleft, xbottom), (xleft, xbottom); segment s is (V_s, V_(s+1) mod 12).
+ *   2. keep.  Segment s is kept iff its two local vertices differ (an exact comparison: local segments are axis-parallel; the
+ *      reference filters before it rotates).  Bit s of keep[n] says so.  Only a zero width drops segments.
+ *   3. placement, the lens rule with scale 1: cs, sn = sincos in double of the fp32 angle, rounded to fp32; qx = fma(-v.y, sn,
+ *      v.x cs), qy = fma(v.y, cs, v.x sn); W = (qx + xoffset, qy + yoffset).  segments[n, s] = (W_s, W_(s+1)), kept or not.
+ *   4. segment term.  For a kept segment (a, b) = (W_s, W_(s+1)) and a curve point p: n = b - a; L = sqrt(fma(n.y, n.y, n.x n.x));
+ *      n = n / L; ap = a - p; len = max(0, min(L, -fma(ap.y, n.y, ap.x n.x))); v = (fma(len, n.x, ap.x), fma(len, n.y, ap.y));
+ *      d2 = fma(v.y, v.y, v.x v.x).  loss[n, 0] = the mean over the P points of min over the kept s of d2.
+ *   5. corner term.  loss[n, 1] = the mean over the kept segments' first vertices W_s of min_j fma(dy, dy, dx dx), (dx, dy) =
+ *      W_s - B_j: the squared distance itself (the reference roots and squares again).  points_to_plus_loss(points, params, w) is
+ *      loss[:, 0] + w loss[:, 1].
+ *   6. densified outline.  The polygon is the kept segments' first vertices, in order, closed; the edge of kept segment s runs from
+ *      E = W_s to S = the next kept first vertex, which is W_(s+1) bit for bit (a dropped segment's two vertices are the same
+ *      bits).  count = max(1, rint(max(|S.x - E.x|, |S.y - E.y|) / max_dist)) in double from the fp32 vertices and the fp32
+ *      max_dist, rint = round half to even.  Point i of count: E when count = 1; otherwise t = float(i) / float(count - 1), the
+ *      correctly rounded quotient, and A = fma(t, S, (1 - t) E) per axis - both end points exact, so each vertex appears twice, as
+ *      in the reference.  counts[n, s] = count, 0 for a dropped segment; M_n = their sum.
+ *   7. distances.  D(i, j), mA_i, mB_j, max_h [n_rows] and avg_h [n_rows] between A (M_n points) and B (P points) exactly as
+ *      hint_hausdorff_desc states them: the roots correctly rounded in fp32, their sums and the division by M_n + P in double.
+ *      The association of every double sum is hint_hausdorff_run's: thread 64 v + l over its own points i = 256 c + 64 v + l (c
+ *      ascending; for A, tile after tile of 1024 outline points), a butterfly over the lanes (distances 32 .. 1), the four
+ *      wavefronts in order.  The segment term's sum over the P minima is added the same way and divided by P in double; the corner
+ *      term's minima (exact, whatever the order) are added in double over s ascending and divided by the kept count.
+ *   8. rows that cannot be served: M_n > 4096, a parameter that is not finite, a placed vertex or a quotient that is not finite.
+ *      The quotient is cut at 8192 in double before it becomes an integer, so no loop bound comes from a wild value.  Such a row
+ *      gets NaN in max_h and avg_h and counts[n, :] = -1; its segments, keep and loss need no outline and are computed as usual
+ *      (unspecified for non-finite inputs).  Nothing faults and no other row is disturbed.
+ *   9. A row's outputs do not depend on n_rows, on where the row stands, on max_groups or on what the outputs held; two runs agree
+ *      bit for bit.  No float atomics, no counters.
+ *   run              stream-ordered on the current device: one launch, no host synchronisation, no allocation (capturable).  Each
+ *                    output may be NULL, not all six.  When none of loss, max_h and avg_h is asked, the curve is not read: x and
+ *                    b_points may then both be NULL, and n_coeffs and n_points are looked at only if one of them is named.
+ *                    max_groups: 0 = the default grid, otherwise the workgroups at most.  Rejects, before any device call and
+ *                    naming the field: a null params; both of x and b_points; neither when loss, max_h or avg_h is asked; no
+ *                    output; n_rows outside 1..2^30; with x, n_coeffs even or outside 1..25 (ignored with b_points); n_points
+ *                    outside 2..1024; max_dist not finite or <= 0; max_groups < 0; a pointer that is not 4-byte aligned.
+ *   workspace_bytes  0: no workspace is needed, so the descriptor names none.  For sizes run would reject (n_coeffs = 0 stands
+ *                    for the given source) hint_last_error() says why, otherwise it is left empty.
+ *   geometry         host only, for the default grid: field 0 the workgroups, 1 the rows a workgroup has in flight (one), 2 the
+ *                    outline points of an LDS tile, 3 the grid cap, 4 the most outline points a row may have.  Workgroup w of G
+ *                    takes rows w, w + G, ...  -1 on an error.
+ * None of these has a caller's device buffer among its parameters: the buffers are named by the descriptor. */
+typedef struct hint_plus_desc {
+    const float* x;                        /* NULL, or [n_rows, 4 n_coeffs] row-major: the traced source */
+    const float* b_points;                 /* NULL, or device float[n_rows, n_points, 2]: the given source */
+    int64_t n_rows;
+    int32_t n_coeffs, n_points;            /* K odd 1..25 (traced source), P 2..1024 */
+    const float* params;                   /* device float[n_rows, 9] */
+    float max_dist;                        /* finite, > 0; the reference's value is 0.02 */
+    int32_t max_groups;
+    float* segments;                       /* NULL, or device float[n_rows, 12, 2, 2] */
+    int32_t* keep;                         /* NULL, or device int32[n_rows]: bit s = segment s is kept */
+    int32_t* counts;                       /* NULL, or device int32[n_rows, 12] */
+    float* loss;                           /* NULL, or device float[n_rows, 2]: segment term, corner term */
+    float* max_h;                          /* NULL, or device float[n_rows] */
+    float* avg_h;                          /* NULL, or device float[n_rows] */
+} hint_plus_desc;
+size_t hint_plus_workspace_bytes(int64_t n_rows, int32_t n_coeffs, int32_t n_points);
+int hint_plus_run(const hint_plus_desc* desc, void* stream);
+int64_t hint_plus_geometry(int64_t n_rows, int32_t n_points, int32_t field);
+
 int hint_abi_version(void);
 const char* hint_last_error(void);
 /* what the library binary was built with and runs with: "libhint_amd abi N, gfx950, HIP x.y.z, clang ..., src <12 hex digits: hash

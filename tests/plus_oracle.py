@@ -1,0 +1,375 @@
+"""Float64 restatement of the plus shape's outline, fit loss and Hausdorff distances (hint_amd.curves plus_segments /
+plus_outline_counts / plus_fit_terms / plus_hausdorff_distances, include/hint_amd.h hint_plus_run) and the rule device results are
+compared by.  Written fresh from the contract; nothing of the reference is used.  The curve's points come from
+tests/curve_oracle.py (points64, scale).
+
+The contract, per row with params = (xlength, ylength, xwidth, ywidth, xshift, yshift, xoffset, yoffset, angle):
+  local vertices V0..V11 from the eight coordinates (the arms' ends clamped 0.01 beyond the other bar's sides), segment s =
+  (V_s, V_(s+1)), kept iff the two differ;  W = V R + (xoffset, yoffset), row vectors, R = [[cos, sin], [-sin, cos]]
+  loss[0] = mean over the curve's points of min over the kept segments of the squared distance to the segment
+  loss[1] = mean over the kept segments' first vertices of the squared distance to the nearest curve point
+  outline = for each kept segment count = max(1, round-half-even(max(|dx|, |dy|) / max_dist)) points E + t (S - E), t = i / (count - 1)
+  max_h, avg_h = the two-sided nearest-point distances of the outline's M points and the curve's P points
+
+The comparison rule.  u = 2^-24, R = max_s (|V_s.x| + |V_s.y|), O = max(|xoffset|, |yoffset|), S = curve_oracle.scale(x).
+  delta_B = (2K + 2) u S   for traced points, 0 for given ones (tests/hausdorff_oracle.py)
+  delta_A = 12 u (R + O)   per coordinate of an outline point: the vertex (1 rounding), the clamp's constant (0.01f against 0.01:
+                           2.3e-10 < u, and its sum's rounding), the placement (two products, an fma, a sum, the rounded cos and
+                           sin: about 4), the interpolation (t, 1 - t, a product, an fma: about 3) - about 10, with slack 12
+  E = 2 (delta_A + delta_B) + 4 u far,  far = the largest distance between a vertex and a curve point:   |max_h - max_h64| <= E
+  |avg_h - avg_h64| <= E + u avg_h64
+  each loss term within 2 sqrt(the term's largest per-point minimum in float64) E' + E'^2,  E' = E + 8 u far  (the normalisation
+                           of n and the clamped projection)
+  segments within delta_A of the oracle's; keep and counts equal (the generator keeps every quotient 1e-3 away from a half-integer,
+  which the tests assert)
+"""
+import numpy as np
+
+import curve_oracle as co
+
+U = 2.0 ** -24
+MAX_M = 4096
+VX = (0, 1, 1, 2, 2, 3, 3, 2, 2, 1, 1, 0)          # of (xleft, yleft, yright, xright)
+VY = (0, 0, 1, 1, 0, 0, 2, 2, 3, 3, 2, 2)          # of (xtop, ytop, xbottom, ybottom)
+
+# fixtures tests/golden/plus_<name>.npz (tests/golden/make_plus_golden.py): x = curve_oracle.gauss(seed, rows, K), params =
+# golden_params(case)
+GOLDEN_CASES = (
+    dict(name="k25_n8", seed=301, rows=8, K=25, zero=()),
+    dict(name="k5_n16", seed=302, rows=16, K=5, zero=()),
+    dict(name="k5_n8_zero_width", seed=303, rows=8, K=5, zero=(2, 5)),
+)
+GOLDEN_P = 1000
+GOLDEN_FIT_P = 100
+GOLDEN_WEIGHTS = (1.0, 0.5, 0.0)
+GOLDEN_MAX_DIST = 0.02
+
+
+def quotients(params, max_dist):
+    """[N, 12] float64: max(|dx|, |dy|) / max_dist of every edge (0 for a dropped one), from float64 vertices"""
+    seg, keep = segments64(params)
+    d = np.abs(seg[:, :, 1, :] - seg[:, :, 0, :]).max(2)
+    return np.where(keep_bits(keep), d / float(np.float32(max_dist)), 0.0)
+
+
+def half_gap(params, max_dist):
+    """[N]: how far the nearest kept edge's quotient is from a half-integer"""
+    q = quotients(params, max_dist)
+    return np.abs(q - np.floor(q) - 0.5).min(1)
+
+
+def draw_params(seed, N, max_dists=(0.02,), zero=None):
+    """plausible fits [N, 9] fp32: lengths 3..6, widths 0.4..2.2, shifts +-1.5, offsets N(0, 0.5), every angle; a draw of which any
+    edge's float64 quotient lies within 1e-3 of a half-integer (for one of max_dists) is rejected, so float64 and fp32 counts agree.
+    zero: {row: columns set to 0 before the draw is judged} - rows of zero width"""
+    rs = np.random.RandomState(seed)
+    rows = []
+    while len(rows) < N:
+        p = np.concatenate([rs.uniform(3, 6, 2), rs.uniform(0.4, 2.2, 2), rs.uniform(-1.5, 1.5, 2), 0.5 * rs.randn(2),
+                            rs.uniform(-np.pi, np.pi, 1)]).astype(np.float32)
+        if zero and len(rows) in zero:
+            p[list(zero[len(rows)])] = 0.0
+        if all(half_gap(p[None], md)[0] > 1e-3 for md in max_dists):
+            rows.append(p)
+    return np.stack(rows)
+
+
+def golden_params(case):
+    p = draw_params(case["seed"] + 1000, case["rows"], (GOLDEN_MAX_DIST,))
+    for r in case["zero"]:
+        p[r, 2] = 0.0                                # xwidth = 0: segments 5 and 11 drop
+    assert (half_gap(p, GOLDEN_MAX_DIST) > 1e-3).all()
+    return p
+
+
+def golden_x(case):
+    return co.gauss(case["seed"], case["rows"], case["K"])
+
+
+def keep_bits(keep):
+    return ((np.asarray(keep, np.int64)[:, None] >> np.arange(12)[None, :]) & 1).astype(bool)
+
+
+def local64(params):
+    """local vertices [N, 12, 2] in float64 (the clamp's constant is the float64 0.01, as in the reference)"""
+    p = np.asarray(params, np.float64).reshape(-1, 9)
+    xl, yl, xw, yw, xs, ys = (p[:, i] for i in range(6))
+    xleft, xright, xtop, xbottom = xs - xl / 2, xs + xl / 2, xw / 2, -xw / 2
+    yleft, yright, ybottom, ytop = -yw / 2, yw / 2, ys - yl / 2, ys + yl / 2
+    xleft, xright = np.minimum(xleft, yleft - 0.01), np.maximum(xright, yright + 0.01)
+    ytop, ybottom = np.maximum(ytop, xtop + 0.01), np.minimum(ybottom, xbottom - 0.01)
+    cx, cy = np.stack([xleft, yleft, yright, xright], 1), np.stack([xtop, ytop, xbottom, ybottom], 1)
+    return np.stack([cx[:, VX], cy[:, VY]], 2)
+
+
+def segments64(params):
+    """(segments [N, 12, 2, 2] placed, keep [N] bit masks)"""
+    p = np.asarray(params, np.float64).reshape(-1, 9)
+    V = local64(p)
+    V1 = np.roll(V, -1, 1)
+    keep = ((V != V1).any(2) * (1 << np.arange(12))[None, :]).sum(1)
+    cs, sn = np.cos(p[:, 8])[:, None], np.sin(p[:, 8])[:, None]
+    W = np.stack([V[:, :, 0] * cs - V[:, :, 1] * sn + p[:, 6:7], V[:, :, 0] * sn + V[:, :, 1] * cs + p[:, 7:8]], 2)
+    return np.stack([W, np.roll(W, -1, 1)], 2), keep
+
+
+def counts64(params, max_dist):
+    """[N, 12] int: round-half-even of the quotients, at least 1 on a kept edge, 0 on a dropped one"""
+    _, keep = segments64(params)
+    c = np.maximum(1, np.rint(np.minimum(quotients(params, max_dist), 1e6))).astype(np.int64)
+    return np.where(keep_bits(keep), c, 0)
+
+
+def outline64(seg, counts):
+    """the densified outline [M, 2] of one row"""
+    out = []
+    for s in range(12):
+        c = int(counts[s])
+        if c == 0:
+            continue
+        t = np.array([0.0]) if c == 1 else np.arange(c) / (c - 1.0)
+        out.append(t[:, None] * seg[s, 1][None, :] + (1 - t)[:, None] * seg[s, 0][None, :])
+    return np.concatenate(out)
+
+
+def segment_d2(seg, b):
+    """[S, P]: squared distance of every point of b to every segment of seg [S, 2, 2]"""
+    a, n = seg[:, 0], seg[:, 1] - seg[:, 0]
+    L = np.sqrt((n ** 2).sum(1))
+    n = n / L[:, None]
+    ap = a[:, None, :] - b[None, :, :]
+    ln = np.clip(-(ap * n[:, None, :]).sum(2), 0.0, L[:, None])
+    return ((ap + ln[:, :, None] * n[:, None, :]) ** 2).sum(2)
+
+
+def minima64(a, b, chunk=512):
+    mA, mB = np.empty(len(a)), np.full(len(b), np.inf)
+    for i in range(0, len(a), chunk):
+        D = ((a[i:i + chunk, None, :] - b[None, :, :]) ** 2).sum(2)
+        mA[i:i + chunk] = D.min(1)
+        mB = np.minimum(mB, D.min(0))
+    return mA, mB
+
+
+def plus64(params, curve=None, P=None, max_dist=0.02, distances=True):
+    """everything of the contract in float64 and the rule's bounds, as a dict of arrays over the rows.  curve: x [N, 4K] (traced at
+    P), points [N, P, 2], or None (segments, keep, counts and dA alone).  A row of more than 4096 outline points has NaN in
+    max_h / avg_h and -1 in counts."""
+    params = np.asarray(params, np.float32).reshape(-1, 9)
+    N = params.shape[0]
+    p64 = params.astype(np.float64)
+    seg, keep = segments64(params)
+    V = local64(params)
+    cnt = counts64(params, max_dist)
+    M = cnt.sum(1)
+    over = M > MAX_M
+    out = dict(segments=seg, keep=keep, counts=np.where(over[:, None], -1, cnt), M=M,
+               dA=12 * U * (np.abs(V).sum(2).max(1) + np.abs(p64[:, 6:8]).max(1)))
+    if curve is None:
+        return out
+    curve = np.asarray(curve)
+    traced = curve.ndim == 2
+    b_all = co.points64(curve, P) if traced else np.asarray(curve, np.float64)
+    dB = (2 * (curve.shape[1] // 4) + 2) * U * co.scale(curve) if traced else np.zeros(N)
+    kb = keep_bits(keep)
+    loss, top, far = np.empty((N, 2)), np.empty((N, 2)), np.empty(N)
+    max_h, avg_h = np.full(N, np.nan), np.full(N, np.nan)
+    for n in range(N):
+        b = b_all[n]
+        ks = seg[n][kb[n]]
+        d2 = segment_d2(ks, b).min(0)
+        cd = ((ks[:, 0, None, :] - b[None, :, :]) ** 2).sum(2).min(1)
+        loss[n], top[n] = (d2.mean(), cd.mean()), (d2.max(), cd.max())
+        far[n] = np.sqrt(((seg[n][:, 0, None, :] - b[None, :, :]) ** 2).sum(2).max())
+        if distances and not over[n]:
+            mA, mB = minima64(outline64(seg[n], cnt[n]), b)
+            both = np.sqrt(np.concatenate([mA, mB]))
+            max_h[n], avg_h[n] = both.max(), both.mean()
+    E = 2 * (out["dA"] + dB) + 4 * U * far
+    E2 = E + 8 * U * far
+    out.update(loss=loss, max_h=max_h, avg_h=avg_h, E=E, e_avg=E + U * np.nan_to_num(avg_h),
+               e_loss=2 * np.sqrt(top) * E2[:, None] + E2[:, None] ** 2, far=far)
+    return out
+
+
+def _ratio(got, want, bound):
+    err = np.abs(np.asarray(got, np.float64) - want)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        q = np.where(bound > 0, err / bound, np.where(err == 0, 0.0, np.inf))
+    q = np.where(np.isnan(want) & np.isnan(np.asarray(got, np.float64)), 0.0, q)      # a row that cannot be served: NaN for NaN
+    return np.where(np.isfinite(q), q, np.inf)
+
+
+def ratios(ref, segments=None, loss=None, max_h=None, avg_h=None):
+    """error / bound per row for each quantity given: a dict of [N] arrays"""
+    r = {}
+    if segments is not None:
+        err = np.abs(np.asarray(segments, np.float64) - ref["segments"]).reshape(len(ref["dA"]), -1).max(1)
+        r["segments"] = _ratio(err, 0.0, ref["dA"])
+    if loss is not None:
+        for i, name in enumerate(("loss_segment", "loss_corner")):
+            r[name] = _ratio(np.asarray(loss, np.float64)[:, i], ref["loss"][:, i], ref["e_loss"][:, i])
+    if max_h is not None:
+        r["max_h"] = _ratio(max_h, ref["max_h"], ref["E"])
+    if avg_h is not None:
+        r["avg_h"] = _ratio(avg_h, ref["avg_h"], ref["e_avg"])
+    return r
+
+
+def worst(ref, **got):
+    """[N]: the worst error / bound of a row over the quantities given"""
+    return np.max(np.stack(list(ratios(ref, **got).values())), 0)
+
+
+def check(ref, **got):
+    """the comparison rule: (rows that fail it, the worst error / bound)"""
+    r = worst(ref, **got)
+    return np.nonzero(~(r <= 1.0))[0], float(r.max())
+
+
+def find_max_dist(params, target, rows=None):
+    """(max_dist as an fp32 value, row): a max_dist at which the outline of `row` has exactly `target` points and every row's
+    quotients keep 1e-3 from a half-integer; rows: the candidates, in order.  The outline's size falls as max_dist grows, so the
+    values that give `target` are an interval, found by bisection; equal edges can make the size skip a value, then the next row
+    is tried"""
+    params = np.asarray(params, np.float32).reshape(-1, 9)
+    for r in (range(len(params)) if rows is None else rows):
+        size = lambda md: int(counts64(params[r:r + 1], float(np.float32(md))).sum())      # noqa: E731
+        ext = quotients(params[r:r + 1], 1.0)[0].sum()
+        ends = []
+        for above in (True, False):                          # the smallest max_dist with size <= target, the largest with size >= target
+            lo, hi = ext / (target + 40.0), 4.0 * ext
+            for _ in range(60):
+                mid = 0.5 * (lo + hi)
+                if (size(mid) > target) if above else (size(mid) >= target):
+                    lo = mid
+                else:
+                    hi = mid
+            ends.append(0.5 * (lo + hi))
+        for f in np.linspace(0.05, 0.95, 19):
+            md32 = float(np.float32(ends[0] + f * (ends[1] - ends[0])))
+            if size(md32) == target and (half_gap(params, md32) > 1e-3).all():
+                return md32, r
+    raise AssertionError(f"no max_dist gives an outline of {target} points")
+
+
+# ---- a float32 emulation of the contract's operation order (and deliberately wrong variants of it), for the CPU tests ----
+def _f32(v):
+    return np.asarray(v, np.float64).astype(np.float32).astype(np.float64)
+
+
+def _fma(a, b, c):
+    """fp32 fma of fp32 values held in float64: the product is exact in float64, the sum is rounded to 53 bits and then to 24"""
+    return _f32(a * b + c)
+
+
+WRONG = ("R transposed", "offset before rotation", "clamp from the clamped partner", "projection unclamped", "dropped segment kept",
+         "duplicate vertex dropped", "mean over 12 corners", "corner term rooted")
+C32 = float(np.float32(0.01))
+
+
+def local32(p, wrong=None):
+    """one row's local vertices [12, 2], fp32 values in float64"""
+    xl, yl, xw, yw, xs, ys = (float(v) for v in p[:6])
+    hx, hy = _f32(0.5 * xl), _f32(0.5 * yl)
+    xtop, yright = _f32(0.5 * xw), _f32(0.5 * yw)
+    xbottom, yleft = -xtop, -yright
+    xleft, xright, ybottom, ytop = _f32(xs - hx), _f32(xs + hx), _f32(ys - hy), _f32(ys + hy)
+    if wrong == "clamp from the clamped partner":            # the partner gives way, and the arm's own clamp finds nothing to do
+        yleft, yright = np.maximum(yleft, _f32(xleft + C32)), np.minimum(yright, _f32(xright - C32))
+        xtop, xbottom = np.minimum(xtop, _f32(ytop - C32)), np.maximum(xbottom, _f32(ybottom + C32))
+    xleft, xright = np.minimum(xleft, _f32(yleft - C32)), np.maximum(xright, _f32(yright + C32))
+    ytop, ybottom = np.maximum(ytop, _f32(xtop + C32)), np.minimum(ybottom, _f32(xbottom - C32))
+    cx, cy = np.array([xleft, yleft, yright, xright], np.float64), np.array([xtop, ytop, xbottom, ybottom], np.float64)
+    return np.stack([cx[list(VX)], cy[list(VY)]], 1)
+
+
+def place32(V, p, wrong=None):
+    xo, yo, ang = float(p[6]), float(p[7]), float(p[8])
+    cs, sn = float(np.float32(np.cos(ang))), float(np.float32(np.sin(ang)))
+    if wrong == "R transposed":
+        sn = -sn
+    vx, vy = V[:, 0], V[:, 1]
+    if wrong == "offset before rotation":
+        vx, vy, xo, yo = _f32(vx + xo), _f32(vy + yo), 0.0, 0.0
+    qx, qy = _fma(-vy, sn, _f32(vx * cs)), _fma(vy, cs, _f32(vx * sn))
+    return np.stack([_f32(qx + xo), _f32(qy + yo)], 1)
+
+
+def counts32(W, kept, max_dist, half_up=False):
+    """[12]: the contract's counts from fp32 vertices and the fp32 max_dist, in double"""
+    W1 = np.roll(W, -1, 0)
+    q = np.abs(W1 - W).max(1) / float(np.float32(max_dist))
+    c = np.floor(q + 0.5) if half_up else np.rint(q)
+    return np.where(kept, np.maximum(1, c), 0).astype(np.int64)
+
+
+def emulate32(params, curve=None, P=None, max_dist=0.02, wrong=None, half_up=False):
+    """dict of segments, keep, counts, loss, max_h, avg_h as the contract's fp32 operation order gives them; wrong: one of WRONG"""
+    from hausdorff_oracle import trace32
+    assert wrong is None or wrong in WRONG
+    params = np.asarray(params, np.float32).reshape(-1, 9)
+    N = params.shape[0]
+    b_all = None
+    if curve is not None:
+        curve = np.asarray(curve)
+        b_all = trace32(curve, P) if curve.ndim == 2 else np.asarray(curve, np.float32).astype(np.float64)
+    out = dict(segments=np.empty((N, 12, 2, 2)), keep=np.empty(N, np.int64), counts=np.empty((N, 12), np.int64),
+               loss=np.full((N, 2), np.nan), max_h=np.full(N, np.nan), avg_h=np.full(N, np.nan))
+    for n in range(N):
+        p = params[n].astype(np.float64)
+        V = local32(p, wrong)
+        kept = (V != np.roll(V, -1, 0)).any(1)
+        out["keep"][n] = int((kept * (1 << np.arange(12))).sum())
+        if wrong == "dropped segment kept":
+            kept = np.ones(12, bool)
+        W = place32(V, p, wrong)
+        W1 = np.roll(W, -1, 0)
+        out["segments"][n] = np.stack([W, W1], 1)
+        cnt = counts32(W, kept, max_dist, half_up)
+        out["counts"][n] = cnt if cnt.sum() <= MAX_M else -1
+        if b_all is None:
+            continue
+        b = b_all[n]
+        # the segment term
+        nv = _f32(W1 - W)
+        L = _f32(np.sqrt(_fma(nv[:, 1], nv[:, 1], _f32(nv[:, 0] * nv[:, 0]))))
+        with np.errstate(invalid="ignore", divide="ignore"):
+            nv = _f32(nv / L[:, None])
+        ap = _f32(W[:, None, :] - b[None, :, :])
+        dot = -_fma(ap[:, :, 1], nv[:, None, 1], _f32(ap[:, :, 0] * nv[:, None, 0]))
+        ln = dot if wrong == "projection unclamped" else np.maximum(0.0, np.minimum(L[:, None], dot))
+        vx, vy = _fma(ln, nv[:, None, 0], ap[:, :, 0]), _fma(ln, nv[:, None, 1], ap[:, :, 1])
+        d2 = _fma(vy, vy, _f32(vx * vx))
+        seg_term = np.fmin.reduce(d2[kept], 0).sum() / len(b)
+        # the corner term
+        dx, dy = _f32(W[:, None, 0] - b[None, :, 0]), _f32(W[:, None, 1] - b[None, :, 1])
+        cm = _fma(dy, dy, _f32(dx * dx)).min(1)[kept]
+        if wrong == "corner term rooted":
+            cm = _f32(np.sqrt(cm))
+        corner = cm.sum() / (12 if wrong == "mean over 12 corners" else len(cm))
+        out["loss"][n] = np.float32(seg_term), np.float32(corner)
+        if cnt.sum() > MAX_M:
+            continue
+        # the outline and the distances
+        pts = []
+        for s in range(12):
+            c = int(cnt[s])
+            if c == 0:
+                continue
+            if c == 1:
+                pts.append(W[s][None, :])
+                continue
+            t = _f32(np.arange(c) / (c - 1.0))
+            a = _fma(t[:, None], W1[s][None, :], _f32(_f32(1.0 - t)[:, None] * W[s][None, :]))
+            pts.append(a[:-1] if wrong == "duplicate vertex dropped" else a)
+        a = np.concatenate(pts)
+        mA, mB = np.empty(len(a)), np.full(len(b), np.inf)
+        for i in range(0, len(a), 512):
+            ddx, ddy = _f32(a[i:i + 512, None, 0] - b[None, :, 0]), _f32(a[i:i + 512, None, 1] - b[None, :, 1])
+            D = _fma(ddy, ddy, _f32(ddx * ddx))
+            mA[i:i + 512] = D.min(1)
+            mB = np.minimum(mB, D.min(0))
+        roots = _f32(np.sqrt(np.concatenate([mA, mB])))
+        out["max_h"][n], out["avg_h"][n] = np.float32(roots.max()), np.float32(roots.sum() / len(roots))
+    return out

@@ -233,15 +233,13 @@ int hint_curve_run(const hint_curve_desc* desc, void* stream) {
     if (desc->mean && !desc->target) return fail("hint_curve_run: mean needs a target (target is null)");
     if (desc->max_groups < 0) return fail("hint_curve_run: max_groups must be >= 0 (got %d)", desc->max_groups);
     if (!std::isfinite(desc->noise)) return fail("hint_curve_run: noise must be finite");
-    if (((uintptr_t)desc->x & 3) != 0) return fail("hint_curve_run: x must be 4-byte aligned");
-    if (((uintptr_t)desc->eps & 3) != 0) return fail("hint_curve_run: eps must be 4-byte aligned");
-    if (((uintptr_t)desc->target & 3) != 0) return fail("hint_curve_run: target must be 4-byte aligned");
-    if (((uintptr_t)desc->y & 3) != 0) return fail("hint_curve_run: y must be 4-byte aligned");
-    if (((uintptr_t)desc->dist & 3) != 0) return fail("hint_curve_run: dist must be 4-byte aligned");
-    if (((uintptr_t)desc->mean & 3) != 0) return fail("hint_curve_run: mean must be 4-byte aligned");
+    const char* who = "hint_curve_run";
+    if (misaligned(who, "x", desc->x, 3) || misaligned(who, "eps", desc->eps, 3) || misaligned(who, "target", desc->target, 3) ||
+        misaligned(who, "y", desc->y, 3) || misaligned(who, "dist", desc->dist, 3) || misaligned(who, "mean", desc->mean, 3))
+        return 1;
     if (desc->mean) {
         if (!desc->workspace) return fail("hint_curve_run: workspace is null (mean needs one)");
-        if (((uintptr_t)desc->workspace & 15) != 0) return fail("hint_curve_run: workspace must be 16-byte aligned");
+        if (misaligned(who, "workspace", desc->workspace, 15)) return 1;
         if (desc->workspace_bytes < curve_ws_bytes())
             return fail("hint_curve_run: workspace_bytes = %zu is too small (hint_curve_workspace_bytes: %zu)", desc->workspace_bytes,
                         curve_ws_bytes());

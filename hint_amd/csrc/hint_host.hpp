@@ -83,6 +83,11 @@ std::string& last_error_ref();           // that message (hint_plan_create keeps
         if (e_ != hipSuccess) return fail("%s: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
 
+// an entry point's check of a pointer argument (null passes): 0, or fail() with the message every entry point words alike
+inline int misaligned(const char* who, const char* name, const void* p, int mask) {
+    return ((uintptr_t)p & mask) != 0 ? fail("%s: %s must be %d-byte aligned", who, name, mask + 1) : 0;
+}
+
 inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 inline int pad4(int v) { return (v + 3) & ~3; }
 

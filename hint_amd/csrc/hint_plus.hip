@@ -8,41 +8,31 @@
 // association of the double sums - is stated in include/hint_amd.h (hint_plus_desc).
 //
 // hint_plus_kernel: the shape of hint_hausdorff_kernel - a persistent grid of G workgroups of 256 threads; workgroup w takes rows
-// w, w + G, ... one at a time; the twiddle table once per workgroup - with a template that exists nowhere in memory:
+// w, w + G, ... one at a time; the twiddle table once per workgroup - built from the same core (hint_pointset.hpp: the trace, the
+// two-pass walk, the reductions), with a template that exists nowhere in memory:
 //   - per row, thread 0 turns the 9 parameters into the 8 clamped coordinates, cs, sn (double sincos, not inlined) and a finite
 //     flag in LDS; lanes 0..11 of wavefront 0 then each take one segment: its two local vertices (picked from the 8 coordinates by
 //     two packed index tables), the keep bit, the two placed vertices (written to `segments`), the loss's constants (a, n, L) and
 //     the outline's count (one double division); a ballot gives `keep`, a 12-lane shuffle scan the prefix sums of the counts;
-//   - B is traced or loaded into LDS as in hint_hausdorff_kernel; each thread then holds its <= 4 B points in registers;
+//   - B is traced or loaded into LDS (ps_stage_curve); each thread then holds its <= 4 B points in registers;
 //   - loss: the thread walks the kept segments (constants from LDS, every read a wavefront broadcast) over its own B points and
 //     keeps min_s d^2; the corner term is 12 workgroup-wide minima (thread, six xor-shuffles, four wavefronts through LDS);
-//   - Hausdorff: the two-pass walk of hint_hausdorff_kernel over LDS tiles of 1024 outline points, which thread t generates
-//     (points t, t + 256, ... of the tile): the point's edge by a 4-step search in the 16 padded prefix sums, one fp32 division for
-//     t, two products and two fmas;
-//   - the reductions as in hint_hausdorff_kernel.
+//   - Hausdorff: ps_two_sided over LDS tiles of 1024 outline points, with a tile filler that generates them: the point's edge by
+//     a 4-step search in the 16 padded prefix sums, one fp32 division for t, two products and two fmas;
+//   - ps_block_reduce over the two root sums, the segment term and the maximum.
 // Nothing is carried from row to row and no output is read back.  No float atomics, no counters, no workspace.  Untuned defaults
 // (tile size, points per thread, grid cap, prefix search, the serial parameter stage): DESIGN section 15.
-#include "hint_host.hpp"
+#include "hint_pointset.hpp"
 
 namespace hint {
 
-constexpr int PL_MAX_K = 25, PL_MIN_P = 2, PL_MAX_P = 1024;
-constexpr int PL_MAX_M = 4096;                  // outline points of a row
-constexpr int PL_TILE = 1024;                   // outline points in LDS at a time
-constexpr int PL_THREADS = 256, PL_PER = 4;     // PL_PER = PL_MAX_P / PL_THREADS = PL_TILE / PL_THREADS points per thread
 constexpr int PL_MAX_WG = 1024;                 // the grid cap: 256 CUs x 4 workgroups (113 VGPRs: 4 wavefronts a SIMD)
-constexpr long long PL_MAX_N = 1LL << 30;
 constexpr double PL_Q_CAP = 8192.0;             // a quotient is cut here before it becomes an integer (12 x 8192 fits an int)
 
 // which of the 8 coordinates (0 xleft, 1 yleft, 2 yright, 3 xright; 4 xtop, 5 ytop, 6 xbottom, 7 ybottom) vertex s takes, 4 bits
 // a vertex
 constexpr unsigned long long PL_VX = 0x011223322110ULL;   // s = 0 is the lowest nibble: 0 1 1 2 2 3 3 2 2 1 1 0
 constexpr unsigned long long PL_VY = 0x667766445544ULL;   // 4 4 5 5 4 4 6 6 7 7 6 6
-
-inline int pl_grid(long long n, int max_groups) {
-    const long long cap = max_groups > 0 && max_groups < PL_MAX_WG ? max_groups : PL_MAX_WG;
-    return (int)(n < cap ? n : cap);
-}
 
 }  // namespace hint
 
@@ -57,43 +47,6 @@ struct pl_row {
     int pre[16];                                 // exclusive prefix sums of the counts; pre[12] = M, pre[13..15] = INT_MAX
     int keep, nk, M, bad;
 };
-
-// (as hd_scan of hint_hausdorff.hip) the walk of both passes: NC points of this thread against n points in LDS
-template <int NC>
-__device__ __forceinline__ void pl_scan(const float2* src, int n, const float (&px)[hint::PL_PER], const float (&py)[hint::PL_PER],
-                                        float (&m)[hint::PL_PER]) {
-#pragma unroll 4
-    for (int j = 0; j < n; ++j) {
-        const float2 q = src[j];
-#pragma unroll
-        for (int c = 0; c < NC; ++c) {
-            const float dx = __fsub_rn(px[c], q.x), dy = __fsub_rn(py[c], q.y);
-            m[c] = fminf(m[c], __fmaf_rn(dy, dy, __fmul_rn(dx, dx)));
-        }
-    }
-}
-
-__device__ __forceinline__ void pl_scan_n(int nc, const float2* src, int n, const float (&px)[hint::PL_PER],
-                                          const float (&py)[hint::PL_PER], float (&m)[hint::PL_PER]) {
-    switch (nc) {                                            // (nc is the same for the whole workgroup)
-        case 1: pl_scan<1>(src, n, px, py, m); break;
-        case 2: pl_scan<2>(src, n, px, py, m); break;
-        case 3: pl_scan<3>(src, n, px, py, m); break;
-        default: pl_scan<4>(src, n, px, py, m); break;
-    }
-}
-
-__device__ __forceinline__ double pl_wave_sum(double v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);             // (a + b = b + a: every lane ends with the same bits)
-    return v;
-}
-
-__device__ __forceinline__ float pl_wave_min(float v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v = fminf(v, __shfl_xor(v, m, 64));
-    return v;
-}
 
 // the row's 8 coordinates, cs, sn and the offsets to LDS, by one thread.  Not inlined, as hd_stage_params and for the same
 // reason: the double-precision sincos holds some thirty registers of constants
@@ -138,25 +91,17 @@ __global__ __launch_bounds__(256) void hint_plus_kernel(const float* __restrict_
                                                         int* __restrict__ counts, float* __restrict__ loss,
                                                         float* __restrict__ max_h, float* __restrict__ avg_h) {
     using namespace hint;
-    __shared__ float2 tw[PL_MAX_P];                          // [r], r < P - 1
-    __shared__ float2 Bp[PL_MAX_P];
-    __shared__ float2 Ap[PL_TILE];
-    __shared__ float coef[4 * PL_MAX_K + 4];
+    __shared__ float2 tw[PS_MAX_P];                          // [r], r < P - 1
+    __shared__ float2 Bp[PS_MAX_P];
+    __shared__ float2 Ap[PS_TILE];
+    __shared__ float coef[4 * PS_MAX_K + 4];
     __shared__ pl_row rw;
-    __shared__ double red[PL_THREADS / 64][3];               // roots of mA, roots of mB, the segment term
-    __shared__ float redm[PL_THREADS / 64];
-    __shared__ float redc[PL_THREADS / 64][12];              // the corner minima
-    const int t = threadIdx.x, l = t & 63, wv = t >> 6;
-    const int Pm1 = P - 1, H = K / 2, C = 4 * K;
+    __shared__ double red[PS_WAVES][3];                      // roots of mA, roots of mB, the segment term
+    __shared__ float redm[PS_WAVES];
+    __shared__ float redc[PS_WAVES][12];                     // the corner minima
+    const int t = threadIdx.x, l = t & 63, wv = t >> 6, C = 4 * K;
     const bool traced = x != nullptr, with_h = max_h || avg_h, with_curve = with_h || loss;
-    const int ncB = (P + PL_THREADS - 1) / PL_THREADS;
-    if (traced && with_curve) {
-        for (int r = t; r < Pm1; r += PL_THREADS) {
-            double sn, cs;
-            sincospi(2.0 * (double)r / (double)(P - 1), &sn, &cs);
-            tw[r] = make_float2((float)cs, (float)sn);
-        }
-    }
+    if (traced && with_curve) ps_twiddles(tw, P, t);
     const float qnan = __int_as_float(0x7fc00000);
     for (int row = blockIdx.x; row < n; row += gridDim.x) {                  // (n <= 2^30)
         if (traced && with_curve && t < C) coef[t] = x[(size_t)row * C + t];
@@ -185,7 +130,7 @@ __global__ __launch_bounds__(256) void hint_plus_kernel(const float* __restrict_
             }
             const unsigned long long kmask = __ballot(kept), wmask = __ballot(wild);
             const int M = __shfl(incl, 11, 64);
-            const bool bad = wmask != 0 || rw.finite == 0 || M < 1 || M > PL_MAX_M;
+            const bool bad = wmask != 0 || rw.finite == 0 || M < 1 || M > PS_MAX_M;
             if (l < 12) {
                 const float nx = __fsub_rn(w1.x, w0.x), ny = __fsub_rn(w1.y, w0.y);
                 const float L = __fsqrt_rn(__fmaf_rn(ny, ny, __fmul_rn(nx, nx)));
@@ -218,61 +163,25 @@ __global__ __launch_bounds__(256) void hint_plus_kernel(const float* __restrict_
             __syncthreads();                                 // the next row overwrites rw
             continue;
         }
-        // ---- B: points t, t + 256, ... to LDS (a rolled loop: one copy of the trace) ----
-#pragma unroll 1
-        for (int tt = t; tt < P; tt += PL_THREADS) {
-            float ax = 0.f, ay = 0.f;
-            if (traced) {
-                const int t0 = tt == Pm1 ? 0 : tt;                           // t mod (P - 1)
-                int r = (H * t0) % Pm1;
-                for (int k = 0; k < K; ++k) {
-                    const int m = k - H;
-                    float2 w = tw[r];
-                    if (m < 0) w.y = -w.y;
-                    ax = __fmaf_rn(coef[k], w.x, ax);
-                    ax = __fmaf_rn(-coef[2 * K + k], w.y, ax);
-                    ay = __fmaf_rn(coef[K + k], w.x, ay);
-                    ay = __fmaf_rn(-coef[3 * K + k], w.y, ay);
-                    if (m < 0) {                                             // r of the next k: |m| goes down to 0, then up
-                        r -= t0;
-                        if (r < 0) r += Pm1;
-                    } else {
-                        r += t0;
-                        if (r >= Pm1) r -= Pm1;
-                    }
-                }
-            } else {
-                const float* bp = b_points + 2 * ((size_t)row * P + tt);
-                ax = bp[0];
-                ay = bp[1];
-            }
-            Bp[tt] = make_float2(ax, ay);
-        }
+        ps_stage_curve(Bp, tw, coef, traced, b_points, nullptr, (size_t)row, K, P, t);
         __syncthreads();                                     // Bp and rw are whole
-        // this thread's B points; a slot past the end repeats the last point and is not counted below
-        float bx[PL_PER], by[PL_PER];
-#pragma unroll
-        for (int c = 0; c < PL_PER; ++c) {
-            const int j = t + PL_THREADS * c;
-            const float2 pb = Bp[j < P ? j : P - 1];
-            bx[c] = pb.x;
-            by[c] = pb.y;
-        }
+        float bx[PS_PER], by[PS_PER];
+        ps_own_points(Bp, P, t, bx, by);
         const int kmask = rw.keep, M = rw.M;
         const bool bad = rw.bad != 0;
         double s_seg = 0.0;
         if (loss) {
             // ---- the segment term: min over the kept segments of the squared distance to the segment ----
-            float ms[PL_PER];
+            float ms[PS_PER];
 #pragma unroll
-            for (int c = 0; c < PL_PER; ++c) ms[c] = INFINITY;
+            for (int c = 0; c < PS_PER; ++c) ms[c] = INFINITY;
 #pragma unroll 1
             for (int s = 0; s < 12; ++s) {
                 if (!((kmask >> s) & 1)) continue;
                 const float2 a = rw.a[s], nn = rw.n[s];
                 const float L = rw.L[s];
 #pragma unroll
-                for (int c = 0; c < PL_PER; ++c) {
+                for (int c = 0; c < PS_PER; ++c) {
                     const float apx = __fsub_rn(a.x, bx[c]), apy = __fsub_rn(a.y, by[c]);
                     const float len = fmaxf(0.f, fminf(L, -__fmaf_rn(apy, nn.y, __fmul_rn(apx, nn.x))));
                     const float vx = __fmaf_rn(len, nn.x, apx), vy = __fmaf_rn(len, nn.y, apy);
@@ -280,108 +189,52 @@ __global__ __launch_bounds__(256) void hint_plus_kernel(const float* __restrict_
                 }
             }
 #pragma unroll
-            for (int c = 0; c < PL_PER; ++c)
-                if (t + PL_THREADS * c < P) s_seg += (double)ms[c];
+            for (int c = 0; c < PS_PER; ++c)
+                if (t + PS_THREADS * c < P) s_seg += (double)ms[c];
             // ---- the corner term: for each vertex the nearest curve point (a repeated slot does not change a minimum) ----
 #pragma unroll 1
             for (int s = 0; s < 12; ++s) {
                 const float2 w = rw.W[s];
                 float m = INFINITY;
 #pragma unroll
-                for (int c = 0; c < PL_PER; ++c) {
+                for (int c = 0; c < PS_PER; ++c) {
                     const float dx = __fsub_rn(w.x, bx[c]), dy = __fsub_rn(w.y, by[c]);
                     m = fminf(m, __fmaf_rn(dy, dy, __fmul_rn(dx, dx)));
                 }
-                m = pl_wave_min(m);
+                m = ps_wave_min(m);
                 if (l == 0) redc[wv][s] = m;
             }
         }
-        float mx = 0.f;                                      // the largest minimum (every D is >= 0 or NaN)
-        double sa_rt = 0.0, sb_rt = 0.0;
+        ps_part part;
         if (with_h && !bad) {
-            float mb[PL_PER];
+            // outline point g lies on the edge s with pre[s] <= g < pre[s + 1]
+            part = ps_two_sided(Ap, Bp, M, P, t, bx, by, [&](int g) {        // (M <= 4096 here)
+                int s = 0;
 #pragma unroll
-            for (int c = 0; c < PL_PER; ++c) mb[c] = INFINITY;
-            for (int a0 = 0; a0 < M; a0 += PL_TILE) {        // (M <= 4096 here)
-                const int cnt = M - a0 < PL_TILE ? M - a0 : PL_TILE;
-                const int ncA = (cnt + PL_THREADS - 1) / PL_THREADS;
-                if (a0) __syncthreads();                     // the walks of the tile before are done with Ap
-                // ---- generate the tile: outline point g lies on the edge s with pre[s] <= g < pre[s + 1] ----
-#pragma unroll 1
-                for (int i = t; i < cnt; i += PL_THREADS) {
-                    const int g = a0 + i;
-                    int s = 0;
-#pragma unroll
-                    for (int d = 8; d >= 1; d >>= 1)
-                        if (rw.pre[s + d] <= g) s += d;      // (s + d <= 15; pre[12] = M > g, so s <= 11)
-                    const int first = rw.pre[s], ec = rw.pre[s + 1] - first;
-                    const float2 e = rw.W[s], nx = rw.W[s + 1];
-                    float2 a = e;
-                    if (ec > 1) {
-                        const float tq = __fdiv_rn((float)(g - first), (float)(ec - 1)), om = __fsub_rn(1.f, tq);
-                        a.x = __fmaf_rn(tq, nx.x, __fmul_rn(om, e.x));
-                        a.y = __fmaf_rn(tq, nx.y, __fmul_rn(om, e.y));
-                    }
-                    Ap[i] = a;
+                for (int d = 8; d >= 1; d >>= 1)
+                    if (rw.pre[s + d] <= g) s += d;          // (s + d <= 15; pre[12] = M > g, so s <= 11)
+                const int first = rw.pre[s], ec = rw.pre[s + 1] - first;
+                const float2 e = rw.W[s], nx = rw.W[s + 1];
+                float2 a = e;
+                if (ec > 1) {
+                    const float tq = __fdiv_rn((float)(g - first), (float)(ec - 1)), om = __fsub_rn(1.f, tq);
+                    a.x = __fmaf_rn(tq, nx.x, __fmul_rn(om, e.x));
+                    a.y = __fmaf_rn(tq, nx.y, __fmul_rn(om, e.y));
                 }
-                __syncthreads();
-                float px[PL_PER], py[PL_PER], ma[PL_PER];
-#pragma unroll
-                for (int c = 0; c < PL_PER; ++c) {
-                    const int i = t + PL_THREADS * c;
-                    const float2 pa = Ap[i < cnt ? i : cnt - 1];
-                    px[c] = pa.x;
-                    py[c] = pa.y;
-                    ma[c] = INFINITY;
-                }
-                pl_scan_n(ncA, Bp, P, px, py, ma);           // pass 1: mA of this thread's points of the tile
-                pl_scan_n(ncB, Ap, cnt, bx, by, mb);         // pass 2: mB so far
-#pragma unroll
-                for (int c = 0; c < PL_PER; ++c) {
-                    if (t + PL_THREADS * c < cnt) {          // (then c < ncA)
-                        mx = fmaxf(mx, ma[c]);
-                        sa_rt += (double)__fsqrt_rn(ma[c]);
-                    }
-                }
-            }
-#pragma unroll
-            for (int c = 0; c < PL_PER; ++c) {
-                if (t + PL_THREADS * c < P) {                // (then c < ncB)
-                    mx = fmaxf(mx, mb[c]);
-                    sb_rt += (double)__fsqrt_rn(mb[c]);
-                }
-            }
+                return a;
+            });
         }
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) mx = fmaxf(mx, __shfl_xor(mx, m, 64));
-        sa_rt = pl_wave_sum(sa_rt);
-        sb_rt = pl_wave_sum(sb_rt);
-        s_seg = pl_wave_sum(s_seg);
-        if (l == 0) {
-            red[wv][0] = sa_rt;
-            red[wv][1] = sb_rt;
-            red[wv][2] = s_seg;
-            redm[wv] = mx;
-        }
-        __syncthreads();                                     // (and every walk is done: the next row may overwrite Bp, Ap, coef, rw)
+        double s[3] = {part.a_rt, part.b_rt, s_seg};
+        ps_block_reduce(s, part.mx, red, redm, t);           // (past its barrier the next row may overwrite Bp, Ap, coef, rw)
         if (t == 0) {
-            double s[3];
-            float v = redm[0];
-#pragma unroll
-            for (int q = 0; q < 3; ++q) s[q] = red[0][q];
-            for (int w = 1; w < PL_THREADS / 64; ++w) {
-                v = fmaxf(v, redm[w]);
-#pragma unroll
-                for (int q = 0; q < 3; ++q) s[q] += red[w][q];
-            }
-            if (max_h) max_h[row] = bad ? qnan : __fsqrt_rn(v);
+            if (max_h) max_h[row] = bad ? qnan : __fsqrt_rn(part.mx);
             if (avg_h) avg_h[row] = bad ? qnan : (float)((s[0] + s[1]) / (double)(M + P));
             if (loss) {
                 double sc = 0.0;
                 for (int k = 0; k < 12; ++k) {
                     if (!((kmask >> k) & 1)) continue;
                     float m = redc[0][k];
-                    for (int w = 1; w < PL_THREADS / 64; ++w) m = fminf(m, redc[w][k]);
+                    for (int w = 1; w < PS_WAVES; ++w) m = fminf(m, redc[w][k]);
                     sc += (double)m;
                 }
                 loss[2 * (size_t)row] = (float)(s[2] / (double)P);
@@ -394,33 +247,23 @@ __global__ __launch_bounds__(256) void hint_plus_kernel(const float* __restrict_
 // ---- the C ABI ----
 using namespace hint;
 
-static int pl_check_sizes(const char* who, int64_t n_rows, int32_t n_coeffs, int32_t n_points, bool traced, bool with_curve) {
-    if (n_rows < 1 || n_rows > PL_MAX_N) return fail("%s: n_rows must be 1..%lld (got %lld)", who, PL_MAX_N, (long long)n_rows);
-    if (!with_curve) return 0;
-    if (traced && (n_coeffs < 1 || n_coeffs > PL_MAX_K || (n_coeffs & 1) == 0))
-        return fail("%s: n_coeffs must be odd and 1..%d (got %d)", who, PL_MAX_K, n_coeffs);
-    if (n_points < PL_MIN_P || n_points > PL_MAX_P)
-        return fail("%s: n_points must be %d..%d (got %d)", who, PL_MIN_P, PL_MAX_P, n_points);
-    return 0;
-}
-
 extern "C" {
 
 size_t hint_plus_workspace_bytes(int64_t n_rows, int32_t n_coeffs, int32_t n_points) {
     // n_coeffs = 0 stands for the given-points source, which has no coefficients
-    if (pl_check_sizes("hint_plus_workspace_bytes", n_rows, n_coeffs, n_points, n_coeffs != 0, true)) return 0;
+    if (ps_check_sizes("hint_plus_workspace_bytes", n_rows, n_coeffs, n_points, n_coeffs != 0, true)) return 0;
     last_error_ref().clear();
     return 0;                                                // the kernel needs none
 }
 
 int64_t hint_plus_geometry(int64_t n_rows, int32_t n_points, int32_t field) {
-    if (pl_check_sizes("hint_plus_geometry", n_rows, 1, n_points, false, true)) return -1;
+    if (ps_check_sizes("hint_plus_geometry", n_rows, 1, n_points, false, true)) return -1;
     if (field < 0 || field > 4) {
         fail("hint_plus_geometry: no field %d (0 workgroups, 1 rows per workgroup at a time, 2 outline points per LDS tile, "
              "3 the grid cap, 4 the most outline points of a row)", field);
         return -1;
     }
-    const int64_t out[5] = {pl_grid(n_rows, 0), 1, PL_TILE, PL_MAX_WG, PL_MAX_M};
+    const int64_t out[5] = {ps_grid(n_rows, 0, PL_MAX_WG), 1, PS_TILE, PL_MAX_WG, PS_MAX_M};
     return out[field];
 }
 
@@ -434,24 +277,20 @@ int hint_plus_run(const hint_plus_desc* desc, void* stream) {
     if (desc->x && desc->b_points) return fail("%s: both x and b_points are given (the curve has one source)", who);
     if (with_curve && !desc->x && !desc->b_points)
         return fail("%s: x and b_points are both null (loss, max_h and avg_h need the curve)", who);
-    if (pl_check_sizes(who, desc->n_rows, desc->n_coeffs, desc->n_points, desc->x != nullptr,
+    if (ps_check_sizes(who, desc->n_rows, desc->n_coeffs, desc->n_points, desc->x != nullptr,
                        with_curve || desc->x || desc->b_points))
         return 1;
     if (!(desc->max_dist > 0.f) || !std::isfinite(desc->max_dist))
         return fail("%s: max_dist must be finite and > 0 (got %g)", who, (double)desc->max_dist);
     if (desc->max_groups < 0) return fail("%s: max_groups must be >= 0 (got %d)", who, desc->max_groups);
-    if (((uintptr_t)desc->x & 3) != 0) return fail("%s: x must be 4-byte aligned", who);
-    if (((uintptr_t)desc->b_points & 3) != 0) return fail("%s: b_points must be 4-byte aligned", who);
-    if (((uintptr_t)desc->params & 3) != 0) return fail("%s: params must be 4-byte aligned", who);
-    if (((uintptr_t)desc->segments & 3) != 0) return fail("%s: segments must be 4-byte aligned", who);
-    if (((uintptr_t)desc->keep & 3) != 0) return fail("%s: keep must be 4-byte aligned", who);
-    if (((uintptr_t)desc->counts & 3) != 0) return fail("%s: counts must be 4-byte aligned", who);
-    if (((uintptr_t)desc->loss & 3) != 0) return fail("%s: loss must be 4-byte aligned", who);
-    if (((uintptr_t)desc->max_h & 3) != 0) return fail("%s: max_h must be 4-byte aligned", who);
-    if (((uintptr_t)desc->avg_h & 3) != 0) return fail("%s: avg_h must be 4-byte aligned", who);
-    const int grid = pl_grid(desc->n_rows, desc->max_groups);
+    if (misaligned(who, "x", desc->x, 3) || misaligned(who, "b_points", desc->b_points, 3) ||
+        misaligned(who, "params", desc->params, 3) || misaligned(who, "segments", desc->segments, 3) ||
+        misaligned(who, "keep", desc->keep, 3) || misaligned(who, "counts", desc->counts, 3) ||
+        misaligned(who, "loss", desc->loss, 3) || misaligned(who, "max_h", desc->max_h, 3) || misaligned(who, "avg_h", desc->avg_h, 3))
+        return 1;
+    const int grid = ps_grid(desc->n_rows, desc->max_groups, PL_MAX_WG);
     // without a curve output the kernel reads no curve: P = 2 keeps its (unused) sizes in range
-    hipLaunchKernelGGL(hint_plus_kernel, dim3(grid), dim3(PL_THREADS), 0, (hipStream_t)stream, with_curve ? desc->x : nullptr,
+    hipLaunchKernelGGL(hint_plus_kernel, dim3(grid), dim3(PS_THREADS), 0, (hipStream_t)stream, with_curve ? desc->x : nullptr,
                        with_curve ? desc->b_points : nullptr, (int)desc->n_rows, with_curve && desc->x ? desc->n_coeffs : 1,
                        with_curve ? desc->n_points : 2, desc->params, desc->max_dist, desc->segments, desc->keep, desc->counts,
                        desc->loss, desc->max_h, desc->avg_h);

@@ -269,13 +269,18 @@ def _check_params_shape(shape, n_rows: int, who: str):
                            f"(got {tuple(shape)})")
 
 
-def _distance_args(curve, template, params, offsets, n_points, who: str):
+def _curve_arg(curve, n_points, who: str):
+    """curve, as [N, 4K] coefficients or [N, P, 2] points -> (the checked device tensor, rows, K or 0, P)"""
     if not isinstance(curve, torch.Tensor):
         raise HintAmdError(f"{who}: curve must be a tensor (got {type(curve).__name__})")
     if curve.dim() not in (2, 3):
         raise HintAmdError(f"{who}: curve must be [rows, 4 K] coefficients or [rows, P, 2] points (got shape {tuple(curve.shape)})")
     curve = _check_dev_tensor(curve, "curve", who)
-    n, k, p = _check_curve_shape(tuple(curve.shape), n_points, who)
+    return (curve,) + _check_curve_shape(tuple(curve.shape), n_points, who)
+
+
+def _distance_args(curve, template, params, offsets, n_points, who: str):
+    curve, n, k, p = _curve_arg(curve, n_points, who)
     template = _check_dev_tensor(template, "template", who, curve.device)
     t_pts = _check_template_shape(tuple(template.shape), offsets is not None, who)
     if offsets is not None:
@@ -408,12 +413,7 @@ def _plus_params(params, n_rows: Optional[int], who: str, device=None) -> torch.
 
 
 def _plus_args(curve, params, n_points, who: str):
-    if not isinstance(curve, torch.Tensor):
-        raise HintAmdError(f"{who}: curve must be a tensor (got {type(curve).__name__})")
-    if curve.dim() not in (2, 3):
-        raise HintAmdError(f"{who}: curve must be [rows, 4 K] coefficients or [rows, P, 2] points (got shape {tuple(curve.shape)})")
-    curve = _check_dev_tensor(curve, "curve", who)
-    n, k, p = _check_curve_shape(tuple(curve.shape), n_points, who)
+    curve, n, k, p = _curve_arg(curve, n_points, who)
     return curve, k, p, _plus_params(params, n, who, curve.device)
 
 

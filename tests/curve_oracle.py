@@ -151,3 +151,50 @@ def golden_draw(case):
 def golden_eps(case):
     """what numpy's global generator yields after np.random.seed(seed): the reference's noise for the distance fixtures"""
     return np.random.RandomState(case["seed"]).randn(case["rows"], 2)
+
+
+# ---- what the oracles of the curve-to-point-set distances share (tests/hausdorff_oracle.py, tests/plus_oracle.py) ----
+def minima64(a, b, chunk=512):
+    """(mA [M], mB [P], the largest squared distance) of the [M, P] matrix of squared distances, in chunks of rows"""
+    mA, mB, far = np.empty(len(a)), np.full(len(b), np.inf), 0.0
+    for i in range(0, len(a), chunk):
+        D = ((a[i:i + chunk, None, :] - b[None, :, :]) ** 2).sum(2)
+        mA[i:i + chunk] = D.min(1)
+        mB = np.minimum(mB, D.min(0))
+        far = max(far, D.max())
+    return mA, mB, far
+
+
+# a float32 emulation of the contract's operation order, for the CPU tests
+def _f32(v):
+    return np.asarray(v, np.float64).astype(np.float32).astype(np.float64)
+
+
+def _fma(a, b, c):
+    """fp32 fma of fp32 values held in float64: the product is exact in float64, the sum is rounded to 53 bits and then to 24"""
+    return _f32(a * b + c)
+
+
+def trace32(x, P):
+    """[N, P, 2]: fp32 fma over k ascending, real term then imaginary term, twiddles rounded to fp32 after the exact reduction"""
+    x = np.asarray(x, np.float32).astype(np.float64)
+    n, K = x.shape[0], x.shape[1] // 4
+    re, im = x[:, :2 * K].reshape(n, 2, K), x[:, 2 * K:].reshape(n, 2, K)
+    c, s = twiddles(K, P)
+    c, s = _f32(c), _f32(s)
+    acc = np.zeros((n, P, 2))
+    for k in range(K):
+        acc = _fma(re[:, None, :, k], c[None, :, None, k], acc)
+        acc = _fma(-im[:, None, :, k], s[None, :, None, k], acc)
+    return acc
+
+
+def minima32(a, b, chunk=512):
+    """(mA [M], mB [P]) of D = fma(dy, dy, dx dx) in fp32, a - b, in chunks of rows"""
+    mA, mB = np.empty(len(a)), np.full(len(b), np.inf)
+    for i in range(0, len(a), chunk):
+        dx, dy = _f32(a[i:i + chunk, None, 0] - b[None, :, 0]), _f32(a[i:i + chunk, None, 1] - b[None, :, 1])
+        D = _fma(dy, dy, _f32(dx * dx))
+        mA[i:i + chunk] = D.min(1)
+        mB = np.minimum(mB, D.min(0))
+    return mA, mB

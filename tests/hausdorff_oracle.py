@@ -18,6 +18,7 @@ per coordinate-wise statement of hint_amd.h's operation order.  Min, max and mea
 import numpy as np
 
 import curve_oracle as co
+from curve_oracle import _f32, _fma, trace32
 
 U = 2.0 ** -24
 
@@ -59,20 +60,9 @@ def template64(a, params=None):
     return (a @ R) * s + np.array([x, y])
 
 
-def minima64(a, b, chunk=512):
-    """(mA [M], mB [P], the largest squared distance) of the [M, P] matrix of squared distances, in chunks of rows"""
-    mA, mB, far = np.empty(len(a)), np.full(len(b), np.inf), 0.0
-    for i in range(0, len(a), chunk):
-        D = ((a[i:i + chunk, None, :] - b[None, :, :]) ** 2).sum(2)
-        mA[i:i + chunk] = D.min(1)
-        mB = np.minimum(mB, D.min(0))
-        far = max(far, D.max())
-    return mA, mB, far
-
-
 def row64(a, b):
     """max_h, avg_h, (chamfer0, chamfer1) and the largest distance between a template and a curve point, of one row"""
-    mA, mB, far = minima64(a, b)
+    mA, mB, far = co.minima64(a, b)
     both = np.concatenate([mA, mB])
     return np.sqrt(both.max()), np.sqrt(both).mean(), (mB.mean(), mA.mean()), np.sqrt(far)
 
@@ -125,29 +115,6 @@ def check(ref, max_h=None, avg_h=None, chamfer=None):
 
 
 # ---- a float32 emulation of the contract's operation order (and deliberately wrong variants of it), for the CPU tests ----
-def _f32(v):
-    return np.asarray(v, np.float64).astype(np.float32).astype(np.float64)
-
-
-def _fma(a, b, c):
-    """fp32 fma of fp32 values held in float64: the product is exact in float64, the sum is rounded to 53 bits and then to 24"""
-    return _f32(a * b + c)
-
-
-def trace32(x, P):
-    """[N, P, 2]: fp32 fma over k ascending, real term then imaginary term, twiddles rounded to fp32 after the exact reduction"""
-    x = np.asarray(x, np.float32).astype(np.float64)
-    n, K = x.shape[0], x.shape[1] // 4
-    re, im = x[:, :2 * K].reshape(n, 2, K), x[:, 2 * K:].reshape(n, 2, K)
-    c, s = co.twiddles(K, P)
-    c, s = _f32(c), _f32(s)
-    acc = np.zeros((n, P, 2))
-    for k in range(K):
-        acc = _fma(re[:, None, :, k], c[None, :, None, k], acc)
-        acc = _fma(-im[:, None, :, k], s[None, :, None, k], acc)
-    return acc
-
-
 def template32(a, pr, wrong=None):
     a = np.asarray(a, np.float32).astype(np.float64)
     if pr is None:
@@ -180,12 +147,7 @@ def emulate32(curve, a_points, params=None, offsets=None, P=None, wrong=None):
             a_row = a_points[int(offsets[n]):int(offsets[n + 1]) + 1]
         a = template32(a_row, None if params is None else params[n], wrong)
         b = b_all[n][:-1] if wrong == "end point dropped" else b_all[n]
-        mA, mB = np.empty(len(a)), np.full(len(b), np.inf)
-        for i in range(0, len(a), 512):
-            dx, dy = _f32(a[i:i + 512, None, 0] - b[None, :, 0]), _f32(a[i:i + 512, None, 1] - b[None, :, 1])
-            D = _fma(dy, dy, _f32(dx * dx))
-            mA[i:i + 512] = D.min(1)
-            mB = np.minimum(mB, D.min(0))
+        mA, mB = co.minima32(a, b)
         both = mA if wrong == "one direction only" else np.concatenate([mA, mB])
         roots = both if wrong == "squares for roots" else _f32(np.sqrt(both))
         max_h[n] = roots.max()

@@ -26,6 +26,7 @@ The comparison rule.  u = 2^-24, R = max_s (|V_s.x| + |V_s.y|), O = max(|xoffset
 import numpy as np
 
 import curve_oracle as co
+from curve_oracle import _f32, _fma, trace32
 
 U = 2.0 ** -24
 MAX_M = 4096
@@ -142,15 +143,6 @@ def segment_d2(seg, b):
     return ((ap + ln[:, :, None] * n[:, None, :]) ** 2).sum(2)
 
 
-def minima64(a, b, chunk=512):
-    mA, mB = np.empty(len(a)), np.full(len(b), np.inf)
-    for i in range(0, len(a), chunk):
-        D = ((a[i:i + chunk, None, :] - b[None, :, :]) ** 2).sum(2)
-        mA[i:i + chunk] = D.min(1)
-        mB = np.minimum(mB, D.min(0))
-    return mA, mB
-
-
 def plus64(params, curve=None, P=None, max_dist=0.02, distances=True):
     """everything of the contract in float64 and the rule's bounds, as a dict of arrays over the rows.  curve: x [N, 4K] (traced at
     P), points [N, P, 2], or None (segments, keep, counts and dA alone).  A row of more than 4096 outline points has NaN in
@@ -182,7 +174,7 @@ def plus64(params, curve=None, P=None, max_dist=0.02, distances=True):
         loss[n], top[n] = (d2.mean(), cd.mean()), (d2.max(), cd.max())
         far[n] = np.sqrt(((seg[n][:, 0, None, :] - b[None, :, :]) ** 2).sum(2).max())
         if distances and not over[n]:
-            mA, mB = minima64(outline64(seg[n], cnt[n]), b)
+            mA, mB, _ = co.minima64(outline64(seg[n], cnt[n]), b)
             both = np.sqrt(np.concatenate([mA, mB]))
             max_h[n], avg_h[n] = both.max(), both.mean()
     E = 2 * (out["dA"] + dB) + 4 * U * far
@@ -254,15 +246,6 @@ def find_max_dist(params, target, rows=None):
 
 
 # ---- a float32 emulation of the contract's operation order (and deliberately wrong variants of it), for the CPU tests ----
-def _f32(v):
-    return np.asarray(v, np.float64).astype(np.float32).astype(np.float64)
-
-
-def _fma(a, b, c):
-    """fp32 fma of fp32 values held in float64: the product is exact in float64, the sum is rounded to 53 bits and then to 24"""
-    return _f32(a * b + c)
-
-
 WRONG = ("R transposed", "offset before rotation", "clamp from the clamped partner", "projection unclamped", "dropped segment kept",
          "duplicate vertex dropped", "mean over 12 corners", "corner term rooted")
 C32 = float(np.float32(0.01))
@@ -306,7 +289,6 @@ def counts32(W, kept, max_dist, half_up=False):
 
 def emulate32(params, curve=None, P=None, max_dist=0.02, wrong=None, half_up=False):
     """dict of segments, keep, counts, loss, max_h, avg_h as the contract's fp32 operation order gives them; wrong: one of WRONG"""
-    from hausdorff_oracle import trace32
     assert wrong is None or wrong in WRONG
     params = np.asarray(params, np.float32).reshape(-1, 9)
     N = params.shape[0]
@@ -364,12 +346,7 @@ def emulate32(params, curve=None, P=None, max_dist=0.02, wrong=None, half_up=Fal
             a = _fma(t[:, None], W1[s][None, :], _f32(_f32(1.0 - t)[:, None] * W[s][None, :]))
             pts.append(a[:-1] if wrong == "duplicate vertex dropped" else a)
         a = np.concatenate(pts)
-        mA, mB = np.empty(len(a)), np.full(len(b), np.inf)
-        for i in range(0, len(a), 512):
-            ddx, ddy = _f32(a[i:i + 512, None, 0] - b[None, :, 0]), _f32(a[i:i + 512, None, 1] - b[None, :, 1])
-            D = _fma(ddy, ddy, _f32(ddx * ddx))
-            mA[i:i + 512] = D.min(1)
-            mB = np.minimum(mB, D.min(0))
+        mA, mB = co.minima32(a, b)
         roots = _f32(np.sqrt(np.concatenate([mA, mB])))
         out["max_h"][n], out["avg_h"][n] = np.float32(roots.max()), np.float32(roots.sum() / len(roots))
     return out

@@ -1,0 +1,109 @@
+"""The cases of tests/golden/pointset_bits.npz: small launches of hint_hausdorff_run and hint_plus_run whose output bits were
+recorded once (tests/golden/make_pointset_bits.py) and must never move again (tests/test_gpu_pointset_bits.py).  Every operation
+of both kernels is a correctly rounded intrinsic in an order that include/hint_amd.h fixes, so a change that only moves code
+changes no bit.
+
+Every case has 5 rows on 2 workgroups: a workgroup takes 2-3 rows in turn and reuses its LDS between them.  The inputs come from
+the oracles' seeded generators; the fixture keeps a sha256 of each, so that a drift of a generator is reported as such and not as
+a change of the kernels.  Hausdorff (K, P, M): every K of 1, 5, 25; every P of 2, 100, 256, 257 (the step from one curve point a
+thread to two), 1000, 1024; every M of 1, 1023, 1024, 1025 (around one LDS tile), 4096, the ragged case all five at once.  Plus:
+the same K and P; max_dist steers the largest row's outline to one tile to the point, to one tile and two points (an outline's
+edges come in pairs of equal count, so its size is always even: 1025 does not exist), to more than three tiles and to the most a
+row may have, next to a row that is past it."""
+import hashlib
+
+import numpy as np
+
+import curve_oracle as co
+import hausdorff_oracle as ho
+import plus_oracle as po
+
+ROWS, GROUPS = 5, 2
+RAGGED = (1, 1023, 1024, 1025, 4096)
+# name -> (seed, K (0: given points), P, M or None (points alone), mode)
+HAUSDORFF = {
+    "hd_k1_p2_m1": (1, 1, 2, 1, "shared"),
+    "hd_k5_p100_m1023_params": (2, 5, 100, 1023, "params"),
+    "hd_k25_p256_m1024": (3, 25, 256, 1024, "shared"),
+    "hd_k5_p257_ragged": (4, 5, 257, sum(RAGGED), "ragged"),
+    "hd_k25_p1000_m4096_params": (5, 25, 1000, 4096, "params"),
+    "hd_given_p1024_m1025": (6, 0, 1024, 1025, "shared"),
+    "hd_k25_p1024_points_alone": (7, 25, 1024, None, "points"),
+}
+PLUS_ALL = ("segments", "keep", "counts", "loss", "max_h", "avg_h")
+# name -> (seed, K, P, the outline size of the largest row that is served, rows of zero width, the row past 4096 points, outputs)
+PLUS = {
+    "pl_k1_p2_m1024": (11, 1, 2, 1024, {}, None, PLUS_ALL),
+    "pl_k5_p100_m1026": (12, 5, 100, 1026, {}, None, PLUS_ALL),
+    "pl_k25_p256_m3500": (13, 25, 256, 3500, {}, None, PLUS_ALL),
+    "pl_k5_p257_zero_width": (14, 5, 257, 2348, {1: (2,), 3: (2, 3)}, None, PLUS_ALL),
+    "pl_k25_p1000_m4096_one_row_over": (15, 25, 1000, 4096, {}, 2, PLUS_ALL),
+    "pl_k5_p1024_m1024": (16, 5, 1024, 1024, {}, None, PLUS_ALL),
+    "pl_k25_p100_loss_alone": (17, 25, 100, 1026, {}, None, ("loss",)),
+}
+HASHED = ("points", "segments")          # outputs the fixture keeps as a sha256
+
+
+def sha(a):
+    a = np.ascontiguousarray(a)
+    return hashlib.sha256(str((a.dtype.str, a.shape)).encode() + a.tobytes()).hexdigest()
+
+
+def inputs(name):
+    """the case's input arrays (a dict; max_dist, where there is one, as a 0-d fp32 array)"""
+    if name in HAUSDORFF:
+        seed, K, P, M, mode = HAUSDORFF[name]
+        x = co.gauss(100 + seed, ROWS, K or 5)
+        inp = dict(curve=x if K else co.points64(x, P).astype(np.float32))
+        if mode == "ragged":
+            inp["template"] = np.concatenate([ho.lens_template(m) for m in RAGGED])
+            inp["offsets"] = np.concatenate([[0], np.cumsum(RAGGED)]).astype(np.int64)
+        elif mode != "points":
+            inp["template"] = ho.lens_template(M)
+        if mode == "params":
+            inp["params"] = ho.golden_params(seed, ROWS)
+        return inp
+    seed, K, P, size, zero, over, _ = PLUS[name]
+    pr = po.draw_params(200 + seed, ROWS, (), zero=zero)
+    if over is not None:
+        pr[over, :2] = 40.0                                  # an outline of twice the served rows' points
+    served = [r for r in np.argsort(-po.quotients(pr, 1.0).sum(1)) if r != over]      # the largest first: none goes past `size`
+    md, _ = po.find_max_dist(pr, size, rows=served)
+    return dict(params=pr, curve=(co.gauss(300 + seed, ROWS, K) * np.float32(3)).astype(np.float32), max_dist=np.float32(md))
+
+
+def check_plus_rows(name, inp):
+    """the CPU condition: every row is served (counts >= 0) but the one meant not to be, and the largest served outline has the
+    size the case is named for"""
+    _, _, _, size, zero, over, _ = PLUS[name]
+    ref = po.plus64(inp["params"], max_dist=float(inp["max_dist"]))
+    unserved = np.nonzero((ref["counts"] < 0).any(1))[0].tolist()
+    assert unserved == ([] if over is None else [over]), (name, unserved)
+    assert ref["M"][[r for r in range(ROWS) if r != over]].max() == size, (name, ref["M"])
+    for r, cols in zero.items():
+        assert (ref["counts"][r] == 0).sum() == 2 * len(cols), (name, r, ref["counts"][r])
+
+
+def run(name, inp):
+    """the case on the device: a dict of its outputs as numpy arrays"""
+    import torch
+    from hint_amd import curves
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0")      # noqa: E731
+    if name in HAUSDORFF:
+        _, K, P, M, mode = HAUSDORFF[name]
+        t = lambda k: dev(inp[k]) if k in inp else None                          # noqa: E731
+        out = curves._hd_run(dev(inp["curve"]), K, P, t("template"), t("offsets"), t("params"), want_h=M is not None,
+                             want_chamfer=M is not None, want_points=K > 0, max_groups=GROUPS)
+        out = dict(zip(("max_h", "avg_h", "chamfer", "points"), out))
+    else:
+        _, K, P, _, _, _, want = PLUS[name]
+        out = curves._plus_run(dev(inp["params"]), dev(inp["curve"]), K, P, float(inp["max_dist"]), want, GROUPS)
+    return {k: v.cpu().numpy() for k, v in out.items() if v is not None}
+
+
+def record(name, inp, out):
+    """what the fixture keeps of a case, {key: array}: a sha256 of every input array (max_dist itself), the outputs raw or hashed"""
+    rec = {f"{name}/in/{k}": v if k == "max_dist" else np.array(sha(v)) for k, v in inp.items()}
+    for k, v in out.items():
+        rec[f"{name}/out/{k}"] = np.array(sha(v)) if k in HASHED else v
+    return rec

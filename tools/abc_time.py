@@ -15,19 +15,15 @@ quartiles and extremes are printed and written.
 import argparse
 import json
 import os
-import statistics
 import subprocess
 import sys
+
+from _timing import stats
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SIZES = (1 << 20, 1 << 24, 10 ** 8)
 NY, K = 2, 4002
 LIMIT_S = 240           # per size
-
-
-def stats(us):
-    q = statistics.quantiles(us, n=4)
-    return {"median_us": statistics.median(us), "q1_us": q[0], "q3_us": q[2], "min_us": min(us), "max_us": max(us), "reps": len(us)}
 
 
 def one_size(n, reps, warmup):

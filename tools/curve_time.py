@@ -17,20 +17,16 @@ import argparse
 import json
 import math
 import os
-import statistics
 import subprocess
 import sys
+
+from _timing import commit_of_tree, stats
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SIZES = ((4000, 30), (1 << 20, 10), (1 << 24, 3))          # (rows, repetitions)
 K, P = 5, 100
 CHUNK = 1 << 16         # rows of the torch formulation's [chunk, P, P] matrix: 2.6 GB in fp32
 LIMIT_S = 300           # per size
-
-
-def stats(us):
-    q = statistics.quantiles(us, n=4) if len(us) > 1 else [us[0]] * 3
-    return {"median_us": statistics.median(us), "q1_us": q[0], "q3_us": q[2], "min_us": min(us), "max_us": max(us), "reps": len(us)}
 
 
 def one_size(n, reps, warmup):
@@ -94,13 +90,6 @@ def one_size(n, reps, warmup):
     row["device"] = torch.cuda.get_device_name(0)
     row["build"] = lib.hint_build_info().decode()
     return row
-
-
-def commit_of_tree():
-    try:
-        return subprocess.run(["git", "-C", ROOT, "rev-parse", "HEAD"], capture_output=True, text=True, check=True).stdout.strip()
-    except (OSError, subprocess.CalledProcessError):
-        return "unknown"
 
 
 def main():

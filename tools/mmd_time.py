@@ -10,10 +10,11 @@ repetition is bracketed by HIP events on the current stream, and the medians, qu
 import argparse
 import json
 import os
-import statistics
 import sys
 
 import torch
+
+from _timing import stats
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -44,11 +45,6 @@ def timed(fn):
     b.record()
     b.synchronize()
     return a.elapsed_time(b) * 1e3, out          # microseconds
-
-
-def stats(us):
-    q = statistics.quantiles(us, n=4)
-    return {"median_us": statistics.median(us), "q1_us": q[0], "q3_us": q[2], "min_us": min(us), "max_us": max(us), "reps": len(us)}
 
 
 def main():

@@ -22,21 +22,17 @@ import argparse
 import json
 import math
 import os
-import statistics
 import subprocess
 import sys
 import time
+
+from _timing import commit_of_tree, stats
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SIZES = ((1000, 20, 3), (1 << 16, 5, 1))          # (rows, repetitions of the device routes, of the host route)
 K, P, P_FIT, MAX_DIST = 25, 1000, 100, 0.02
 CHUNK = 64              # rows of the torch formulation's [chunk, 12 * longest edge, P] matrix: under 1 GiB in fp32
 LIMIT_S = 420           # per size
-
-
-def stats(us):
-    q = statistics.quantiles(us, n=4) if len(us) > 1 else [us[0]] * 3
-    return {"median_us": statistics.median(us), "q1_us": q[0], "q3_us": q[2], "min_us": min(us), "max_us": max(us), "reps": len(us)}
 
 
 def one_size(n, reps, host_reps, warmup):
@@ -182,13 +178,6 @@ def one_size(n, reps, host_reps, warmup):
     row["device"] = torch.cuda.get_device_name(0)
     row["build"] = lib.hint_build_info().decode()
     return row
-
-
-def commit_of_tree():
-    try:
-        return subprocess.run(["git", "-C", ROOT, "rev-parse", "HEAD"], capture_output=True, text=True, check=True).stdout.strip()
-    except (OSError, subprocess.CalledProcessError):
-        return "unknown"
 
 
 def main():

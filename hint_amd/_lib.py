@@ -65,6 +65,16 @@ class PlusDesc(C.Structure):
                 ("max_h", C.c_void_p), ("avg_h", C.c_void_p)]
 
 
+class LensFitDesc(C.Structure):
+    """mirror of `hint_lensfit_desc` (include/hint_amd.h)"""
+    _fields_ = [("x", C.c_void_p), ("b_points", C.c_void_p), ("n_rows", C.c_int64), ("n_coeffs", C.c_int32),
+                ("n_points", C.c_int32), ("a_points", C.c_void_p), ("n_template", C.c_int64), ("starts", C.c_void_p),
+                ("n_starts", C.c_int32), ("n_steps", C.c_int32), ("lr", C.c_double), ("angle_lr", C.c_double),
+                ("gamma", C.c_double), ("momentum", C.c_double), ("weight", C.c_double), ("params", C.c_void_p),
+                ("loss", C.c_void_p), ("best", C.c_void_p), ("all_params", C.c_void_p), ("all_loss", C.c_void_p),
+                ("grad", C.c_void_p), ("trace", C.c_void_p), ("max_groups", C.c_int32)]
+
+
 _lib = None
 
 _PROTOS = {
@@ -147,6 +157,9 @@ _PROTOS = {
     "hint_plus_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32]),
     "hint_plus_run": (C.c_int, [C.POINTER(PlusDesc), C.c_void_p]),
     "hint_plus_geometry": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
+    "hint_lensfit_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32]),
+    "hint_lensfit_run": (C.c_int, [C.POINTER(LensFitDesc), C.c_void_p]),
+    "hint_lensfit_geometry": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
 }
 
 

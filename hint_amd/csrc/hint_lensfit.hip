@@ -1,0 +1,293 @@
+// The lens-shape fit of a curve (gfx950): the fit loss, its gradient and the whole SGD loop over several starts in one launch.
+//
+// Reference being replaced (read-only): run_experiments.py:150-159 calls, per row in a Python loop, fit_lens_shape_to_points
+// (best_shape_fit.py:230-261): two starts of 100 autograd steps of torch's SGD (momentum 0.2, StepLR) on points_to_lens_loss
+// (best_shape_fit.py:203-209) over lens_points_from_params (best_shape_fit.py:195-199), a [P, M] distance matrix per step.
+// The contract - placement, the fp32 order of every operation, the selected pairs, the association of the double sums, the
+// update rule and what a start and a row return - is stated in include/hint_amd.h (hint_lensfit_desc).
+//
+// hint_lensfit_kernel: the shape of hint_hausdorff_kernel - a persistent grid of G workgroups of 256 threads; workgroup w takes
+// rows w, w + G, ... one at a time and runs the row's S starts one after the other, so the selection needs no second launch and
+// no traffic between workgroups.  Built from hint_pointset.hpp (the trace, the own points, the reduction) and its arg-min walk:
+//   - once per workgroup: the P - 1 twiddles and the untransformed prototype (M <= 1024: one tile) to LDS;
+//   - per row: the coefficients; B traced or loaded into LDS; each thread holds its <= 4 B points in registers;
+//   - per step: thread 0 stages cs, sn and the parameters (not inlined, as hd_stage_params); every thread places its <= 4
+//     prototype points and writes them to LDS; pass 1 walks B for them, pass 2 walks the placed prototype for the thread's B
+//     points, both keeping the index of the minimum; the selected pairs' terms are recomputed in fp32 (q from the prototype in
+//     LDS: the same operations, the same bits) and added in double; ten double sums - the loss term and the four gradient terms
+//     of either side, kept apart because the weights are applied after the sums - go through ps_block_reduce; thread 0 forms the
+//     loss and the gradient, writes the trace and takes the step.  Three barriers a step.
+// The state of a fit (parameters, momentum buffer, the two learning rates) lives in LDS and is set afresh for every start.
+// Nothing is carried from row to row and no output is read back.  No float atomics, no counters, no workspace.
+// Untuned defaults (a workgroup per row although at P = 100, M = 130 only 130 threads hold a point; starts in sequence): DESIGN
+// section 16.
+#include "hint_pointset.hpp"
+
+namespace hint {
+constexpr int LF_MAX_WG = 1024;                 // the grid cap: 256 CUs x 4 workgroups (32.8 KiB of LDS each)
+constexpr int LF_MAX_M = PS_TILE, LF_MAX_S = 16, LF_MAX_STEPS = 1024;
+}
+
+// a fit's state in LDS
+struct lf_state {
+    float p[4], buf[4];                          // x, y, scale, angle; the momentum buffer
+    float cs, sn;
+    double lr, alr;                              // the learning rates before their fp32 rounding
+    float best_p[4], best_l;
+    int best;
+};
+
+// cs, sn of the state's angle, by one thread.  Not inlined, as hd_stage_params and for the same reason: the double-precision
+// sincos holds some thirty registers of constants
+__device__ __noinline__ void lf_stage_params(lf_state* st) {
+    double sn, cs;
+    sincos((double)st->p[3], &sn, &cs);
+    st->cs = (float)cs;
+    st->sn = (float)sn;
+}
+
+__device__ __forceinline__ float2 lf_rotate(float2 a, float cs, float sn) {
+    return make_float2(__fmaf_rn(-a.y, sn, __fmul_rn(a.x, cs)), __fmaf_rn(a.y, cs, __fmul_rn(a.x, sn)));
+}
+
+// the terms of a selected pair (e = A_i - B_j, q = the rotated prototype point) onto five double sums
+__device__ __forceinline__ void lf_add_pair(double (&s)[10], int o, float d, float ex, float ey, float2 q) {
+    s[o] += (double)d;
+    s[o + 1] += (double)ex;
+    s[o + 2] += (double)ey;
+    s[o + 3] += (double)__fmaf_rn(ey, q.y, __fmul_rn(ex, q.x));
+    s[o + 4] += (double)__fmaf_rn(ey, q.x, -__fmul_rn(ex, q.y));
+}
+
+__global__ __launch_bounds__(256) void hint_lensfit_kernel(const float* __restrict__ x, const float* __restrict__ b_points, int n,
+                                                           int K, int P, const float* __restrict__ a_points, int M,
+                                                           const float* __restrict__ starts, int S, int n_steps, double lr0,
+                                                           double alr0, double gamma, float momentum, double weight,
+                                                           float* __restrict__ params, float* __restrict__ loss,
+                                                           int* __restrict__ best, float* __restrict__ all_params,
+                                                           float* __restrict__ all_loss, float* __restrict__ grad,
+                                                           float* __restrict__ trace) {
+    using namespace hint;
+    __shared__ float2 tw[PS_MAX_P];                          // [r], r < P - 1
+    __shared__ float2 Bp[PS_MAX_P];
+    __shared__ float2 A0[LF_MAX_M];                          // the prototype as given
+    __shared__ float2 Ap[LF_MAX_M];                          // ... placed by the step's parameters
+    __shared__ float coef[4 * PS_MAX_K + 4];
+    __shared__ lf_state st;
+    __shared__ double red[PS_WAVES][10];
+    __shared__ float redm[PS_WAVES];
+    const int t = threadIdx.x, C = 4 * K;
+    const bool traced = x != nullptr;
+    const int ncA = (M + PS_THREADS - 1) / PS_THREADS, ncB = (P + PS_THREADS - 1) / PS_THREADS;
+    const int evals = n_steps > 0 ? n_steps : 1;             // n_steps = 0: one evaluation, no update
+    if (traced) ps_twiddles(tw, P, t);
+    for (int i = t; i < M; i += PS_THREADS) {
+        float2 a;                                            // (4-byte aligned: one 8-byte load all the same)
+        __builtin_memcpy(&a, a_points + 2 * (size_t)i, sizeof(a));
+        A0[i] = a;
+    }
+    for (int row = blockIdx.x; row < n; row += gridDim.x) {                  // (n <= 2^30)
+        if (traced && t < C) coef[t] = x[(size_t)row * C + t];
+        __syncthreads();                                     // coef (and, the first time, tw and A0) are whole
+        ps_stage_curve(Bp, tw, coef, traced, b_points, nullptr, (size_t)row, K, P, t);
+        __syncthreads();                                     // Bp is whole
+        float bx[PS_PER], by[PS_PER];
+        ps_own_points(Bp, P, t, bx, by);
+#pragma unroll 1
+        for (int s = 0; s < S; ++s) {
+            const size_t rs = (size_t)row * S + s;
+            if (t == 0) {                                    // the fit starts afresh
+                for (int k = 0; k < 4; ++k) {
+                    st.p[k] = starts[4 * rs + k];
+                    st.buf[k] = 0.f;
+                }
+                st.lr = lr0;
+                st.alr = alr0;
+                lf_stage_params(&st);
+            }
+            float L = 0.f, g[4] = {0.f, 0.f, 0.f, 0.f};      // of the last evaluation (thread 0)
+#pragma unroll 1
+            for (int it = 0; it < evals; ++it) {
+                __syncthreads();                             // st is staged; the walks of the step before are done with Ap
+                const float cs = st.cs, sn = st.sn, sc = st.p[2], xo = st.p[0], yo = st.p[1];
+                // ---- place: this thread's prototype points; a slot past the end repeats the last point and is not counted ----
+                float ax[PS_PER], ay[PS_PER];
+#pragma unroll
+                for (int c = 0; c < PS_PER; ++c) {
+                    const int i = t + PS_THREADS * c;
+                    const float2 q = lf_rotate(A0[i < M ? i : M - 1], cs, sn);
+                    ax[c] = __fmaf_rn(q.x, sc, xo);
+                    ay[c] = __fmaf_rn(q.y, sc, yo);
+                    if (i < M) Ap[i] = make_float2(ax[c], ay[c]);
+                }
+                __syncthreads();                             // Ap is whole
+                double sm[10];
+#pragma unroll
+                for (int k = 0; k < 10; ++k) sm[k] = 0.0;
+                {   // ---- pass 1: mA of this thread's A points, and where ----
+                    float m[PS_PER];
+                    int at[PS_PER];
+#pragma unroll
+                    for (int c = 0; c < PS_PER; ++c) {
+                        m[c] = INFINITY;
+                        at[c] = 0;
+                    }
+                    ps_scan_arg_n(ncA, Bp, P, ax, ay, m, at);
+#pragma unroll
+                    for (int c = 0; c < PS_PER; ++c) {
+                        const int i = t + PS_THREADS * c;
+                        if (i < M) {                         // (then c < ncA)
+                            const float2 b = Bp[at[c]];
+                            const float ex = __fsub_rn(ax[c], b.x), ey = __fsub_rn(ay[c], b.y);
+                            lf_add_pair(sm, 5, __fmaf_rn(ey, ey, __fmul_rn(ex, ex)), ex, ey, lf_rotate(A0[i], cs, sn));
+                        }
+                    }
+                }
+                {   // ---- pass 2: mB of this thread's B points, and where ----
+                    float m[PS_PER];
+                    int at[PS_PER];
+#pragma unroll
+                    for (int c = 0; c < PS_PER; ++c) {
+                        m[c] = INFINITY;
+                        at[c] = 0;
+                    }
+                    ps_scan_arg_n(ncB, Ap, M, bx, by, m, at);
+#pragma unroll
+                    for (int c = 0; c < PS_PER; ++c) {
+                        if (t + PS_THREADS * c < P) {        // (then c < ncB)
+                            const float2 a = Ap[at[c]];
+                            const float ex = __fsub_rn(a.x, bx[c]), ey = __fsub_rn(a.y, by[c]);
+                            lf_add_pair(sm, 0, __fmaf_rn(ey, ey, __fmul_rn(ex, ex)), ex, ey, lf_rotate(A0[at[c]], cs, sn));
+                        }
+                    }
+                }
+                float mx = 0.f;
+                ps_block_reduce(sm, mx, red, redm, t);       // (its barrier ends the walks of this step)
+                if (t == 0) {
+                    // sm[0..4]: over the P pairs of B; sm[5..9]: over the M pairs of A - loss term, x, y, scale, angle terms
+                    const double dP = (double)P, dM = (double)M;
+                    L = (float)(sm[0] / dP + weight * (sm[5] / dM));
+                    g[0] = (float)(2.0 * (sm[1] / dP + weight * (sm[6] / dM)));
+                    g[1] = (float)(2.0 * (sm[2] / dP + weight * (sm[7] / dM)));
+                    g[2] = (float)(2.0 * (sm[3] / dP + weight * (sm[8] / dM)));
+                    g[3] = (float)(2.0 * (double)sc * (sm[4] / dP + weight * (sm[9] / dM)));
+                    if (n_steps > 0) {
+                        if (trace) {
+                            float* tr = trace + 9 * (rs * (size_t)n_steps + it);
+                            for (int k = 0; k < 4; ++k) {
+                                tr[k] = st.p[k];
+                                tr[5 + k] = g[k];
+                            }
+                            tr[4] = L;
+                        }
+                        const float lr = (float)st.lr, alr = (float)st.alr;
+                        for (int k = 0; k < 4; ++k) {
+                            const float b = it == 0 ? g[k] : __fmaf_rn(momentum, st.buf[k], g[k]);
+                            st.buf[k] = b;
+                            st.p[k] = __fmaf_rn(-(k == 3 ? alr : lr), b, st.p[k]);
+                        }
+                        st.lr *= gamma;
+                        st.alr *= gamma;
+                        if (it + 1 < evals) lf_stage_params(&st);
+                    }
+                }
+            }
+            if (t == 0) {                                    // the start's result, and the row's best so far
+                if (all_params)
+                    for (int k = 0; k < 4; ++k) all_params[4 * rs + k] = st.p[k];
+                if (all_loss) all_loss[rs] = L;
+                if (grad)
+                    for (int k = 0; k < 4; ++k) grad[4 * rs + k] = g[k];
+                if (s == 0 || L < st.best_l || (st.best_l != st.best_l && L == L)) {     // (a NaN compares as larger)
+                    for (int k = 0; k < 4; ++k) st.best_p[k] = st.p[k];
+                    st.best_l = L;
+                    st.best = s;
+                }
+            }
+        }
+        if (t == 0) {
+            if (params)
+                for (int k = 0; k < 4; ++k) params[4 * (size_t)row + k] = st.best_p[k];
+            if (loss) loss[row] = st.best_l;
+            if (best) best[row] = st.best;
+        }
+        // (the next row's first barrier comes before anything of this row in LDS is overwritten but coef, which no one reads now)
+    }
+}
+
+// ---- the C ABI ----
+using namespace hint;
+
+static int lf_check_sizes(const char* who, int64_t n_rows, int32_t n_coeffs, int32_t n_points, int64_t n_template, int32_t n_starts,
+                          int32_t n_steps, bool traced) {
+    if (ps_check_sizes(who, n_rows, n_coeffs, n_points, traced)) return 1;
+    if (n_template < 1 || n_template > LF_MAX_M)
+        return fail("%s: n_template must be 1..%d (got %lld)", who, LF_MAX_M, (long long)n_template);
+    if (n_starts < 1 || n_starts > LF_MAX_S) return fail("%s: n_starts must be 1..%d (got %d)", who, LF_MAX_S, n_starts);
+    if (n_steps < 0 || n_steps > LF_MAX_STEPS) return fail("%s: n_steps must be 0..%d (got %d)", who, LF_MAX_STEPS, n_steps);
+    return 0;
+}
+
+static int lf_check_rate(const char* who, const char* name, double v) {
+    if (!std::isfinite(v) || v < 0.0) return fail("%s: %s must be finite and >= 0 (got %g)", who, name, v);
+    return 0;
+}
+
+extern "C" {
+
+size_t hint_lensfit_workspace_bytes(int64_t n_rows, int32_t n_coeffs, int32_t n_points, int64_t n_template, int32_t n_starts,
+                                    int32_t n_steps) {
+    // n_coeffs = 0 stands for the given-points source, which has no coefficients
+    if (lf_check_sizes("hint_lensfit_workspace_bytes", n_rows, n_coeffs, n_points, n_template, n_starts, n_steps, n_coeffs != 0))
+        return 0;
+    last_error_ref().clear();
+    return 0;                                                // the kernel needs none
+}
+
+int64_t hint_lensfit_geometry(int64_t n_rows, int32_t n_points, int32_t field) {
+    if (ps_check_sizes("hint_lensfit_geometry", n_rows, 1, n_points, false, true)) return -1;
+    if (field < 0 || field > 4) {
+        fail("hint_lensfit_geometry: no field %d (0 workgroups, 1 rows per workgroup at a time, 2 prototype points per LDS tile, "
+             "3 the grid cap, 4 the most prototype points)", field);
+        return -1;
+    }
+    const int64_t out[5] = {ps_grid(n_rows, 0, LF_MAX_WG), 1, PS_TILE, LF_MAX_WG, LF_MAX_M};
+    return out[field];
+}
+
+int hint_lensfit_run(const hint_lensfit_desc* desc, void* stream) {
+    const char* who = "hint_lensfit_run";
+    if (!desc) return fail("%s: desc is null", who);
+    if (!desc->a_points) return fail("%s: a_points is null", who);
+    if (!desc->starts) return fail("%s: starts is null", who);
+    if (desc->x && desc->b_points) return fail("%s: both x and b_points are given (the curve has one source)", who);
+    if (!desc->x && !desc->b_points) return fail("%s: x and b_points are both null (the curve needs a source)", who);
+    if (!desc->params && !desc->loss && !desc->best && !desc->all_params && !desc->all_loss && !desc->grad && !desc->trace)
+        return fail("%s: no output requested (params, loss, best, all_params, all_loss, grad and trace are all null)", who);
+    if (lf_check_sizes(who, desc->n_rows, desc->n_coeffs, desc->n_points, desc->n_template, desc->n_starts, desc->n_steps,
+                       desc->x != nullptr))
+        return 1;
+    if (desc->trace && desc->n_steps == 0) return fail("%s: trace holds a record per step, and n_steps is 0", who);
+    if (lf_check_rate(who, "lr", desc->lr) || lf_check_rate(who, "angle_lr", desc->angle_lr) ||
+        lf_check_rate(who, "gamma", desc->gamma) || lf_check_rate(who, "momentum", desc->momentum))
+        return 1;
+    if (!std::isfinite(desc->weight)) return fail("%s: weight must be finite (got %g)", who, desc->weight);
+    if (desc->max_groups < 0) return fail("%s: max_groups must be >= 0 (got %d)", who, desc->max_groups);
+    if (misaligned(who, "x", desc->x, 3) || misaligned(who, "b_points", desc->b_points, 3) ||
+        misaligned(who, "a_points", desc->a_points, 3) || misaligned(who, "starts", desc->starts, 3) ||
+        misaligned(who, "params", desc->params, 3) || misaligned(who, "loss", desc->loss, 3) ||
+        misaligned(who, "best", desc->best, 3) || misaligned(who, "all_params", desc->all_params, 3) ||
+        misaligned(who, "all_loss", desc->all_loss, 3) || misaligned(who, "grad", desc->grad, 3) ||
+        misaligned(who, "trace", desc->trace, 3))
+        return 1;
+    const int grid = ps_grid(desc->n_rows, desc->max_groups, LF_MAX_WG);
+    hipLaunchKernelGGL(hint_lensfit_kernel, dim3(grid), dim3(PS_THREADS), 0, (hipStream_t)stream, desc->x, desc->b_points,
+                       (int)desc->n_rows, desc->x ? desc->n_coeffs : 1, desc->n_points, desc->a_points, (int)desc->n_template,
+                       desc->starts, desc->n_starts, desc->n_steps, desc->lr, desc->angle_lr, desc->gamma, (float)desc->momentum,
+                       desc->weight, desc->params, desc->loss, desc->best, desc->all_params, desc->all_loss, desc->grad,
+                       desc->trace);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+}  // extern "C"

@@ -232,3 +232,33 @@ __device__ __forceinline__ void ps_block_reduce(double (&s)[NS], float& mx, doub
         }
     }
 }
+
+// ps_scan that also says where: the minimum is replaced only by a strictly smaller D, so among equal D the lowest index of src
+// stays (and a NaN never enters); at[c] starts at 0 and is always an index of src.  (hint_lensfit.hip recomputes the selected
+// pair's difference from it for the gradient.)
+template <int NC>
+__device__ __forceinline__ void ps_scan_arg(const float2* src, int n, const float (&px)[hint::PS_PER], const float (&py)[hint::PS_PER],
+                                            float (&m)[hint::PS_PER], int (&at)[hint::PS_PER]) {
+#pragma unroll 4
+    for (int j = 0; j < n; ++j) {
+        const float2 q = src[j];
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+            const float dx = __fsub_rn(px[c], q.x), dy = __fsub_rn(py[c], q.y);
+            const float d = __fmaf_rn(dy, dy, __fmul_rn(dx, dx));
+            const bool lt = d < m[c];
+            m[c] = lt ? d : m[c];
+            at[c] = lt ? j : at[c];
+        }
+    }
+}
+
+__device__ __forceinline__ void ps_scan_arg_n(int nc, const float2* src, int n, const float (&px)[hint::PS_PER],
+                                              const float (&py)[hint::PS_PER], float (&m)[hint::PS_PER], int (&at)[hint::PS_PER]) {
+    switch (nc) {                                            // (nc is the same for the whole workgroup)
+        case 1: ps_scan_arg<1>(src, n, px, py, m, at); break;
+        case 2: ps_scan_arg<2>(src, n, px, py, m, at); break;
+        case 3: ps_scan_arg<3>(src, n, px, py, m, at); break;
+        default: ps_scan_arg<4>(src, n, px, py, m, at); break;
+    }
+}

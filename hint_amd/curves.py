@@ -1,7 +1,8 @@
 """curve_features / lens_forward_process / target_distances / mean_target_distance: the lens-shape simulator of the reference's
 evaluation loop on the kernel of hint_curve.hip; trace_fourier_curves / hausdorff_distances / chamfer_distances / lens_fit_loss:
 its shape-quality side on the kernel of hint_hausdorff.hip (below, after the simulator); plus_segments / plus_outline_counts /
-plus_fit_terms / plus_fit_loss / plus_hausdorff_distances: the plus shape's side on the kernel of hint_plus.hip (at the end).
+plus_fit_terms / plus_fit_loss / plus_hausdorff_distances: the plus shape's side on the kernel of hint_plus.hip; lens_fit_grad /
+lens_fit_starts / fit_lens_shapes: the lens shape's fit on the kernel of hint_lensfit.hip (at the end).
 
     LensShapeModel.forward_process(x, noise=0.05)                      data.py:127-139 (over trace_fourier_curves, data.py:51-57)
     mean_target_distance(model, y_target, x)                           rejection_sampling.py:99-102, called at :204
@@ -24,7 +25,8 @@ from ._lib import HintAmdError
 
 __all__ = ["curve_features", "lens_forward_process", "target_distances", "mean_target_distance",
            "trace_fourier_curves", "hausdorff_distances", "chamfer_distances", "lens_fit_loss",
-           "plus_segments", "plus_outline_counts", "plus_fit_terms", "plus_fit_loss", "plus_hausdorff_distances"]
+           "plus_segments", "plus_outline_counts", "plus_fit_terms", "plus_fit_loss", "plus_hausdorff_distances",
+           "lens_fit_grad", "lens_fit_starts", "fit_lens_shapes"]
 
 MAX_COEFFS = 25
 MIN_POINTS, MAX_POINTS = 2, 128
@@ -490,3 +492,192 @@ def plus_hausdorff_distances(curve: torch.Tensor, params: torch.Tensor, *, max_d
     curve, k, p, params = _plus_args(curve, params, n_points, who)
     res = _plus_run(params, curve, k, p, max_dist, want=("max_h", "avg_h"))
     return res["max_h"], res["avg_h"]
+
+
+# ---- the lens shape's fit: loss, gradient and the SGD loop over the starts in one launch (hint_lensfit.hip) ----
+#     fit_lens_shape_to_points(points)                                   best_shape_fit.py:230-261, per row at run_experiments.py:150-159
+#     points_to_lens_loss(prototype, points, params, w).backward()       best_shape_fit.py:203-209 (over :195-199)
+# One launch of hint_lensfit_run per call: no [N, S, P, M] tensor, no autograd graph, no per-row host work; the arithmetic, the
+# selected pairs, the order of the sums and the update rule are fixed (include/hint_amd.h).  The plus shape's fit stays on the host.
+MAX_PROTOTYPE_POINTS = 1024
+MAX_STARTS = 16
+MAX_FIT_STEPS = 1024
+FIT_POINTS = 100           # the points a curve given as coefficients is traced at (run_experiments.py:147)
+
+
+def _check_real(v, name: str, who: str, nonneg: bool = True) -> float:
+    if isinstance(v, bool) or not isinstance(v, (int, float)):
+        raise HintAmdError(f"{who}: {name} must be a number (got {type(v).__name__})")
+    v = float(v)
+    if v != v or v in (float("inf"), float("-inf")):
+        raise HintAmdError(f"{who}: {name} must be finite (got {v})")
+    if nonneg and v < 0.0:
+        raise HintAmdError(f"{who}: {name} must be >= 0 (got {v})")
+    return v
+
+
+def _check_steps(v, who: str) -> int:
+    if isinstance(v, bool) or not isinstance(v, int):
+        raise HintAmdError(f"{who}: n_steps must be an int (got {type(v).__name__})")
+    if v < 0 or v > MAX_FIT_STEPS:
+        raise HintAmdError(f"{who}: n_steps must be 0..{MAX_FIT_STEPS} (got {v})")
+    return v
+
+
+def _check_prototype_shape(shape, who: str) -> int:
+    if len(shape) != 2 or shape[1] != 2:
+        raise HintAmdError(f"{who}: prototype must be [points, 2] (got shape {tuple(shape)})")
+    if shape[0] < 1 or shape[0] > MAX_PROTOTYPE_POINTS:
+        raise HintAmdError(f"{who}: prototype must hold 1..{MAX_PROTOTYPE_POINTS} points (got shape {tuple(shape)})")
+    return shape[0]
+
+
+def _check_starts_shape(shape, n_rows: int, who: str) -> int:
+    shape = tuple(shape)
+    if len(shape) != 3 or shape[0] != n_rows or shape[2] != 4 or not 1 <= shape[1] <= MAX_STARTS:
+        raise HintAmdError(f"{who}: starts must have shape [{n_rows}, S, 4] with S 1..{MAX_STARTS}: x, y, scale, angle "
+                           f"(got {shape})")
+    return shape[1]
+
+
+def _fit_args(curve, prototype, who: str):
+    curve, n, k, p = _curve_arg(curve, FIT_POINTS, who)
+    prototype = _check_dev_tensor(prototype, "prototype", who, curve.device)
+    _check_prototype_shape(tuple(prototype.shape), who)
+    return curve, n, k, p, prototype
+
+
+_LF_OUT = dict(params=(lambda n, s, t: (n, 4)), loss=(lambda n, s, t: (n,)), best=(lambda n, s, t: (n,)),
+               all_params=(lambda n, s, t: (n, s, 4)), all_loss=(lambda n, s, t: (n, s)), grad=(lambda n, s, t: (n, s, 4)),
+               trace=(lambda n, s, t: (n, s, t, 9)))
+
+
+def _lf_run(curve: torch.Tensor, k: int, p: int, prototype: torch.Tensor, starts: torch.Tensor, n_steps: int = 0, lr: float = 0.1,
+            angle_lr: float = 0.01, gamma: float = 1.0, momentum: float = 0.0, weight: float = 1.0,
+            want=("params", "loss", "best", "all_params", "all_loss", "grad"), max_groups: int = 0, out=None):
+    """one hint_lensfit_run on checked arguments: a dict of the outputs named in `want` (params [N, 4], loss [N], best [N] int32,
+    all_params [N, S, 4], all_loss [N, S], grad [N, S, 4], trace [N, S, n_steps, 9]).  k = 0: curve is [N, P, 2] points.
+    out: tensors to write into instead of new ones (the tests' guarded buffers)"""
+    lib = _lib.load()
+    n, dev, n_starts = curve.shape[0], curve.device, starts.shape[1]
+    with torch.cuda.device(dev):
+        res = {}
+        for name in want:
+            if out is not None and name in out:
+                res[name] = out[name]
+            else:
+                res[name] = torch.empty(_LF_OUT[name](n, n_starts, n_steps), device=dev,
+                                        dtype=torch.int32 if name == "best" else torch.float32)
+        desc = _lib.LensFitDesc()
+        desc.x, desc.b_points = (curve.data_ptr(), None) if k else (None, curve.data_ptr())
+        desc.n_rows, desc.n_coeffs, desc.n_points = n, k, p
+        desc.a_points, desc.n_template = prototype.data_ptr(), prototype.shape[0]
+        desc.starts, desc.n_starts, desc.n_steps = starts.data_ptr(), n_starts, n_steps
+        desc.lr, desc.angle_lr, desc.gamma, desc.momentum, desc.weight = lr, angle_lr, gamma, momentum, weight
+        for name in _LF_OUT:
+            setattr(desc, name, res[name].data_ptr() if name in res else None)
+        desc.max_groups = max_groups
+        st = lib.hint_lensfit_run(desc, torch.cuda.current_stream(dev).cuda_stream)
+    _lib.check(st, "hint_lensfit_run")
+    return res
+
+
+def lens_fit_grad(curve: torch.Tensor, prototype: torch.Tensor, params: torch.Tensor, lens_fit_weight: float = 1.0):
+    """the reference's points_to_lens_loss(prototype, points, params, lens_fit_weight) and its autograd gradient by the four
+    parameters, for every row: (loss [N], grad [N, 4]) fp32 - one launch, no autograd graph.  curve is [N, 4K] coefficients,
+    traced at 100 points as the fit's points are, or [N, P, 2] points; prototype [M, 2], M <= 1024; params [N, 4], [1, 4] or [4] =
+    x, y, scale, angle.  Where two prototype (or curve) points are equally near, the gradient is the one of the first"""
+    who = "lens_fit_grad"
+    weight = _check_real(lens_fit_weight, "lens_fit_weight", who, nonneg=False)
+    if params is None:
+        raise HintAmdError(f"{who}: params must be a tensor (got None)")
+    curve, n, k, p, prototype = _fit_args(curve, prototype, who)
+    params = _check_dev_tensor(params, "params", who, curve.device)
+    _check_params_shape(tuple(params.shape), n, who)
+    starts = params.reshape(-1, 4).expand(n, 4).reshape(n, 1, 4).contiguous()
+    res = _lf_run(curve, k, p, prototype, starts, 0, weight=weight, want=("all_loss", "grad"))
+    return res["all_loss"].reshape(n), res["grad"].reshape(n, 4)
+
+
+def lens_fit_starts(curve: torch.Tensor) -> torch.Tensor:
+    """[N, 2, 4] fp32: the two starts (x, y, scale, angle) of the reference's fit_lens_shape_to_points for every row, computed on
+    the device - the centre is the mean of the curve's points (a traced curve's repeated end point included), the scale 2, the
+    angle -atan2(dx, dy) of the vector between the two points farthest apart (the first such pair in row-major order) and
+    (angle + pi) mod 2 pi.  curve is [N, 4K] coefficients, traced at 100 points, or [N, P, 2] points (plain torch on the [P, P]
+    distances then, at most 2^24 of them at a time).  A row that holds a value that is not finite gets unspecified starts; no
+    index comes from it and no other row is touched"""
+    who = "lens_fit_starts"
+    curve, n, k, p = _curve_arg(curve, FIT_POINTS, who)
+    if k:
+        f = _run(curve, p)[0]                                                 # (dy, dx) of curve_features' pair
+        pts = _hd_run(curve, k, p, None, want_points=True)[3]
+        dy, dx = f[:, 0], f[:, 1]
+    else:
+        pts = curve
+        # the first maximum of the [P, P] squared distances in row-major order, rows in chunks so that no more than 2^24 of them
+        # exist at a time.  A distance that is not a number counts as -1: the index is then always one of the row's own pairs,
+        # whatever the row holds
+        v = torch.empty(n, 2, dtype=torch.float32, device=curve.device)
+        flat = torch.arange(p * p, device=curve.device)
+        step = max(1, (1 << 24) // (p * p))
+        for a in range(0, n, step):
+            c = pts[a:a + step]
+            ddx, ddy = c[:, :, None, 0] - c[:, None, :, 0], c[:, :, None, 1] - c[:, None, :, 1]
+            d2 = torch.nan_to_num(ddx * ddx + ddy * ddy, nan=-1.0).reshape(c.shape[0], p * p)
+            first = torch.where(d2 == d2.amax(1, keepdim=True), flat, p * p).amin(1).clamp_(max=p * p - 1)
+            rows = torch.arange(c.shape[0], device=curve.device)
+            v[a:a + step] = c[rows, first % p] - c[rows, first // p]
+        dx, dy = v[:, 0], v[:, 1]
+    angle = -torch.atan2(dx, dy)
+    second = torch.remainder(angle + torch.pi, 2 * torch.pi)
+    # the mean of the points as a pairwise tree of elementwise sums (the row count padded to a power of two with zeros): a
+    # row's bits do not depend on the batch, as a library reduction's might
+    width = 1 << (p - 1).bit_length()
+    acc = torch.zeros(n, width, 2, dtype=torch.float32, device=curve.device)
+    acc[:, :p] = pts
+    while width > 1:
+        width //= 2
+        acc = acc[:, :width] + acc[:, width:]
+    centre = acc[:, 0] / p
+    out = torch.empty(n, 2, 4, dtype=torch.float32, device=curve.device)
+    out[:, :, 0:2] = centre[:, None, :]
+    out[:, :, 2] = 2.0
+    out[:, 0, 3] = angle
+    out[:, 1, 3] = second
+    return out
+
+
+def fit_lens_shapes(curve: torch.Tensor, prototype: torch.Tensor, *, starts: Optional[torch.Tensor] = None, n_steps: int = 100,
+                    lr: float = 0.1, angle_lr: float = 0.01, momentum: float = 0.2, gamma: float = 0.1 ** (1 / 100),
+                    lens_fit_weight: float = 1.0, return_all: bool = False, return_trace: bool = False):
+    """the reference's fit_lens_shape_to_points for every row in one launch: from each of the row's starts (lens_fit_starts(curve)
+    unless given, [N, S, 4], S <= 16) n_steps steps of SGD with momentum on the fit loss, the step sizes lr (angle_lr for the
+    angle) times gamma after every step; the start whose last recorded loss is smallest wins.  Returns (params [N, 4] = x, y,
+    scale, angle; loss [N]) and, with return_all or return_trace, a dict as third value: best [N] int32, all_params [N, S, 4],
+    all_loss [N, S] (return_all), trace [N, S, n_steps, 9] = the parameters, the loss and the gradient of every step
+    (return_trace).  curve and prototype as in lens_fit_grad.  The loss is the one of the last step before its update, as the
+    reference records it; n_steps = 0 evaluates the starts"""
+    who = "fit_lens_shapes"
+    n_steps = _check_steps(n_steps, who)
+    lr, angle_lr = _check_real(lr, "lr", who), _check_real(angle_lr, "angle_lr", who)
+    momentum, gamma = _check_real(momentum, "momentum", who), _check_real(gamma, "gamma", who)
+    weight = _check_real(lens_fit_weight, "lens_fit_weight", who, nonneg=False)
+    curve, n, k, p, prototype = _fit_args(curve, prototype, who)
+    if starts is None:
+        starts = lens_fit_starts(curve)
+    else:
+        starts = _check_dev_tensor(starts, "starts", who, curve.device)
+        _check_starts_shape(tuple(starts.shape), n, who)
+    want = ["params", "loss"]
+    if return_all or return_trace:
+        want.append("best")
+    if return_all:
+        want += ["all_params", "all_loss"]
+    if return_trace and n_steps > 0:
+        want.append("trace")
+    res = _lf_run(curve, k, p, prototype, starts, n_steps, lr, angle_lr, gamma, momentum, weight, want=tuple(want))
+    if not (return_all or return_trace):
+        return res["params"], res["loss"]
+    if return_trace and n_steps == 0:
+        res["trace"] = torch.empty(n, starts.shape[1], 0, 9, dtype=torch.float32, device=curve.device)
+    return res["params"], res["loss"], {name: v for name, v in res.items() if name not in ("params", "loss")}

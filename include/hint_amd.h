@@ -647,6 +647,76 @@ size_t hint_plus_workspace_bytes(int64_t n_rows, int32_t n_coeffs, int32_t n_poi
 int hint_plus_run(const hint_plus_desc* desc, void* stream);
 int64_t hint_plus_geometry(int64_t n_rows, int32_t n_points, int32_t field);
 
+/* The lens-shape fit of a curve: the fit loss, its gradient and the whole SGD loop of the reference's fit in one launch
+ * (run_experiments.py:150-159 calls, per row, best_shape_fit.py:230-261 fit_lens_shape_to_points: two starts of 100 autograd steps
+ * of torch's SGD on best_shape_fit.py:203-209 points_to_lens_loss over best_shape_fit.py:195-199 lens_points_from_params).  Per row
+ * n and start s the parameters p = (x, y, scale, angle) begin at starts[n, s] and take n_steps steps; the curve B (as
+ * hint_hausdorff_desc's: traced from x [n_rows, 4 K] by the same rule and the same bits, or given as b_points [n_rows, P, 2]) is
+ * compared with the prototype a_points [M, 2], 1 <= M <= 1024, shared by all rows (no ragged form).  All arithmetic is fp32, each
+ * operation rounded once, unless said otherwise.
+ *   1. evaluation at p.  The prototype is placed as hint_hausdorff_run places its template: cs, sn = sincos in double of the fp32
+ *      angle, rounded to fp32; q = (fma(-a.y, sn, a.x cs), fma(a.y, cs, a.x sn)); A = (fma(q.x, scale, x), fma(q.y, scale, y)).
+ *      e = A_i - B_j, D(i, j) = fma(e.y, e.y, e.x e.x).  mA_i = min_j D, taken at the lowest j among equal D; mB_j = min_i D, taken
+ *      at the lowest i.  (The duplicate B_(P-1) = B_0 of a traced curve is therefore always resolved to j = 0, and both points
+ *      count in the other direction, as in the reference.)  A NaN D is never selected; where nothing is, index 0 is.
+ *   2. loss.  L = sum_j mB_j / P + w (sum_i mA_i / M): the sums and the divisions in double, in the association of
+ *      hint_hausdorff_run's sums (thread 64 v + l over its own points 256 c + 64 v + l, c ascending; a butterfly over the lanes,
+ *      distances 32 .. 1; the four wavefronts in order); L is rounded to fp32.  w = weight.
+ *   3. gradient.  Each selected pair gives, from the recomputed e and q, the fp32 terms (e.x, e.y, fma(e.y, q.y, e.x q.x),
+ *      fma(e.y, q.x, -(e.x q.y))).  Each term is added in double, in the same association, over the P pairs of B (sums SB) and
+ *      over the M pairs of A (sums SA); then, in double, g = 2 (SB / P + w (SA / M)) for x, y and scale and scale times that for
+ *      the angle; g is rounded to fp32.  This is the autograd gradient of points_to_lens_loss wherever the minima are unique.
+ *   4. step i = 0 .. n_steps - 1 (torch's SGD with momentum and dampening 0 under StepLR with step_size 1): evaluate (L_i, g_i) at
+ *      p_i; buf = g_0 at i = 0, else fma(momentum rounded to fp32, buf, g_i); p_(i+1) = fma(-lr_i, buf, p_i), where lr_i is the
+ *      fp32 rounding of a double that starts at lr (at angle_lr for the angle) and is multiplied by gamma after every step.  The
+ *      buffer and the rates start afresh for every start and every row.
+ *   5. a start's result: all_params[n, s] = p_(n_steps); all_loss[n, s] = L_(n_steps - 1), the loss of the last step before its
+ *      update, as the reference records it; grad[n, s] = g_(n_steps - 1).  n_steps = 0 is the evaluation alone: all_loss = L(p_0),
+ *      grad = g(p_0), all_params = p_0.
+ *   6. a row's result: the start with the smallest loss, the first one on a tie, gives params[n], loss[n] and best[n] (int32).  A
+ *      NaN compares as larger; if every start's loss is NaN, start 0 is taken.
+ *   7. trace[n, s, i] = (p_i [4], L_i, g_i [4]), 9 floats a step (n_steps >= 1).
+ *   8. A row's outputs do not depend on n_rows, on where the row stands, on max_groups or on what the outputs held; two runs agree
+ *      bit for bit.  No float atomics, no counters.
+ *   9. A row with non-finite input gives unspecified values, faults nothing and disturbs no other row: every loop bound and every
+ *      index range comes from the descriptor, never from data.
+ *   run              stream-ordered on the current device: one launch, no workspace, no host synchronisation, no allocation
+ *                    (capturable).  Each output may be NULL, not all seven.  max_groups: 0 = the default grid, otherwise the
+ *                    workgroups at most.  Rejects, before any device call and naming the field: a null a_points or starts; both or
+ *                    neither of x and b_points; no output; n_rows outside 1..2^30; with x, n_coeffs even or outside 1..25 (ignored
+ *                    with b_points); n_points outside 2..1024; n_template outside 1..1024; n_starts outside 1..16; n_steps outside
+ *                    0..1024; trace with n_steps = 0; lr, angle_lr, gamma or momentum not finite or negative; weight not finite;
+ *                    max_groups < 0; a pointer that is not 4-byte aligned.
+ *   workspace_bytes  0: no workspace is needed, so the descriptor names none.  For sizes run would reject (n_coeffs = 0 stands
+ *                    for the given source) hint_last_error() says why, otherwise it is left empty.
+ *   geometry         host only, for the default grid: field 0 the workgroups, 1 the rows a workgroup has in flight (one), 2 the
+ *                    prototype points of an LDS tile, 3 the grid cap, 4 the most prototype points.  Workgroup w of G takes rows
+ *                    w, w + G, ... and runs a row's starts one after the other.  -1 on an error.
+ * None of these has a caller's device buffer among its parameters: the buffers are named by the descriptor. */
+typedef struct hint_lensfit_desc {
+    const float* x;                        /* NULL, or [n_rows, 4 n_coeffs] row-major: the traced source */
+    const float* b_points;                 /* NULL, or device float[n_rows, n_points, 2]: the given source */
+    int64_t n_rows;
+    int32_t n_coeffs, n_points;            /* K odd 1..25 (traced source), P 2..1024 */
+    const float* a_points;                 /* device float[n_template, 2]: the prototype */
+    int64_t n_template;                    /* M: 1..1024 */
+    const float* starts;                   /* device float[n_rows, n_starts, 4]: x, y, scale, angle */
+    int32_t n_starts, n_steps;             /* S 1..16; 0..1024 */
+    double lr, angle_lr, gamma, momentum, weight;
+    float* params;                         /* NULL, or device float[n_rows, 4] */
+    float* loss;                           /* NULL, or device float[n_rows] */
+    int32_t* best;                         /* NULL, or device int32[n_rows] */
+    float* all_params;                     /* NULL, or device float[n_rows, n_starts, 4] */
+    float* all_loss;                       /* NULL, or device float[n_rows, n_starts] */
+    float* grad;                           /* NULL, or device float[n_rows, n_starts, 4] */
+    float* trace;                          /* NULL, or device float[n_rows, n_starts, n_steps, 9] */
+    int32_t max_groups;
+} hint_lensfit_desc;
+size_t hint_lensfit_workspace_bytes(int64_t n_rows, int32_t n_coeffs, int32_t n_points, int64_t n_template, int32_t n_starts,
+                                    int32_t n_steps);
+int hint_lensfit_run(const hint_lensfit_desc* desc, void* stream);
+int64_t hint_lensfit_geometry(int64_t n_rows, int32_t n_points, int32_t field);
+
 int hint_abi_version(void);
 const char* hint_last_error(void);
 /* what the library binary was built with and runs with: "libhint_amd abi N, gfx950, HIP x.y.z, clang ..., src <12 hex digits: hash

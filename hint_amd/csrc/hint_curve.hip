@@ -32,7 +32,7 @@
 // the same trip count and each step is one conflict-free 8-byte LDS read for ~12 vector operations, so LDS is not the limit
 // (4 SIMDs x 1 read per ~12 operations against one LDS port), no lane sits idle beyond 2 l > P - 1, and no workgroup barrier
 // stands in the row loop.  Untuned: see DESIGN section 12.
-#include "hint_host.hpp"
+#include "hint_pointset.hpp"
 
 namespace hint {
 
@@ -231,11 +231,11 @@ int hint_curve_run(const hint_curve_desc* desc, void* stream) {
     if (curve_check_sizes("hint_curve_run", desc->n_rows, desc->n_coeffs, desc->n_points)) return 1;
     if (desc->dist && !desc->target) return fail("hint_curve_run: dist needs a target (target is null)");
     if (desc->mean && !desc->target) return fail("hint_curve_run: mean needs a target (target is null)");
-    if (desc->max_groups < 0) return fail("hint_curve_run: max_groups must be >= 0 (got %d)", desc->max_groups);
-    if (!std::isfinite(desc->noise)) return fail("hint_curve_run: noise must be finite");
     const char* who = "hint_curve_run";
-    if (misaligned(who, "x", desc->x, 3) || misaligned(who, "eps", desc->eps, 3) || misaligned(who, "target", desc->target, 3) ||
-        misaligned(who, "y", desc->y, 3) || misaligned(who, "dist", desc->dist, 3) || misaligned(who, "mean", desc->mean, 3))
+    if (ps_check_groups(who, desc->max_groups)) return 1;
+    if (!std::isfinite(desc->noise)) return fail("hint_curve_run: noise must be finite");
+    if (ps_check_aligned(who, {{"x", desc->x, 3}, {"eps", desc->eps, 3}, {"target", desc->target, 3}, {"y", desc->y, 3},
+                               {"dist", desc->dist, 3}, {"mean", desc->mean, 3}}))
         return 1;
     if (desc->mean) {
         if (!desc->workspace) return fail("hint_curve_run: workspace is null (mean needs one)");

@@ -11,13 +11,13 @@
 // mA_i = min_j D, mB_j = min_i D; max_h = sqrt(max of all minima), avg_h = mean of their roots, chamfer = (mean mB, mean mA).
 //
 // hint_hausdorff_kernel: a persistent grid of G workgroups of 256 threads; workgroup w takes rows w, w + G, ... one at a time.  The
-// curve's trace, the two-pass walk over LDS tiles of the other point set and the reductions are hint_pointset.hpp's, shared with
-// hint_plus.hip; this file adds where the template comes from:
+// curve's trace, the placement, the two-pass walk over LDS tiles of the other point set and the reductions are
+// hint_pointset.hpp's, shared with hint_plus.hip and hint_lensfit.hip; this file adds where the template comes from:
 //   - once per workgroup: the P - 1 twiddles in LDS (ps_twiddles);
-//   - per row: the 4K coefficients and the five transform constants go to LDS; B is traced or loaded into LDS (8 KiB) and, if
+//   - per row: the 4K coefficients and the row's pose (ps_stage_pose) go to LDS; B is traced or loaded into LDS (8 KiB) and, if
 //     asked, written to `points` (ps_stage_curve);
-//   - the template passes through LDS in tiles of 1024 points (8 KiB), loaded from a_points and moved by the row's constants on
-//     the way in - the tile filler this kernel hands to ps_two_sided;
+//   - the template passes through LDS in tiles of 1024 points (8 KiB), loaded from a_points and placed by the row's pose
+//     (ps_place) on the way in - the tile filler this kernel hands to ps_two_sided;
 //   - the maximum and the four double sums by ps_block_reduce; thread 0 writes the row's outputs.
 // Nothing is carried from row to row and nothing is read back from global memory, so a row's bits do not depend on the batch, the
 // grid or what any buffer held.  No float atomics, no counters, no workspace.
@@ -28,18 +28,6 @@
 
 namespace hint {
 constexpr int HD_MAX_WG = 1280;                 // the grid cap: 256 CUs x 5 workgroups (88 VGPRs: 5 wavefronts a SIMD)
-}
-
-// the row's transform constants (cs, sn, scale, x, y) to LDS, by one thread.  Not inlined: the double-precision sincos holds some
-// thirty registers of constants, which would otherwise stay live across the whole row loop
-__device__ __noinline__ void hd_stage_params(const float* pr, float* prm) {
-    double sn, cs;
-    sincos((double)pr[3], &sn, &cs);
-    prm[0] = (float)cs;
-    prm[1] = (float)sn;
-    prm[2] = pr[2];
-    prm[3] = pr[0];
-    prm[4] = pr[1];
 }
 
 __global__ __launch_bounds__(256) void hint_hausdorff_kernel(const float* __restrict__ x, const float* __restrict__ b_points,
@@ -53,7 +41,7 @@ __global__ __launch_bounds__(256) void hint_hausdorff_kernel(const float* __rest
     __shared__ float2 Bp[PS_MAX_P];
     __shared__ float2 Ap[PS_TILE];
     __shared__ float coef[4 * PS_MAX_K + 4];
-    __shared__ float prm[8];                                 // cs, sn, scale, x, y
+    __shared__ ps_pose pose;
     __shared__ double red[PS_WAVES][4];
     __shared__ float redm[PS_WAVES];
     const int t = threadIdx.x, C = 4 * K;
@@ -70,7 +58,7 @@ __global__ __launch_bounds__(256) void hint_hausdorff_kernel(const float* __rest
         const bool bad = o0 < 0 || o1 > T || o1 - o0 < 1 || o1 - o0 > PS_MAX_M;
         const int M = bad ? 0 : (int)(o1 - o0);
         if (traced && t < C) coef[t] = x[(size_t)row * C + t];
-        if (with_prm && with_dist && t == 0) hd_stage_params(a_params + 4 * (size_t)row, prm);
+        if (with_prm && with_dist && t == 0) ps_stage_pose(a_params + 4 * (size_t)row, &pose);
         __syncthreads();
         ps_stage_curve(Bp, tw, coef, traced, b_points, points, (size_t)row, K, P, t);
         if (!with_dist) {                                    // points alone: the template is not read
@@ -90,17 +78,13 @@ __global__ __launch_bounds__(256) void hint_hausdorff_kernel(const float* __rest
         float bx[PS_PER], by[PS_PER];
         ps_own_points(Bp, P, t, bx, by);
         ps_part part = ps_two_sided(Ap, Bp, M, P, t, bx, by, [&](int g) {
-            float2 a;                                        // (4-byte aligned: one 8-byte load all the same)
-            __builtin_memcpy(&a, a_points + 2 * (size_t)(o0 + g), sizeof(a));
-            if (with_prm) {
-                const float cs = prm[0], sn = prm[1];
-                const float qx = __fmaf_rn(-a.y, sn, __fmul_rn(a.x, cs)), qy = __fmaf_rn(a.y, cs, __fmul_rn(a.x, sn));
-                a = make_float2(__fmaf_rn(qx, prm[2], prm[3]), __fmaf_rn(qy, prm[2], prm[4]));
-            }
+            float2 a;
+            ps_load_point(a, a_points + 2 * (size_t)(o0 + g));
+            if (with_prm) a = ps_place(a, pose);
             return a;
         });
         double s[4] = {part.a_rt, part.a_sq, part.b_rt, part.b_sq};
-        ps_block_reduce(s, part.mx, red, redm, t);           // (past its barrier the next row may overwrite Bp, Ap, prm)
+        ps_block_reduce(s, part.mx, red, redm, t);           // (past its barrier the next row may overwrite Bp, Ap, pose)
         if (t == 0) {
             if (max_h) max_h[row] = __fsqrt_rn(part.mx);
             if (avg_h) avg_h[row] = (float)((s[0] + s[2]) / (double)(M + P));
@@ -147,8 +131,7 @@ int hint_hausdorff_run(const hint_hausdorff_desc* desc, void* stream) {
     const char* who = "hint_hausdorff_run";
     if (!desc) return fail("%s: desc is null", who);
     if (!desc->a_points) return fail("%s: a_points is null", who);
-    if (desc->x && desc->b_points) return fail("%s: both x and b_points are given (the curve has one source)", who);
-    if (!desc->x && !desc->b_points) return fail("%s: x and b_points are both null (the curve needs a source)", who);
+    if (ps_check_source(who, desc->x, desc->b_points, "the curve needs a source")) return 1;
     if (desc->points && desc->b_points) return fail("%s: points is an output of the traced source only (b_points is given)", who);
     if (!desc->max_h && !desc->avg_h && !desc->chamfer && !desc->points)
         return fail("%s: no output requested (max_h, avg_h, chamfer and points are all null)", who);
@@ -158,12 +141,10 @@ int hint_hausdorff_run(const hint_hausdorff_desc* desc, void* stream) {
     if (hd_check_sizes(who, desc->n_rows, desc->n_coeffs, desc->n_points, row_max, desc->x != nullptr)) return 1;
     if (desc->a_offsets && desc->n_template > desc->n_rows * (int64_t)PS_MAX_M)
         return fail("%s: n_template = %lld is more than n_rows x %d points", who, (long long)desc->n_template, PS_MAX_M);
-    if (desc->max_groups < 0) return fail("%s: max_groups must be >= 0 (got %d)", who, desc->max_groups);
-    if (misaligned(who, "x", desc->x, 3) || misaligned(who, "b_points", desc->b_points, 3) ||
-        misaligned(who, "a_points", desc->a_points, 3) || misaligned(who, "a_offsets", desc->a_offsets, 7) ||
-        misaligned(who, "a_params", desc->a_params, 3) || misaligned(who, "max_h", desc->max_h, 3) ||
-        misaligned(who, "avg_h", desc->avg_h, 3) || misaligned(who, "chamfer", desc->chamfer, 3) ||
-        misaligned(who, "points", desc->points, 3))
+    if (ps_check_groups(who, desc->max_groups)) return 1;
+    if (ps_check_aligned(who, {{"x", desc->x, 3}, {"b_points", desc->b_points, 3}, {"a_points", desc->a_points, 3},
+                               {"a_offsets", desc->a_offsets, 7}, {"a_params", desc->a_params, 3}, {"max_h", desc->max_h, 3},
+                               {"avg_h", desc->avg_h, 3}, {"chamfer", desc->chamfer, 3}, {"points", desc->points, 3}}))
         return 1;
     const int grid = ps_grid(desc->n_rows, desc->max_groups, HD_MAX_WG);
     hipLaunchKernelGGL(hint_hausdorff_kernel, dim3(grid), dim3(PS_THREADS), 0, (hipStream_t)stream, desc->x, desc->b_points,

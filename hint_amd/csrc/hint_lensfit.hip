@@ -8,15 +8,16 @@
 //
 // hint_lensfit_kernel: the shape of hint_hausdorff_kernel - a persistent grid of G workgroups of 256 threads; workgroup w takes
 // rows w, w + G, ... one at a time and runs the row's S starts one after the other, so the selection needs no second launch and
-// no traffic between workgroups.  Built from hint_pointset.hpp (the trace, the own points, the reduction) and its arg-min walk:
+// no traffic between workgroups.  Built on hint_pointset.hpp: the trace, the own points, the placement, the walk in its form
+// that keeps the index of the minimum, the reduction.  This file adds the gradient's terms and the update rule:
 //   - once per workgroup: the P - 1 twiddles and the untransformed prototype (M <= 1024: one tile) to LDS;
 //   - per row: the coefficients; B traced or loaded into LDS; each thread holds its <= 4 B points in registers;
-//   - per step: thread 0 stages cs, sn and the parameters (not inlined, as hd_stage_params); every thread places its <= 4
-//     prototype points and writes them to LDS; pass 1 walks B for them, pass 2 walks the placed prototype for the thread's B
-//     points, both keeping the index of the minimum; the selected pairs' terms are recomputed in fp32 (q from the prototype in
-//     LDS: the same operations, the same bits) and added in double; ten double sums - the loss term and the four gradient terms
-//     of either side, kept apart because the weights are applied after the sums - go through ps_block_reduce; thread 0 forms the
-//     loss and the gradient, writes the trace and takes the step.  Three barriers a step.
+//   - per step: thread 0 stages the pose of the parameters (ps_stage_pose); every thread places its <= 4 prototype points
+//     (ps_place) and writes them to LDS; pass 1 walks B for them, pass 2 walks the placed prototype for the thread's B
+//     points, both keeping the index of the minimum; the selected pairs' terms are recomputed in fp32 (q by ps_rotate from the
+//     prototype in LDS: the same operations, the same bits) and added in double; ten double sums - the loss term and the four
+//     gradient terms of either side, kept apart because the weights are applied after the sums - go through ps_block_reduce;
+//     thread 0 forms the loss and the gradient, writes the trace and takes the step.  Three barriers a step.
 // The state of a fit (parameters, momentum buffer, the two learning rates) lives in LDS and is set afresh for every start.
 // Nothing is carried from row to row and no output is read back.  No float atomics, no counters, no workspace.
 // Untuned defaults (a workgroup per row although at P = 100, M = 130 only 130 threads hold a point; starts in sequence): DESIGN
@@ -31,24 +32,11 @@ constexpr int LF_MAX_M = PS_TILE, LF_MAX_S = 16, LF_MAX_STEPS = 1024;
 // a fit's state in LDS
 struct lf_state {
     float p[4], buf[4];                          // x, y, scale, angle; the momentum buffer
-    float cs, sn;
+    ps_pose pose;                                // of p, staged before every evaluation
     double lr, alr;                              // the learning rates before their fp32 rounding
     float best_p[4], best_l;
     int best;
 };
-
-// cs, sn of the state's angle, by one thread.  Not inlined, as hd_stage_params and for the same reason: the double-precision
-// sincos holds some thirty registers of constants
-__device__ __noinline__ void lf_stage_params(lf_state* st) {
-    double sn, cs;
-    sincos((double)st->p[3], &sn, &cs);
-    st->cs = (float)cs;
-    st->sn = (float)sn;
-}
-
-__device__ __forceinline__ float2 lf_rotate(float2 a, float cs, float sn) {
-    return make_float2(__fmaf_rn(-a.y, sn, __fmul_rn(a.x, cs)), __fmaf_rn(a.y, cs, __fmul_rn(a.x, sn)));
-}
 
 // the terms of a selected pair (e = A_i - B_j, q = the rotated prototype point) onto five double sums
 __device__ __forceinline__ void lf_add_pair(double (&s)[10], int o, float d, float ex, float ey, float2 q) {
@@ -81,11 +69,7 @@ __global__ __launch_bounds__(256) void hint_lensfit_kernel(const float* __restri
     const int ncA = (M + PS_THREADS - 1) / PS_THREADS, ncB = (P + PS_THREADS - 1) / PS_THREADS;
     const int evals = n_steps > 0 ? n_steps : 1;             // n_steps = 0: one evaluation, no update
     if (traced) ps_twiddles(tw, P, t);
-    for (int i = t; i < M; i += PS_THREADS) {
-        float2 a;                                            // (4-byte aligned: one 8-byte load all the same)
-        __builtin_memcpy(&a, a_points + 2 * (size_t)i, sizeof(a));
-        A0[i] = a;
-    }
+    for (int i = t; i < M; i += PS_THREADS) ps_load_point(A0[i], a_points + 2 * (size_t)i);
     for (int row = blockIdx.x; row < n; row += gridDim.x) {                  // (n <= 2^30)
         if (traced && t < C) coef[t] = x[(size_t)row * C + t];
         __syncthreads();                                     // coef (and, the first time, tw and A0) are whole
@@ -103,22 +87,22 @@ __global__ __launch_bounds__(256) void hint_lensfit_kernel(const float* __restri
                 }
                 st.lr = lr0;
                 st.alr = alr0;
-                lf_stage_params(&st);
+                ps_stage_pose(st.p, &st.pose);
             }
             float L = 0.f, g[4] = {0.f, 0.f, 0.f, 0.f};      // of the last evaluation (thread 0)
 #pragma unroll 1
             for (int it = 0; it < evals; ++it) {
                 __syncthreads();                             // st is staged; the walks of the step before are done with Ap
-                const float cs = st.cs, sn = st.sn, sc = st.p[2], xo = st.p[0], yo = st.p[1];
+                const ps_pose ps = st.pose;
                 // ---- place: this thread's prototype points; a slot past the end repeats the last point and is not counted ----
                 float ax[PS_PER], ay[PS_PER];
 #pragma unroll
                 for (int c = 0; c < PS_PER; ++c) {
                     const int i = t + PS_THREADS * c;
-                    const float2 q = lf_rotate(A0[i < M ? i : M - 1], cs, sn);
-                    ax[c] = __fmaf_rn(q.x, sc, xo);
-                    ay[c] = __fmaf_rn(q.y, sc, yo);
-                    if (i < M) Ap[i] = make_float2(ax[c], ay[c]);
+                    const float2 a = ps_place(A0[i < M ? i : M - 1], ps);
+                    ax[c] = a.x;
+                    ay[c] = a.y;
+                    if (i < M) Ap[i] = a;
                 }
                 __syncthreads();                             // Ap is whole
                 double sm[10];
@@ -126,12 +110,8 @@ __global__ __launch_bounds__(256) void hint_lensfit_kernel(const float* __restri
                 for (int k = 0; k < 10; ++k) sm[k] = 0.0;
                 {   // ---- pass 1: mA of this thread's A points, and where ----
                     float m[PS_PER];
-                    int at[PS_PER];
-#pragma unroll
-                    for (int c = 0; c < PS_PER; ++c) {
-                        m[c] = INFINITY;
-                        at[c] = 0;
-                    }
+                    int at[PS_PER] = {0, 0, 0, 0};
+                    ps_no_minima(m);
                     ps_scan_arg_n(ncA, Bp, P, ax, ay, m, at);
 #pragma unroll
                     for (int c = 0; c < PS_PER; ++c) {
@@ -139,25 +119,21 @@ __global__ __launch_bounds__(256) void hint_lensfit_kernel(const float* __restri
                         if (i < M) {                         // (then c < ncA)
                             const float2 b = Bp[at[c]];
                             const float ex = __fsub_rn(ax[c], b.x), ey = __fsub_rn(ay[c], b.y);
-                            lf_add_pair(sm, 5, __fmaf_rn(ey, ey, __fmul_rn(ex, ex)), ex, ey, lf_rotate(A0[i], cs, sn));
+                            lf_add_pair(sm, 5, __fmaf_rn(ey, ey, __fmul_rn(ex, ex)), ex, ey, ps_rotate(A0[i], ps.cs, ps.sn));
                         }
                     }
                 }
                 {   // ---- pass 2: mB of this thread's B points, and where ----
                     float m[PS_PER];
-                    int at[PS_PER];
-#pragma unroll
-                    for (int c = 0; c < PS_PER; ++c) {
-                        m[c] = INFINITY;
-                        at[c] = 0;
-                    }
+                    int at[PS_PER] = {0, 0, 0, 0};
+                    ps_no_minima(m);
                     ps_scan_arg_n(ncB, Ap, M, bx, by, m, at);
 #pragma unroll
                     for (int c = 0; c < PS_PER; ++c) {
                         if (t + PS_THREADS * c < P) {        // (then c < ncB)
                             const float2 a = Ap[at[c]];
                             const float ex = __fsub_rn(a.x, bx[c]), ey = __fsub_rn(a.y, by[c]);
-                            lf_add_pair(sm, 0, __fmaf_rn(ey, ey, __fmul_rn(ex, ex)), ex, ey, lf_rotate(A0[at[c]], cs, sn));
+                            lf_add_pair(sm, 0, __fmaf_rn(ey, ey, __fmul_rn(ex, ex)), ex, ey, ps_rotate(A0[at[c]], ps.cs, ps.sn));
                         }
                     }
                 }
@@ -170,7 +146,7 @@ __global__ __launch_bounds__(256) void hint_lensfit_kernel(const float* __restri
                     g[0] = (float)(2.0 * (sm[1] / dP + weight * (sm[6] / dM)));
                     g[1] = (float)(2.0 * (sm[2] / dP + weight * (sm[7] / dM)));
                     g[2] = (float)(2.0 * (sm[3] / dP + weight * (sm[8] / dM)));
-                    g[3] = (float)(2.0 * (double)sc * (sm[4] / dP + weight * (sm[9] / dM)));
+                    g[3] = (float)(2.0 * (double)ps.scale * (sm[4] / dP + weight * (sm[9] / dM)));
                     if (n_steps > 0) {
                         if (trace) {
                             float* tr = trace + 9 * (rs * (size_t)n_steps + it);
@@ -188,7 +164,7 @@ __global__ __launch_bounds__(256) void hint_lensfit_kernel(const float* __restri
                         }
                         st.lr *= gamma;
                         st.alr *= gamma;
-                        if (it + 1 < evals) lf_stage_params(&st);
+                        if (it + 1 < evals) ps_stage_pose(st.p, &st.pose);
                     }
                 }
             }
@@ -260,8 +236,7 @@ int hint_lensfit_run(const hint_lensfit_desc* desc, void* stream) {
     if (!desc) return fail("%s: desc is null", who);
     if (!desc->a_points) return fail("%s: a_points is null", who);
     if (!desc->starts) return fail("%s: starts is null", who);
-    if (desc->x && desc->b_points) return fail("%s: both x and b_points are given (the curve has one source)", who);
-    if (!desc->x && !desc->b_points) return fail("%s: x and b_points are both null (the curve needs a source)", who);
+    if (ps_check_source(who, desc->x, desc->b_points, "the curve needs a source")) return 1;
     if (!desc->params && !desc->loss && !desc->best && !desc->all_params && !desc->all_loss && !desc->grad && !desc->trace)
         return fail("%s: no output requested (params, loss, best, all_params, all_loss, grad and trace are all null)", who);
     if (lf_check_sizes(who, desc->n_rows, desc->n_coeffs, desc->n_points, desc->n_template, desc->n_starts, desc->n_steps,
@@ -272,13 +247,11 @@ int hint_lensfit_run(const hint_lensfit_desc* desc, void* stream) {
         lf_check_rate(who, "gamma", desc->gamma) || lf_check_rate(who, "momentum", desc->momentum))
         return 1;
     if (!std::isfinite(desc->weight)) return fail("%s: weight must be finite (got %g)", who, desc->weight);
-    if (desc->max_groups < 0) return fail("%s: max_groups must be >= 0 (got %d)", who, desc->max_groups);
-    if (misaligned(who, "x", desc->x, 3) || misaligned(who, "b_points", desc->b_points, 3) ||
-        misaligned(who, "a_points", desc->a_points, 3) || misaligned(who, "starts", desc->starts, 3) ||
-        misaligned(who, "params", desc->params, 3) || misaligned(who, "loss", desc->loss, 3) ||
-        misaligned(who, "best", desc->best, 3) || misaligned(who, "all_params", desc->all_params, 3) ||
-        misaligned(who, "all_loss", desc->all_loss, 3) || misaligned(who, "grad", desc->grad, 3) ||
-        misaligned(who, "trace", desc->trace, 3))
+    if (ps_check_groups(who, desc->max_groups)) return 1;
+    if (ps_check_aligned(who, {{"x", desc->x, 3}, {"b_points", desc->b_points, 3}, {"a_points", desc->a_points, 3},
+                               {"starts", desc->starts, 3}, {"params", desc->params, 3}, {"loss", desc->loss, 3},
+                               {"best", desc->best, 3}, {"all_params", desc->all_params, 3}, {"all_loss", desc->all_loss, 3},
+                               {"grad", desc->grad, 3}, {"trace", desc->trace, 3}}))
         return 1;
     const int grid = ps_grid(desc->n_rows, desc->max_groups, LF_MAX_WG);
     hipLaunchKernelGGL(hint_lensfit_kernel, dim3(grid), dim3(PS_THREADS), 0, (hipStream_t)stream, desc->x, desc->b_points,

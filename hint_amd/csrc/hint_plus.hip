@@ -48,7 +48,7 @@ struct pl_row {
     int keep, nk, M, bad;
 };
 
-// the row's 8 coordinates, cs, sn and the offsets to LDS, by one thread.  Not inlined, as hd_stage_params and for the same
+// the row's 8 coordinates, cs, sn and the offsets to LDS, by one thread.  Not inlined, as ps_stage_pose and for the same
 // reason: the double-precision sincos holds some thirty registers of constants
 __device__ __noinline__ void pl_stage_params(const float* pr, pl_row* rw) {
     const float xlength = pr[0], ylength = pr[1], xwidth = pr[2], ywidth = pr[3], xshift = pr[4], yshift = pr[5];
@@ -173,8 +173,7 @@ __global__ __launch_bounds__(256) void hint_plus_kernel(const float* __restrict_
         if (loss) {
             // ---- the segment term: min over the kept segments of the squared distance to the segment ----
             float ms[PS_PER];
-#pragma unroll
-            for (int c = 0; c < PS_PER; ++c) ms[c] = INFINITY;
+            ps_no_minima(ms);
 #pragma unroll 1
             for (int s = 0; s < 12; ++s) {
                 if (!((kmask >> s) & 1)) continue;
@@ -274,19 +273,16 @@ int hint_plus_run(const hint_plus_desc* desc, void* stream) {
     if (!desc->segments && !desc->keep && !desc->counts && !desc->loss && !desc->max_h && !desc->avg_h)
         return fail("%s: no output requested (segments, keep, counts, loss, max_h and avg_h are all null)", who);
     const bool with_curve = desc->loss || desc->max_h || desc->avg_h;
-    if (desc->x && desc->b_points) return fail("%s: both x and b_points are given (the curve has one source)", who);
-    if (with_curve && !desc->x && !desc->b_points)
-        return fail("%s: x and b_points are both null (loss, max_h and avg_h need the curve)", who);
+    if (ps_check_source(who, desc->x, desc->b_points, with_curve ? "loss, max_h and avg_h need the curve" : nullptr)) return 1;
     if (ps_check_sizes(who, desc->n_rows, desc->n_coeffs, desc->n_points, desc->x != nullptr,
                        with_curve || desc->x || desc->b_points))
         return 1;
     if (!(desc->max_dist > 0.f) || !std::isfinite(desc->max_dist))
         return fail("%s: max_dist must be finite and > 0 (got %g)", who, (double)desc->max_dist);
-    if (desc->max_groups < 0) return fail("%s: max_groups must be >= 0 (got %d)", who, desc->max_groups);
-    if (misaligned(who, "x", desc->x, 3) || misaligned(who, "b_points", desc->b_points, 3) ||
-        misaligned(who, "params", desc->params, 3) || misaligned(who, "segments", desc->segments, 3) ||
-        misaligned(who, "keep", desc->keep, 3) || misaligned(who, "counts", desc->counts, 3) ||
-        misaligned(who, "loss", desc->loss, 3) || misaligned(who, "max_h", desc->max_h, 3) || misaligned(who, "avg_h", desc->avg_h, 3))
+    if (ps_check_groups(who, desc->max_groups)) return 1;
+    if (ps_check_aligned(who, {{"x", desc->x, 3}, {"b_points", desc->b_points, 3}, {"params", desc->params, 3},
+                               {"segments", desc->segments, 3}, {"keep", desc->keep, 3}, {"counts", desc->counts, 3},
+                               {"loss", desc->loss, 3}, {"max_h", desc->max_h, 3}, {"avg_h", desc->avg_h, 3}}))
         return 1;
     const int grid = ps_grid(desc->n_rows, desc->max_groups, PL_MAX_WG);
     // without a curve output the kernel reads no curve: P = 2 keeps its (unused) sizes in range

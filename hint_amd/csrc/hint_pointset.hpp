@@ -1,14 +1,18 @@
 // The core that the kernels measuring a traced curve against a point set are built from (hint_hausdorff.hip: a template in
-// memory; hint_plus.hip: a plus shape's outline, generated on the fly).  Internal; described in DESIGN section 14.
+// memory; hint_plus.hip: a plus shape's outline, generated on the fly; hint_lensfit.hip: a prototype placed anew every step of a
+// fit).  Internal; described in DESIGN section 14.
 // Everything here is part of the contract of include/hint_amd.h - the fp32 order of every operation and the association of the
-// double sums - stated once, so that both kernels give the same bits on the same point sets (tests/test_gpu_plus.py
+// double sums - stated once, so that the kernels give the same bits on the same point sets (tests/test_gpu_plus.py
 // test_the_generated_outline_is_the_host_built_template_bit_for_bit) and keep the ones tests/golden/pointset_bits.npz recorded.
+// The entry points' shared argument checks are here as well, their message texts part of the behaviour.
 //   B = the curve: P <= 1024 points in LDS, traced by hint_curve.hip's rule from P - 1 twiddles or given; thread t owns points
 //       t, t + 256, ... (at most PS_PER = 4) and holds them in registers
 //   A = the other set: M <= 4096 points that pass through LDS in tiles of 1024, made by the kernel's `fill`; thread t owns points
 //       t, t + 256, ... of a tile
 //   D(i, j) = fma(dy, dy, dx dx) of A_i - B_j;  mA_i = min_j D,  mB_j = min_i D
 #pragma once
+#include <initializer_list>
+
 #include "hint_host.hpp"
 
 namespace hint {
@@ -37,33 +41,117 @@ inline int ps_check_sizes(const char* who, int64_t n_rows, int32_t n_coeffs, int
     return 0;
 }
 
+// the curve has one source, x or b_points; needs: what the message says of a call that has neither, null when the call reads
+// no curve
+inline int ps_check_source(const char* who, const void* x, const void* b_points, const char* needs) {
+    if (x && b_points) return fail("%s: both x and b_points are given (the curve has one source)", who);
+    if (needs && !x && !b_points) return fail("%s: x and b_points are both null (%s)", who, needs);
+    return 0;
+}
+
+inline int ps_check_groups(const char* who, int32_t max_groups) {
+    if (max_groups < 0) return fail("%s: max_groups must be >= 0 (got %d)", who, max_groups);
+    return 0;
+}
+
+// the descriptor's pointers, in the order they are reported in (a null pointer is aligned)
+struct ps_ptr {
+    const char* name;
+    const void* p;
+    int mask;
+};
+
+inline int ps_check_aligned(const char* who, std::initializer_list<ps_ptr> ptrs) {
+    for (const ps_ptr& a : ptrs)
+        if (misaligned(who, a.name, a.p, a.mask)) return 1;
+    return 0;
+}
+
 }  // namespace hint
 
 // the walk of both passes: NC points of this thread against n points in LDS.  Every read has one address for the whole wavefront
 // (a broadcast, no bank conflict) and feeds NC times five vector operations.  (D is written for A_i - B_j; pass 2 holds B and
 // walks A, and the differences there are the exact negatives, so the squares - and D - are the same bits.)
-template <int NC>
-__device__ __forceinline__ void ps_scan(const float2* src, int n, const float (&px)[hint::PS_PER], const float (&py)[hint::PS_PER],
-                                        float (&m)[hint::PS_PER]) {
+// ARG: the walk also says where - the minimum is replaced only by a strictly smaller D, so among equal D the lowest index of src
+// stays (and a NaN never enters); at[c] starts at 0 and is always an index of src.  (hint_lensfit.hip recomputes the selected
+// pair's difference from it for the gradient.)  Without ARG at is not looked at
+template <int NC, bool ARG>
+__device__ __forceinline__ void ps_walk(const float2* src, int n, const float (&px)[hint::PS_PER], const float (&py)[hint::PS_PER],
+                                        float (&m)[hint::PS_PER], int* at) {
 #pragma unroll 4
     for (int j = 0; j < n; ++j) {
         const float2 q = src[j];
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
             const float dx = __fsub_rn(px[c], q.x), dy = __fsub_rn(py[c], q.y);
-            m[c] = fminf(m[c], __fmaf_rn(dy, dy, __fmul_rn(dx, dx)));
+            const float d = __fmaf_rn(dy, dy, __fmul_rn(dx, dx));
+            if constexpr (ARG) {
+                const bool lt = d < m[c];
+                m[c] = lt ? d : m[c];
+                at[c] = lt ? j : at[c];
+            } else {
+                m[c] = fminf(m[c], d);
+            }
         }
+    }
+}
+
+template <bool ARG>
+__device__ __forceinline__ void ps_walk_n(int nc, const float2* src, int n, const float (&px)[hint::PS_PER],
+                                          const float (&py)[hint::PS_PER], float (&m)[hint::PS_PER], int* at) {
+    switch (nc) {                                            // (nc is the same for the whole workgroup)
+        case 1: ps_walk<1, ARG>(src, n, px, py, m, at); break;
+        case 2: ps_walk<2, ARG>(src, n, px, py, m, at); break;
+        case 3: ps_walk<3, ARG>(src, n, px, py, m, at); break;
+        default: ps_walk<4, ARG>(src, n, px, py, m, at); break;
     }
 }
 
 __device__ __forceinline__ void ps_scan_n(int nc, const float2* src, int n, const float (&px)[hint::PS_PER],
                                           const float (&py)[hint::PS_PER], float (&m)[hint::PS_PER]) {
-    switch (nc) {                                            // (nc is the same for the whole workgroup)
-        case 1: ps_scan<1>(src, n, px, py, m); break;
-        case 2: ps_scan<2>(src, n, px, py, m); break;
-        case 3: ps_scan<3>(src, n, px, py, m); break;
-        default: ps_scan<4>(src, n, px, py, m); break;
-    }
+    ps_walk_n<false>(nc, src, n, px, py, m, nullptr);
+}
+
+__device__ __forceinline__ void ps_scan_arg_n(int nc, const float2* src, int n, const float (&px)[hint::PS_PER],
+                                              const float (&py)[hint::PS_PER], float (&m)[hint::PS_PER], int (&at)[hint::PS_PER]) {
+    ps_walk_n<true>(nc, src, n, px, py, m, at);
+}
+
+// minima before a walk
+__device__ __forceinline__ void ps_no_minima(float (&m)[hint::PS_PER]) {
+#pragma unroll
+    for (int c = 0; c < hint::PS_PER; ++c) m[c] = INFINITY;
+}
+
+// a point at a 4-byte aligned address: one 8-byte load all the same
+__device__ __forceinline__ void ps_load_point(float2& a, const float* p) { __builtin_memcpy(&a, p, sizeof(a)); }
+
+// where the parameters (x, y, scale, angle) put a point a: q = a R (the angle), then q scale + (x, y) - lens_points_from_params
+struct ps_pose {
+    float cs, sn, scale, x, y;
+};
+
+// the pose of pr = (x, y, scale, angle) to LDS, by one thread.  Not inlined: the double-precision sincos holds some thirty
+// registers of constants, which would otherwise stay live across the whole row loop
+inline __device__ __noinline__ void ps_stage_pose(const float* pr, ps_pose* ps) {
+    double sn, cs;
+    sincos((double)pr[3], &sn, &cs);
+    ps->cs = (float)cs;
+    ps->sn = (float)sn;
+    ps->scale = pr[2];
+    ps->x = pr[0];
+    ps->y = pr[1];
+}
+
+// (the point by reference: handed over by value, the tile filler of hint_hausdorff.hip compiles to a branch a point where it is
+// two selects now)
+__device__ __forceinline__ float2 ps_rotate(const float2& a, float cs, float sn) {
+    return make_float2(__fmaf_rn(-a.y, sn, __fmul_rn(a.x, cs)), __fmaf_rn(a.y, cs, __fmul_rn(a.x, sn)));
+}
+
+__device__ __forceinline__ float2 ps_place(const float2& a, const ps_pose& ps) {
+    const float2 q = ps_rotate(a, ps.cs, ps.sn);
+    return make_float2(__fmaf_rn(q.x, ps.scale, ps.x), __fmaf_rn(q.y, ps.scale, ps.y));
 }
 
 __device__ __forceinline__ double ps_wave_sum(double v) {
@@ -172,8 +260,7 @@ __device__ __forceinline__ ps_part ps_two_sided(float2* Ap, const float2* Bp, in
     ps_part s;
     const int ncB = (P + PS_THREADS - 1) / PS_THREADS;
     float mb[PS_PER];
-#pragma unroll
-    for (int c = 0; c < PS_PER; ++c) mb[c] = INFINITY;
+    ps_no_minima(mb);
     for (int a0 = 0; a0 < M; a0 += PS_TILE) {
         const int cnt = M - a0 < PS_TILE ? M - a0 : PS_TILE;
         const int ncA = (cnt + PS_THREADS - 1) / PS_THREADS;
@@ -183,8 +270,7 @@ __device__ __forceinline__ ps_part ps_two_sided(float2* Ap, const float2* Bp, in
         __syncthreads();
         float px[PS_PER], py[PS_PER], ma[PS_PER];
         ps_own_points(Ap, cnt, t, px, py);
-#pragma unroll
-        for (int c = 0; c < PS_PER; ++c) ma[c] = INFINITY;
+        ps_no_minima(ma);
         ps_scan_n(ncA, Bp, P, px, py, ma);                   // pass 1: mA of this thread's points of the tile
         ps_scan_n(ncB, Ap, cnt, bx, by, mb);                 // pass 2: mB so far
 #pragma unroll
@@ -230,35 +316,5 @@ __device__ __forceinline__ void ps_block_reduce(double (&s)[NS], float& mx, doub
 #pragma unroll
             for (int q = 0; q < NS; ++q) s[q] += red[w][q];
         }
-    }
-}
-
-// ps_scan that also says where: the minimum is replaced only by a strictly smaller D, so among equal D the lowest index of src
-// stays (and a NaN never enters); at[c] starts at 0 and is always an index of src.  (hint_lensfit.hip recomputes the selected
-// pair's difference from it for the gradient.)
-template <int NC>
-__device__ __forceinline__ void ps_scan_arg(const float2* src, int n, const float (&px)[hint::PS_PER], const float (&py)[hint::PS_PER],
-                                            float (&m)[hint::PS_PER], int (&at)[hint::PS_PER]) {
-#pragma unroll 4
-    for (int j = 0; j < n; ++j) {
-        const float2 q = src[j];
-#pragma unroll
-        for (int c = 0; c < NC; ++c) {
-            const float dx = __fsub_rn(px[c], q.x), dy = __fsub_rn(py[c], q.y);
-            const float d = __fmaf_rn(dy, dy, __fmul_rn(dx, dx));
-            const bool lt = d < m[c];
-            m[c] = lt ? d : m[c];
-            at[c] = lt ? j : at[c];
-        }
-    }
-}
-
-__device__ __forceinline__ void ps_scan_arg_n(int nc, const float2* src, int n, const float (&px)[hint::PS_PER],
-                                              const float (&py)[hint::PS_PER], float (&m)[hint::PS_PER], int (&at)[hint::PS_PER]) {
-    switch (nc) {                                            // (nc is the same for the whole workgroup)
-        case 1: ps_scan_arg<1>(src, n, px, py, m, at); break;
-        case 2: ps_scan_arg<2>(src, n, px, py, m, at); break;
-        case 3: ps_scan_arg<3>(src, n, px, py, m, at); break;
-        default: ps_scan_arg<4>(src, n, px, py, m, at); break;
     }
 }

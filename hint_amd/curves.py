@@ -66,13 +66,22 @@ def _check_points(v, who: str, most: int = MAX_POINTS) -> int:
     return v
 
 
-def _check_noise(v, who: str) -> float:
+def _check_real(v, name: str, who: str, nonneg: bool = True) -> float:
     if isinstance(v, bool) or not isinstance(v, (int, float)):
-        raise HintAmdError(f"{who}: noise must be a number (got {type(v).__name__})")
+        raise HintAmdError(f"{who}: {name} must be a number (got {type(v).__name__})")
     v = float(v)
     if v != v or v in (float("inf"), float("-inf")):
-        raise HintAmdError(f"{who}: noise must be finite (got {v})")
+        raise HintAmdError(f"{who}: {name} must be finite (got {v})")
+    if nonneg and v < 0.0:
+        raise HintAmdError(f"{who}: {name} must be >= 0 (got {v})")
     return v
+
+
+def _check_weight(v, name: str, who: str) -> float:
+    """the weight of a loss's second term: any number but NaN (an infinite one included)"""
+    if isinstance(v, bool) or not isinstance(v, (int, float)) or v != v:
+        raise HintAmdError(f"{who}: {name} must be a number (got {v!r})")
+    return float(v)
 
 
 def _check_target(target, n_rows: int, device, who: str) -> torch.Tensor:
@@ -99,7 +108,7 @@ def _check_eps(eps, x: torch.Tensor, who: str) -> torch.Tensor:
 
 
 def _noise_args(x: torch.Tensor, noise, eps, generator, who: str):
-    noise = _check_noise(noise, who)
+    noise = _check_real(noise, "noise", who, nonneg=False)
     if eps is not None:
         return noise, _check_eps(eps, x, who)
     if noise == 0.0:
@@ -109,22 +118,45 @@ def _noise_args(x: torch.Tensor, noise, eps, generator, who: str):
     return noise, torch.randn(x.shape[0], 2, device=x.device, dtype=torch.float32, generator=generator)
 
 
+def _outputs(desc, table, want, out, dev):
+    """the outputs named in `want` as a dict, by table = name -> (shape, dtype): the tensor `out` holds under the name (the tests'
+    guarded buffers) or a new one.  Sets the descriptor's pointer of every name of the table, None where it is not wanted"""
+    res = {}
+    for name in want:
+        shape, dtype = table[name]
+        res[name] = out[name] if out is not None and name in out else torch.empty(shape, dtype=dtype, device=dev)
+    for name in table:
+        setattr(desc, name, res[name].data_ptr() if name in res else None)
+    return res
+
+
+def _set_curve(desc, curve: Optional[torch.Tensor], n: int, k: int, p: int):
+    """the descriptor's rows and curve source: curve [N, 4K] coefficients traced at p points, or (k = 0) [N, p, 2] points; None:
+    the call reads no curve"""
+    if curve is not None:
+        desc.x, desc.b_points = (curve.data_ptr(), None) if k else (None, curve.data_ptr())
+    desc.n_rows, desc.n_coeffs, desc.n_points = n, k, p
+
+
+_F32, _I32 = torch.float32, torch.int32
+
+
 def _run(x: torch.Tensor, n_points: int, eps: Optional[torch.Tensor] = None, noise: float = 0.0,
          target: Optional[torch.Tensor] = None, want_dist: bool = False, want_mean: bool = False, max_groups: int = 0):
     """one hint_curve_run on checked arguments: (y [N, 2], dist [N] or None, mean 0-dim or None)"""
     lib = _lib.load()
     n, c = x.shape
     with torch.cuda.device(x.device):
-        y = torch.empty(n, 2, dtype=torch.float32, device=x.device)
-        dist = torch.empty(n, dtype=torch.float32, device=x.device) if want_dist else None
-        mean = torch.empty((), dtype=torch.float32, device=x.device) if want_mean else None
         desc = _lib.CurveDesc()
         desc.x, desc.n_rows, desc.n_coeffs, desc.n_points = x.data_ptr(), n, c // 4, n_points
         desc.eps, desc.noise = (eps.data_ptr() if eps is not None else None), noise
         desc.target = target.data_ptr() if target is not None else None
-        desc.y = y.data_ptr()
-        desc.dist = dist.data_ptr() if want_dist else None
-        desc.mean = mean.data_ptr() if want_mean else None
+        want = ["y"]
+        if want_dist:
+            want.append("dist")
+        if want_mean:
+            want.append("mean")
+        res = _outputs(desc, dict(y=((n, 2), _F32), dist=((n,), _F32), mean=((), _F32)), want, None, x.device)
         desc.max_groups = max_groups
         ws = None
         if want_mean:
@@ -135,7 +167,7 @@ def _run(x: torch.Tensor, n_points: int, eps: Optional[torch.Tensor] = None, noi
             desc.workspace, desc.workspace_bytes = ws.data_ptr(), nbytes
         st = lib.hint_curve_run(desc, torch.cuda.current_stream(x.device).cuda_stream)
     _lib.check(st, "hint_curve_run")
-    return y, dist, mean
+    return res["y"], res.get("dist"), res.get("mean")
 
 
 def curve_features(x: torch.Tensor, n_points: int = 100) -> torch.Tensor:
@@ -196,6 +228,12 @@ def _check_dense_points(v, who: str) -> int:
     return _check_points(v, who, MAX_DENSE_POINTS)
 
 
+def _check_no_grad(t: torch.Tensor, name: str, who: str) -> None:
+    if t.requires_grad and torch.is_grad_enabled():
+        raise HintAmdError(f"{who}: {name} requires grad, and no gradient is implemented; call it under torch.no_grad() or "
+                           "detach the input")
+
+
 def _check_dev_tensor(t, name: str, who: str, device=None) -> torch.Tensor:
     """a floating-point tensor on the GPU (on `device`, if given) that no gradient is asked of -> detached, fp32, contiguous"""
     if not isinstance(t, torch.Tensor):
@@ -206,9 +244,7 @@ def _check_dev_tensor(t, name: str, who: str, device=None) -> torch.Tensor:
         raise HintAmdError(f"{who}: {name} is on {t.device} and curve on {device}")
     if not t.is_floating_point():
         raise HintAmdError(f"{who}: {name} is {t.dtype}; expected a floating-point tensor")
-    if t.requires_grad and torch.is_grad_enabled():
-        raise HintAmdError(f"{who}: {name} requires grad, and no gradient is implemented; call it under torch.no_grad() or "
-                           "detach the input")
+    _check_no_grad(t, name, who)
     t = t.detach()
     if t.dtype != torch.float32 or not t.is_contiguous():              # (copies only where needed)
         t = t.to(torch.float32).contiguous()
@@ -303,24 +339,25 @@ def _hd_run(curve: torch.Tensor, k: int, p: int, template: Optional[torch.Tensor
     lib = _lib.load()
     n, dev = curve.shape[0], curve.device
     with torch.cuda.device(dev):
-        new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)     # noqa: E731
-        max_h, avg_h = (new(n), new(n)) if want_h else (None, None)
-        chamfer = new(n, 2) if want_chamfer else None
-        points = new(n, p, 2) if want_points else None
         desc = _lib.HausdorffDesc()
-        desc.x, desc.b_points = (curve.data_ptr(), None) if k else (None, curve.data_ptr())
-        desc.n_rows, desc.n_coeffs, desc.n_points = n, k, p
+        _set_curve(desc, curve, n, k, p)
         desc.a_points = template.data_ptr() if template is not None else curve.data_ptr()
         desc.n_template = template.shape[0] if template is not None else 1
         desc.a_offsets = offsets.data_ptr() if offsets is not None else None
         desc.a_params = params.data_ptr() if params is not None else None
-        desc.max_h, desc.avg_h = (max_h.data_ptr(), avg_h.data_ptr()) if want_h else (None, None)
-        desc.chamfer = chamfer.data_ptr() if want_chamfer else None
-        desc.points = points.data_ptr() if want_points else None
+        want = []
+        if want_h:
+            want += ["max_h", "avg_h"]
+        if want_chamfer:
+            want.append("chamfer")
+        if want_points:
+            want.append("points")
+        res = _outputs(desc, dict(max_h=((n,), _F32), avg_h=((n,), _F32), chamfer=((n, 2), _F32), points=((n, p, 2), _F32)),
+                       want, None, dev)
         desc.max_groups = max_groups
         st = lib.hint_hausdorff_run(desc, torch.cuda.current_stream(dev).cuda_stream)
     _lib.check(st, "hint_hausdorff_run")
-    return max_h, avg_h, chamfer, points
+    return res.get("max_h"), res.get("avg_h"), res.get("chamfer"), res.get("points")
 
 
 def trace_fourier_curves(x: torch.Tensor, n_points: int = 100) -> torch.Tensor:
@@ -328,9 +365,8 @@ def trace_fourier_curves(x: torch.Tensor, n_points: int = 100) -> torch.Tensor:
     [N, n_points, 2] fp32 on x's device, 2 <= n_points <= 1024; the last point repeats the first bit for bit.  Up to 128 points
     these are the points curve_features measures"""
     who = "trace_fourier_curves"
-    if isinstance(x, torch.Tensor) and x.requires_grad and torch.is_grad_enabled():
-        raise HintAmdError(f"{who}: x requires grad, and no gradient is implemented; call it under torch.no_grad() or detach "
-                           "the input")
+    if isinstance(x, torch.Tensor):
+        _check_no_grad(x, "x", who)
     x = _check_x(x, who)
     return _hd_run(x, x.shape[1] // 4, _check_dense_points(n_points, who), None, want_points=True)[3]
 
@@ -363,13 +399,12 @@ def lens_fit_loss(curve: torch.Tensor, prototype: torch.Tensor, params: torch.Te
     chamfer[:, 0] + lens_fit_weight * chamfer[:, 1] of chamfer_distances(curve, prototype, params).  curve as in
     hausdorff_distances; coefficients are traced at 100 points, as the fit's points are"""
     who = "lens_fit_loss"
-    if isinstance(lens_fit_weight, bool) or not isinstance(lens_fit_weight, (int, float)) or lens_fit_weight != lens_fit_weight:
-        raise HintAmdError(f"{who}: lens_fit_weight must be a number (got {lens_fit_weight!r})")
+    weight = _check_weight(lens_fit_weight, "lens_fit_weight", who)
     if params is None:
         raise HintAmdError(f"{who}: params must be a tensor (got None)")
     curve, k, p, prototype, _, params = _distance_args(curve, prototype, params, None, 100, who)
     ch = _hd_run(curve, k, p, prototype, None, params, want_chamfer=True)[2]
-    return ch[:, 0] + float(lens_fit_weight) * ch[:, 1]
+    return ch[:, 0] + weight * ch[:, 1]
 
 
 # ---- the plus shape: outline, fit loss and distances to the densified outline (hint_plus.hip) ----
@@ -426,20 +461,12 @@ def _plus_run(params: torch.Tensor, curve: Optional[torch.Tensor] = None, k: int
     out: tensors to write into instead of new ones (the tests' guarded buffers)"""
     lib = _lib.load()
     n, dev = params.shape[0], params.device
-    shapes = dict(segments=((n, 12, 2, 2), torch.float32), keep=((n,), torch.int32), counts=((n, 12), torch.int32),
-                  loss=((n, 2), torch.float32), max_h=((n,), torch.float32), avg_h=((n,), torch.float32))
     with torch.cuda.device(dev):
-        res = {}
-        for name in want:
-            shape, dtype = shapes[name]
-            res[name] = out[name] if out is not None and name in out else torch.empty(shape, dtype=dtype, device=dev)
         desc = _lib.PlusDesc()
-        if curve is not None:
-            desc.x, desc.b_points = (curve.data_ptr(), None) if k else (None, curve.data_ptr())
-        desc.n_rows, desc.n_coeffs, desc.n_points = n, k, p
+        _set_curve(desc, curve, n, k, p)
         desc.params, desc.max_dist, desc.max_groups = params.data_ptr(), max_dist, max_groups
-        for name in shapes:
-            setattr(desc, name, res[name].data_ptr() if name in res else None)
+        res = _outputs(desc, dict(segments=((n, 12, 2, 2), _F32), keep=((n,), _I32), counts=((n, 12), _I32), loss=((n, 2), _F32),
+                                  max_h=((n,), _F32), avg_h=((n,), _F32)), want, out, dev)
         st = lib.hint_plus_run(desc, torch.cuda.current_stream(dev).cuda_stream)
     _lib.check(st, "hint_plus_run")
     return res
@@ -476,11 +503,10 @@ def plus_fit_loss(curve: torch.Tensor, params: torch.Tensor, corner_weight: floa
     """the reference's points_to_plus_loss(points, params, corner_weight) for every row, [N] fp32: terms[:, 0] + corner_weight *
     terms[:, 1] of plus_fit_terms.  Coefficients are traced at 100 points, as the fit's points are"""
     who = "plus_fit_loss"
-    if isinstance(corner_weight, bool) or not isinstance(corner_weight, (int, float)) or corner_weight != corner_weight:
-        raise HintAmdError(f"{who}: corner_weight must be a number (got {corner_weight!r})")
+    weight = _check_weight(corner_weight, "corner_weight", who)
     curve, k, p, params = _plus_args(curve, params, 100, who)
     terms = _plus_run(params, curve, k, p, want=("loss",))["loss"]
-    return terms[:, 0] + float(corner_weight) * terms[:, 1]
+    return terms[:, 0] + weight * terms[:, 1]
 
 
 def plus_hausdorff_distances(curve: torch.Tensor, params: torch.Tensor, *, max_dist: float = 0.02, n_points: int = 1000):
@@ -503,17 +529,6 @@ MAX_PROTOTYPE_POINTS = 1024
 MAX_STARTS = 16
 MAX_FIT_STEPS = 1024
 FIT_POINTS = 100           # the points a curve given as coefficients is traced at (run_experiments.py:147)
-
-
-def _check_real(v, name: str, who: str, nonneg: bool = True) -> float:
-    if isinstance(v, bool) or not isinstance(v, (int, float)):
-        raise HintAmdError(f"{who}: {name} must be a number (got {type(v).__name__})")
-    v = float(v)
-    if v != v or v in (float("inf"), float("-inf")):
-        raise HintAmdError(f"{who}: {name} must be finite (got {v})")
-    if nonneg and v < 0.0:
-        raise HintAmdError(f"{who}: {name} must be >= 0 (got {v})")
-    return v
 
 
 def _check_steps(v, who: str) -> int:
@@ -547,11 +562,6 @@ def _fit_args(curve, prototype, who: str):
     return curve, n, k, p, prototype
 
 
-_LF_OUT = dict(params=(lambda n, s, t: (n, 4)), loss=(lambda n, s, t: (n,)), best=(lambda n, s, t: (n,)),
-               all_params=(lambda n, s, t: (n, s, 4)), all_loss=(lambda n, s, t: (n, s)), grad=(lambda n, s, t: (n, s, 4)),
-               trace=(lambda n, s, t: (n, s, t, 9)))
-
-
 def _lf_run(curve: torch.Tensor, k: int, p: int, prototype: torch.Tensor, starts: torch.Tensor, n_steps: int = 0, lr: float = 0.1,
             angle_lr: float = 0.01, gamma: float = 1.0, momentum: float = 0.0, weight: float = 1.0,
             want=("params", "loss", "best", "all_params", "all_loss", "grad"), max_groups: int = 0, out=None):
@@ -559,23 +569,16 @@ def _lf_run(curve: torch.Tensor, k: int, p: int, prototype: torch.Tensor, starts
     all_params [N, S, 4], all_loss [N, S], grad [N, S, 4], trace [N, S, n_steps, 9]).  k = 0: curve is [N, P, 2] points.
     out: tensors to write into instead of new ones (the tests' guarded buffers)"""
     lib = _lib.load()
-    n, dev, n_starts = curve.shape[0], curve.device, starts.shape[1]
+    n, dev, s = curve.shape[0], curve.device, starts.shape[1]
     with torch.cuda.device(dev):
-        res = {}
-        for name in want:
-            if out is not None and name in out:
-                res[name] = out[name]
-            else:
-                res[name] = torch.empty(_LF_OUT[name](n, n_starts, n_steps), device=dev,
-                                        dtype=torch.int32 if name == "best" else torch.float32)
         desc = _lib.LensFitDesc()
-        desc.x, desc.b_points = (curve.data_ptr(), None) if k else (None, curve.data_ptr())
-        desc.n_rows, desc.n_coeffs, desc.n_points = n, k, p
+        _set_curve(desc, curve, n, k, p)
         desc.a_points, desc.n_template = prototype.data_ptr(), prototype.shape[0]
-        desc.starts, desc.n_starts, desc.n_steps = starts.data_ptr(), n_starts, n_steps
+        desc.starts, desc.n_starts, desc.n_steps = starts.data_ptr(), s, n_steps
         desc.lr, desc.angle_lr, desc.gamma, desc.momentum, desc.weight = lr, angle_lr, gamma, momentum, weight
-        for name in _LF_OUT:
-            setattr(desc, name, res[name].data_ptr() if name in res else None)
+        res = _outputs(desc, dict(params=((n, 4), _F32), loss=((n,), _F32), best=((n,), _I32), all_params=((n, s, 4), _F32),
+                                  all_loss=((n, s), _F32), grad=((n, s, 4), _F32), trace=((n, s, n_steps, 9), _F32)),
+                       want, out, dev)
         desc.max_groups = max_groups
         st = lib.hint_lensfit_run(desc, torch.cuda.current_stream(dev).cuda_stream)
     _lib.check(st, "hint_lensfit_run")

@@ -1,15 +1,18 @@
 #!/usr/bin/env python3
-"""Generate tests/golden/pointset_bits.npz: the output bits of hint_hausdorff_run and hint_plus_run on the cases of
-tests/pointset_cases.py, as the library that is built in the tree computes them on an MI355X.
+"""Extend tests/golden/pointset_bits.npz: the output bits of hint_hausdorff_run, hint_plus_run and hint_lensfit_run on the cases of
+tests/pointset_cases.py, as the library that is built in the tree (or the one HINT_AMD_LIB names) computes them on an MI355X.
 
-Runs at development time only, on a machine with the GPU, at a commit whose bits are the ones to keep:
+Runs at development time only, on a machine with the GPU, with a library whose bits are the ones to keep:
 
     python tests/golden/make_pointset_bits.py [output file]
 
-The fixture was recorded at the last commit at which hint_hausdorff.hip and hint_plus.hip each held their own copy of the walk,
-the trace, the tile loop and the reductions; tests/test_gpu_pointset_bits.py holds every later build to it.  Re-record only for a
-change that is meant to move bits (a change of the contract in include/hint_amd.h), never to make that test pass.  A fixture holds
-data only: per case a sha256 of each input array, max_dist, and the outputs (`points` and `segments` as a sha256).
+Only the cases the fixture does not hold yet are run and recorded; every array it holds is carried over as it is, and the script
+refuses to write a file in which one of them differs.  The hd_* and pl_* cases were recorded at the last commit at which
+hint_hausdorff.hip and hint_plus.hip each held their own copy of the walk, the trace, the tile loop and the reductions (`build`);
+the lf_* cases at the last commit at which hint_lensfit.hip held its own placement and arg-min walk (`build/lensfit`).
+tests/test_gpu_pointset_bits.py holds every later build to them.  Re-record only for a change that is meant to move bits (a change
+of the contract in include/hint_amd.h), never to make that test pass.  A fixture holds data only: per case a sha256 of each input
+array, max_dist, and the outputs (`points` and `segments` as a sha256).
 """
 import os
 import sys
@@ -21,20 +24,43 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
 sys.path.insert(0, os.path.dirname(HERE))
 import pointset_cases as pc  # noqa: E402
 
+FIXTURE = os.path.join(HERE, "pointset_bits.npz")
+BUILD_KEY = {"hd": "build", "pl": "build", "lf": "build/lensfit"}         # by a case name's prefix
+
+
+def same(a, b):
+    return a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
+
 
 def main():
-    path = sys.argv[1] if len(sys.argv) > 1 else os.path.join(HERE, "pointset_bits.npz")
+    path = sys.argv[1] if len(sys.argv) > 1 else FIXTURE
+    old = {}
+    if os.path.exists(FIXTURE):
+        with np.load(FIXTURE) as f:
+            old = {k: f[k] for k in f.files}
+    held = {k.split("/")[0] for k in old}
     from hint_amd import _lib
-    rec = {"build": np.array(_lib.load().hint_build_info().decode())}
-    for name in list(pc.HAUSDORFF) + list(pc.PLUS):
+    build = np.array(_lib.load().hint_build_info().decode())
+    rec = dict(old)
+    for name in list(pc.HAUSDORFF) + list(pc.PLUS) + list(pc.LENSFIT):
+        if name in held:
+            continue
         inp = pc.inputs(name)
         if name in pc.PLUS:
             pc.check_plus_rows(name, inp)                    # before anything is recorded
         out = pc.run(name, inp)
-        rec.update(pc.record(name, inp, out))
+        if name in pc.LENSFIT:                               # a NaN would pin nothing about the arithmetic
+            assert all(np.isfinite(v).all() for v in out.values()), (name, {k: int((~np.isfinite(v)).sum()) for k, v in out.items()})
+        new = pc.record(name, inp, out)
+        new[BUILD_KEY[name[:2]]] = build
+        for k, v in new.items():
+            assert k not in old or same(old[k], v), f"{k} is in the fixture already and would change"
+        rec.update(new)
         print(name, {k: (v.shape, str(v.dtype)) for k, v in out.items()}, "max_dist", inp.get("max_dist"))
     np.savez_compressed(path, **rec)
-    print(f"{path}: {os.path.getsize(path)} bytes, {len(rec)} arrays; {rec['build']}")
+    with np.load(path) as f:
+        assert set(old) <= set(f.files) and all(same(f[k], v) for k, v in old.items()), "an array of the fixture changed"
+        print(f"{path}: {os.path.getsize(path)} bytes, {len(f.files)} arrays ({len(old)} carried over)")
 
 
 if __name__ == "__main__":

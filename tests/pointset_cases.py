@@ -1,7 +1,7 @@
-"""The cases of tests/golden/pointset_bits.npz: small launches of hint_hausdorff_run and hint_plus_run whose output bits were
-recorded once (tests/golden/make_pointset_bits.py) and must never move again (tests/test_gpu_pointset_bits.py).  Every operation
-of both kernels is a correctly rounded intrinsic in an order that include/hint_amd.h fixes, so a change that only moves code
-changes no bit.
+"""The cases of tests/golden/pointset_bits.npz: small launches of hint_hausdorff_run, hint_plus_run and hint_lensfit_run whose
+output bits were recorded once (tests/golden/make_pointset_bits.py) and must never move again (tests/test_gpu_pointset_bits.py).
+Every operation of the three kernels is a correctly rounded intrinsic in an order that include/hint_amd.h fixes, so a change that
+only moves code changes no bit.
 
 Every case has 5 rows on 2 workgroups: a workgroup takes 2-3 rows in turn and reuses its LDS between them.  The inputs come from
 the oracles' seeded generators; the fixture keeps a sha256 of each, so that a drift of a generator is reported as such and not as
@@ -9,13 +9,17 @@ a change of the kernels.  Hausdorff (K, P, M): every K of 1, 5, 25; every P of 2
 thread to two), 1000, 1024; every M of 1, 1023, 1024, 1025 (around one LDS tile), 4096, the ragged case all five at once.  Plus:
 the same K and P; max_dist steers the largest row's outline to one tile to the point, to one tile and two points (an outline's
 edges come in pairs of equal count, so its size is always even: 1025 does not exist), to more than three tiles and to the most a
-row may have, next to a row that is past it."""
+row may have, next to a row that is past it.  Lens fit (K, P, M, S starts, n_steps, weight): every K of 0 (given points), 1, 5, 25;
+every number 1..4 of points a thread holds of the curve (P = 2, 100 / 257 / 600 / 1024) and of the prototype (M = 1, 130 / 300 /
+700 / 1023, 1024); 1, 2 and 16 starts; the evaluation alone (n_steps 0, no trace), one step and five; both weights; all outputs,
+and params and loss alone."""
 import hashlib
 
 import numpy as np
 
 import curve_oracle as co
 import hausdorff_oracle as ho
+import lensfit_oracle as lo
 import plus_oracle as po
 
 ROWS, GROUPS = 5, 2
@@ -41,6 +45,16 @@ PLUS = {
     "pl_k5_p1024_m1024": (16, 5, 1024, 1024, {}, None, PLUS_ALL),
     "pl_k25_p100_loss_alone": (17, 25, 100, 1026, {}, None, ("loss",)),
 }
+LENSFIT_ALL = ("params", "loss", "best", "all_params", "all_loss", "grad", "trace")
+# name -> (seed, K (0: given points), P, M, starts, n_steps, weight, the curve's generator, outputs)
+LENSFIT = {
+    "lf_k1_p2_m1_s1_eval": (21, 1, 2, 1, 1, 0, 1.0, "gauss", LENSFIT_ALL[:-1]),        # (n_steps 0 has no trace)
+    "lf_k5_p100_m130_s2_n5": (22, 5, 100, 130, 2, 5, 1.0, "lens", LENSFIT_ALL),
+    "lf_k25_p257_m1023_s16_n1_w025": (23, 25, 257, 1023, 16, 1, 0.25, "gauss", LENSFIT_ALL),
+    "lf_given_p1024_m1024_s2_n5": (24, 0, 1024, 1024, 2, 5, 1.0, "lens", LENSFIT_ALL),
+    "lf_k5_p600_m300_s1_n1_w025": (25, 5, 600, 300, 1, 1, 0.25, "gauss", LENSFIT_ALL),
+    "lf_k5_p100_m700_s2_n5_params_loss_alone": (26, 5, 100, 700, 2, 5, 1.0, "lens", ("params", "loss")),
+}
 HASHED = ("points", "segments")          # outputs the fixture keeps as a sha256
 
 
@@ -63,6 +77,12 @@ def inputs(name):
         if mode == "params":
             inp["params"] = ho.golden_params(seed, ROWS)
         return inp
+    if name in LENSFIT:
+        seed, K, P, M, S, _, _, gen, _ = LENSFIT[name]
+        x = lo.lens_rows(400 + seed, ROWS, K or 5) if gen == "lens" else co.gauss(400 + seed, ROWS, K or 5)
+        return dict(curve=x if K else co.points64(x, P).astype(np.float32),
+                    prototype=lo.lens_prototype(M) if M > 1 else np.array([[0.75, -0.5]], np.float32),
+                    starts=lo.golden_grad_params(seed, ROWS * S).reshape(ROWS, S, 4))
     seed, K, P, size, zero, over, _ = PLUS[name]
     pr = po.draw_params(200 + seed, ROWS, (), zero=zero)
     if over is not None:
@@ -95,6 +115,10 @@ def run(name, inp):
         out = curves._hd_run(dev(inp["curve"]), K, P, t("template"), t("offsets"), t("params"), want_h=M is not None,
                              want_chamfer=M is not None, want_points=K > 0, max_groups=GROUPS)
         out = dict(zip(("max_h", "avg_h", "chamfer", "points"), out))
+    elif name in LENSFIT:
+        _, K, P, _, _, n_steps, w, _, want = LENSFIT[name]
+        out = curves._lf_run(dev(inp["curve"]), K, P, dev(inp["prototype"]), dev(inp["starts"]), n_steps, lo.LR, lo.ANGLE_LR,
+                             lo.GAMMA, lo.MOMENTUM, w, want, GROUPS)
     else:
         _, K, P, _, _, _, want = PLUS[name]
         out = curves._plus_run(dev(inp["params"]), dev(inp["curve"]), K, P, float(inp["max_dist"]), want, GROUPS)

@@ -184,7 +184,7 @@ def test_python_argument_errors():
     for bad, what in (("a", "noise must be a number"), (None, "noise must be a number"), (float("nan"), "noise must be finite"),
                       (float("inf"), "noise must be finite")):
         with pytest.raises(HintAmdError, match="target_distances: " + what):
-            curves._check_noise(bad, "target_distances")
+            curves._check_real(bad, "noise", "target_distances", nonneg=False)
     for bad in (torch.randn(3), torch.randn(2, 3), torch.randn(7, 2), torch.randn(1, 1, 2)):
         with pytest.raises(HintAmdError, match=r"mean_target_distance: y_target must have shape \[2\], \[1, 2\] or \[50, 2\]"):
             curves._check_target(bad, 50, "cpu", "mean_target_distance")

@@ -1,6 +1,7 @@
-"""hint_hausdorff_run and hint_plus_run give, on the cases of tests/pointset_cases.py, the bits that tests/golden/pointset_bits.npz
-recorded before the two kernels were built from one shared core (hint_amd/csrc/hint_pointset.hpp): every output compared as
-int32 words, exactly.  A generator that drifted is told apart from a kernel that did: the fixture holds a sha256 of every input."""
+"""hint_hausdorff_run, hint_plus_run and hint_lensfit_run give, on the cases of tests/pointset_cases.py, the bits that
+tests/golden/pointset_bits.npz recorded before each kernel was built from the shared core (hint_amd/csrc/hint_pointset.hpp):
+every output compared as int32 words, exactly.  A generator that drifted is told apart from a kernel that did: the fixture holds
+a sha256 of every input."""
 import os
 
 import numpy as np
@@ -12,19 +13,30 @@ pytestmark = pytest.mark.gpu
 
 PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "pointset_bits.npz")
 GOLD = np.load(PATH)
+NAMES = list(pc.HAUSDORFF) + list(pc.PLUS) + list(pc.LENSFIT)
 
 
 def test_the_fixture_holds_every_case_and_is_small():
-    names = list(pc.HAUSDORFF) + list(pc.PLUS)
-    assert {k.split("/")[0] for k in GOLD.files} == set(names) | {"build"}
+    assert {k.split("/")[0] for k in GOLD.files} == set(NAMES) | {"build"}
     assert os.path.getsize(PATH) < 64 << 10
     assert {v[1] for v in pc.HAUSDORFF.values()} == {0, 1, 5, 25} and {v[1] for v in pc.PLUS.values()} == {1, 5, 25}
     for cases in (pc.HAUSDORFF, pc.PLUS):
         assert {v[2] for v in cases.values()} == {2, 100, 256, 257, 1000, 1024}
     assert {v[3] for v in pc.HAUSDORFF.values()} | set(pc.RAGGED) == {None, 1, 1023, 1024, 1025, 4096, sum(pc.RAGGED)}
+    lf = list(pc.LENSFIT.values())
+    assert (pc.ROWS, pc.GROUPS) == (5, 2) and {v[1] for v in lf} == {0, 1, 5, 25}
+    per = lambda n: -(-n // 256)                                                   # noqa: E731  points a thread holds
+    assert {per(v[2]) for v in lf} == {1, 2, 3, 4} == {per(v[3]) for v in lf}
+    assert {(2, 1), (100, 130), (257, 1023), (1024, 1024)} <= {(v[2], v[3]) for v in lf}
+    assert {v[4] for v in lf} == {1, 2, 16} and {v[5] for v in lf} == {0, 1, 5} and {v[6] for v in lf} == {1.0, 0.25}
+    assert all(("trace" in v[8]) == (v[5] > 0) for v in lf if len(v[8]) > 2)       # n_steps 0 has no trace
+    full = [v for v in lf if set(v[8]) >= set(pc.LENSFIT_ALL[:-1])]
+    assert len(full) >= len(lf) - 1 and any(v[8] == pc.LENSFIT_ALL for v in lf) and ("params", "loss") in {v[8] for v in lf}
+    for name in pc.LENSFIT:                                                        # a NaN would pin nothing about the arithmetic
+        assert all(np.isfinite(GOLD[k]).all() for k in GOLD.files if k.startswith(f"{name}/out/"))
 
 
-@pytest.mark.parametrize("name", list(pc.HAUSDORFF) + list(pc.PLUS))
+@pytest.mark.parametrize("name", NAMES)
 def test_output_bits_are_the_recorded_ones(name):
     inp = pc.inputs(name)
     for k, v in inp.items():

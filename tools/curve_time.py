@@ -13,14 +13,11 @@ own under a time limit, and a size that fails ends the run: nothing more is star
 warmed up, every repetition is bracketed by HIP events on the current stream, and the medians, quartiles and extremes are
 printed and written, with the library's build string and the commit.
 """
-import argparse
-import json
 import math
 import os
-import subprocess
 import sys
 
-from _timing import commit_of_tree, stats
+from _timing import alternate, commit_of_tree, drive, emit_row, parser, print_stats, stats
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SIZES = ((4000, 30), (1 << 20, 10), (1 << 24, 3))          # (rows, repetitions)
@@ -61,25 +58,7 @@ def one_size(n, reps, warmup):
 
     routes = {"fused": lambda: hint_amd.target_distances(x, t, 0.0), "torch": torch_route}
 
-    def timed(fn):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        out = fn()
-        b.record()
-        b.synchronize()
-        return a.elapsed_time(b) * 1e3, out          # microseconds
-
-    for _ in range(warmup):
-        for fn in routes.values():
-            fn()
-    torch.cuda.synchronize()
-    us = {name: [] for name in routes}
-    outs = {}
-    for _ in range(reps):                            # alternate: clocks and caches drift for both routes alike
-        for name, fn in routes.items():
-            dt, out = timed(fn)
-            us[name].append(dt)
-            outs[name] = out
+    us, outs = alternate(routes, reps, warmup)
     lib = _lib.load()
     row = {name: stats(v) for name, v in us.items()}
     # the two choose the same pair except where the maximum is nearly tied (cdist's rounding is its own)
@@ -87,47 +66,21 @@ def one_size(n, reps, warmup):
     row["workgroups"], row["rows_per_tile"], row["rows_per_wavefront"] = (int(lib.hint_curve_geometry(n, K, P, f)) for f in range(3))
     row["fused_rows_per_second"] = n / (row["fused"]["median_us"] * 1e-6)
     row["torch_over_fused"] = row["torch"]["median_us"] / row["fused"]["median_us"]
-    row["device"] = torch.cuda.get_device_name(0)
-    row["build"] = lib.hint_build_info().decode()
-    return row
+    return emit_row(row, lib)
+
+
+def summary(n, row):
+    print_stats(n, row, ("fused", "torch"))
+    print(f"N={n} torch / fused = {row['torch_over_fused']:.2f}; fused {row['fused_rows_per_second'] / 1e9:.3f} G rows/s on "
+          f"{row['workgroups']} workgroups; {row['rows_within_1e-4_of_torch']} of {n} distances within 1e-4 of torch's")
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "curve_time.json"))
-    ap.add_argument("--commit", default=None, help="the commit the tree was built from (default: git rev-parse HEAD)")
-    ap.add_argument("--one", type=int, default=0, help="(internal) time this N and print its JSON row")
-    ap.add_argument("--reps", type=int, default=0, help="(internal) repetitions of --one")
-    args = ap.parse_args()
+    args = parser("curve_time.json", 3).parse_args()
     if args.one:
-        print("ROW " + json.dumps(one_size(args.one, args.reps, args.warmup)))
-        return 0
+        return one_size(args.one, args.reps, args.warmup)
     res = {"n_coeffs": K, "n_points": P, "torch_chunk_rows": CHUNK, "commit": args.commit or commit_of_tree(), "shapes": {}}
-    for n, reps in SIZES:
-        try:
-            p = subprocess.run([sys.executable, os.path.abspath(__file__), "--one", str(n), "--reps", str(reps), "--warmup",
-                                str(args.warmup)], capture_output=True, text=True, timeout=LIMIT_S)
-        except subprocess.TimeoutExpired:
-            print(f"N={n}: no result within {LIMIT_S} s; stopping")
-            return 1
-        rows = [ln[4:] for ln in p.stdout.splitlines() if ln.startswith("ROW ")]
-        if p.returncode != 0 or not rows:
-            print(f"N={n}: exit status {p.returncode}; stopping\n{p.stdout[-2000:]}\n{p.stderr[-2000:]}")
-            return 1
-        row = json.loads(rows[-1])
-        res["device"], res["build"] = row.pop("device"), row.pop("build")
-        res["shapes"][str(n)] = row
-        for name in ("fused", "torch"):
-            s = row[name]
-            print(f"N={n} {name:6s} median {s['median_us']:12.1f} us  quartiles {s['q1_us']:.1f} .. {s['q3_us']:.1f}  "
-                  f"range {s['min_us']:.1f} .. {s['max_us']:.1f}  ({s['reps']} repetitions)")
-        print(f"N={n} torch / fused = {row['torch_over_fused']:.2f}; fused {row['fused_rows_per_second'] / 1e9:.3f} G rows/s on "
-              f"{row['workgroups']} workgroups; {row['rows_within_1e-4_of_torch']} of {n} distances within 1e-4 of torch's")
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        json.dump(res, open(args.out, "w"), indent=1)
-    print("wrote", args.out)
-    return 0
+    return drive(__file__, LIMIT_S, [(n, ("--reps", reps, "--warmup", args.warmup)) for n, reps in SIZES], res, args.out, summary)
 
 
 if __name__ == "__main__":

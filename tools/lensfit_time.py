@@ -18,14 +18,11 @@ it.  Both routes are warmed up, every repetition is bracketed by HIP events on t
 extremes are printed and written, with the library's build string and the commit.  The reference's own host loop is not timed
 here (DESIGN section 16 quotes it from a CPU run).
 """
-import argparse
-import json
 import math
 import os
-import subprocess
 import sys
 
-from _timing import commit_of_tree, stats
+from _timing import alternate, commit_of_tree, drive, emit_row, parser, print_stats, stats
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SIZES = ((1000, 10), (1 << 16, 3))          # (rows, repetitions)
@@ -97,30 +94,16 @@ def one_size(n, reps, warmup):
 
     routes = {"fused": lambda: hint_amd.fit_lens_shapes(x, proto), "torch": torch_route}
 
-    def timed(fn):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        out = fn()
-        b.record()
-        b.synchronize()
-        return a.elapsed_time(b) * 1e3, out          # microseconds
+    peak = {}
 
-    for _ in range(warmup):
-        for fn in routes.values():
-            fn()
-    torch.cuda.synchronize()
-    torch.cuda.reset_peak_memory_stats()
-    base = torch.cuda.memory_allocated()
-    routes["fused"]()
-    torch.cuda.synchronize()
-    fused_peak = int(torch.cuda.max_memory_allocated() - base)
-    us = {name: [] for name in routes}
-    outs = {}
-    for _ in range(reps):                            # alternate: clocks and caches drift for both routes alike
-        for name, fn in routes.items():
-            dt, out = timed(fn)
-            us[name].append(dt)
-            outs[name] = out
+    def fused_peak():
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        routes["fused"]()
+        torch.cuda.synchronize()
+        peak["fused"] = int(torch.cuda.max_memory_allocated() - base)
+
+    us, outs = alternate(routes, reps, warmup, fused_peak)
     lib = _lib.load()
     row = {name: stats(v) for name, v in us.items()}
     row["max_abs_difference_loss"] = float((outs["fused"][1] - outs["torch"][1]).abs().max())
@@ -130,52 +113,26 @@ def one_size(n, reps, warmup):
     row["fused_pairs_per_second"] = 2.0 * n * STARTS * STEPS * P * M / (row["fused"]["median_us"] * 1e-6)
     row["fused_us_per_row"] = row["fused"]["median_us"] / n
     row["torch_over_fused"] = row["torch"]["median_us"] / row["fused"]["median_us"]
-    row["fused_peak_bytes_above_inputs"] = fused_peak
+    row["fused_peak_bytes_above_inputs"] = peak["fused"]
     row["torch_peak_bytes"] = int(torch.cuda.max_memory_allocated())
-    row["device"] = torch.cuda.get_device_name(0)
-    row["build"] = lib.hint_build_info().decode()
-    return row
+    return emit_row(row, lib)
+
+
+def summary(n, row):
+    print_stats(n, row, ("fused", "torch"))
+    print(f"N={n} torch / fused = {row['torch_over_fused']:.2f}; fused {row['fused_us_per_row']:.2f} us a row, "
+          f"{row['fused_pairs_per_second'] / 1e12:.3f} T pair visits/s on {row['workgroups']} workgroups, "
+          f"{row['fused_peak_bytes_above_inputs']} bytes allocated above its inputs (torch route: peak {row['torch_peak_bytes']}); "
+          f"the loss differs from torch's by at most {row['max_abs_difference_loss']:.3g} (median loss {row['median_loss']:.3g})")
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "lensfit_time.json"))
-    ap.add_argument("--commit", default=None, help="the commit the tree was built from (default: git rev-parse HEAD)")
-    ap.add_argument("--one", type=int, default=0, help="(internal) time this N and print its JSON row")
-    ap.add_argument("--reps", type=int, default=0, help="(internal) repetitions of --one")
-    args = ap.parse_args()
+    args = parser("lensfit_time.json", 1).parse_args()
     if args.one:
-        print("ROW " + json.dumps(one_size(args.one, args.reps, args.warmup)))
-        return 0
+        return one_size(args.one, args.reps, args.warmup)
     res = {"n_coeffs": K, "n_points": P, "prototype_points": M, "starts": STARTS, "steps": STEPS, "torch_chunk_rows": CHUNK,
            "commit": args.commit or commit_of_tree(), "shapes": {}}
-    for n, reps in SIZES:
-        try:
-            p = subprocess.run([sys.executable, os.path.abspath(__file__), "--one", str(n), "--reps", str(reps), "--warmup",
-                                str(args.warmup)], capture_output=True, text=True, timeout=LIMIT_S)
-        except subprocess.TimeoutExpired:
-            print(f"N={n}: no result within {LIMIT_S} s; stopping")
-            return 1
-        rows = [ln[4:] for ln in p.stdout.splitlines() if ln.startswith("ROW ")]
-        if p.returncode != 0 or not rows:
-            print(f"N={n}: exit status {p.returncode}; stopping\n{p.stdout[-2000:]}\n{p.stderr[-2000:]}")
-            return 1
-        row = json.loads(rows[-1])
-        res["device"], res["build"] = row.pop("device"), row.pop("build")
-        res["shapes"][str(n)] = row
-        for name in ("fused", "torch"):
-            s = row[name]
-            print(f"N={n} {name:6s} median {s['median_us']:12.1f} us  quartiles {s['q1_us']:.1f} .. {s['q3_us']:.1f}  "
-                  f"range {s['min_us']:.1f} .. {s['max_us']:.1f}  ({s['reps']} repetitions)")
-        print(f"N={n} torch / fused = {row['torch_over_fused']:.2f}; fused {row['fused_us_per_row']:.2f} us a row, "
-              f"{row['fused_pairs_per_second'] / 1e12:.3f} T pair visits/s on {row['workgroups']} workgroups, "
-              f"{row['fused_peak_bytes_above_inputs']} bytes allocated above its inputs (torch route: peak {row['torch_peak_bytes']}); "
-              f"the loss differs from torch's by at most {row['max_abs_difference_loss']:.3g} (median loss {row['median_loss']:.3g})")
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        json.dump(res, open(args.out, "w"), indent=1)
-    print("wrote", args.out)
-    return 0
+    return drive(__file__, LIMIT_S, [(n, ("--reps", reps, "--warmup", args.warmup)) for n, reps in SIZES], res, args.out, summary)
 
 
 if __name__ == "__main__":

@@ -14,7 +14,7 @@ import sys
 
 import torch
 
-from _timing import stats
+from _timing import alternate, stats
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -38,15 +38,6 @@ def torch_formulation(x, y, kernels=KERNELS):
     return torch.mean(kxx + kyy - 2. * kxy)
 
 
-def timed(fn):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    out = fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b) * 1e3, out          # microseconds
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=200)
@@ -63,17 +54,8 @@ def main():
         gt = hint_amd.MultiMMD(y)
         routes = {"fused": lambda: hint_amd.multi_mmd(x, y), "fused_yy_kept": lambda: gt.mmd(x),
                   "torch": lambda: torch_formulation(x, y)}
-        for _ in range(args.warmup):
-            for fn in routes.values():
-                fn()
-        torch.cuda.synchronize()
-        us = {k: [] for k in routes}
-        vals = {}
-        for _ in range(args.reps):                 # alternate: clocks and caches drift for all routes alike
-            for k, fn in routes.items():
-                t, out = timed(fn)
-                us[k].append(t)
-                vals[k] = float(out)
+        us, outs = alternate(routes, args.reps, args.warmup)
+        vals = {k: float(v) for k, v in outs.items()}
         row = {k: stats(v) for k, v in us.items()}
         row["values"] = vals
         row["torch_over_fused"] = row["torch"]["median_us"] / row["fused"]["median_us"]

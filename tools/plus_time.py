@@ -18,15 +18,12 @@ in a child process of its own under a time limit, and a size that fails ends the
 it.  The device routes are warmed up, every repetition is bracketed by HIP events on the current stream, and the medians,
 quartiles and extremes are printed and written, with the library's build string and the commit.
 """
-import argparse
-import json
 import math
 import os
-import subprocess
 import sys
 import time
 
-from _timing import commit_of_tree, stats
+from _timing import alternate, commit_of_tree, drive, emit_row, parser, print_stats, stats, timed
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SIZES = ((1000, 20, 3), (1 << 16, 5, 1))          # (rows, repetitions of the device routes, of the host route)
@@ -127,28 +124,10 @@ def one_size(n, reps, host_reps, warmup):
         tpl = np.concatenate(rows).astype(np.float32)
         return tpl, offsets, (time.perf_counter() - t0) * 1e6
 
-    def timed(fn):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        out = fn()
-        b.record()
-        b.synchronize()
-        return a.elapsed_time(b) * 1e3, out          # microseconds
-
     routes = {"fused_hausdorff": lambda: hint_amd.plus_hausdorff_distances(x, params, max_dist=MAX_DIST, n_points=P),
               "torch_hausdorff": torch_hausdorff,
               "fused_loss": lambda: hint_amd.plus_fit_loss(x, params), "torch_loss": torch_loss}
-    for _ in range(warmup):
-        for fn in routes.values():
-            fn()
-    torch.cuda.synchronize()
-    us = {name: [] for name in routes}
-    outs = {}
-    for _ in range(reps):                            # alternate: clocks and caches drift for all routes alike
-        for name, fn in routes.items():
-            dt, out = timed(fn)
-            us[name].append(dt)
-            outs[name] = out
+    us, outs = alternate(routes, reps, warmup)
     # the ragged route: the host loop, then upload and launch
     host_us, dev_us = [], []
     for _ in range(host_reps):
@@ -175,52 +154,28 @@ def one_size(n, reps, host_reps, warmup):
     row["ragged_device_over_fused"] = row["ragged_device"]["median_us"] / row["fused_hausdorff"]["median_us"]
     row["ragged_host_over_fused"] = row["ragged_host"]["median_us"] / row["fused_hausdorff"]["median_us"]
     row["torch_peak_bytes"] = int(torch.cuda.max_memory_allocated())
-    row["device"] = torch.cuda.get_device_name(0)
-    row["build"] = lib.hint_build_info().decode()
-    return row
+    return emit_row(row, lib)
+
+
+def summary(n, row):
+    print_stats(n, row, ("fused_hausdorff", "torch_hausdorff", "ragged_host", "ragged_device", "fused_loss", "torch_loss"), 16, 14)
+    print(f"N={n} torch / fused: distances {row['torch_over_fused_hausdorff']:.2f}, loss {row['torch_over_fused_loss']:.2f}; ragged "
+          f"route / fused: device {row['ragged_device_over_fused']:.2f}, host {row['ragged_host_over_fused']:.1f}; "
+          f"{row['outline_points_mean']:.0f} outline points a row, {row['rows_served']} of {n} rows served; max_h differs from "
+          f"torch's by at most {row['max_abs_difference_max_h_torch']:.3g}, from the ragged route's by "
+          f"{row['max_abs_difference_max_h_ragged']:.3g}; the loss from torch's by {row['max_abs_difference_loss_torch']:.3g}")
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "plus_time.json"))
-    ap.add_argument("--commit", default=None, help="the commit the tree was built from (default: git rev-parse HEAD)")
-    ap.add_argument("--one", type=int, default=0, help="(internal) time this N and print its JSON row")
-    ap.add_argument("--reps", type=int, default=0, help="(internal) repetitions of --one")
+    ap = parser("plus_time.json", 3)
     ap.add_argument("--host-reps", type=int, default=1, help="(internal) repetitions of the host route of --one")
     args = ap.parse_args()
     if args.one:
-        print("ROW " + json.dumps(one_size(args.one, args.reps, args.host_reps, args.warmup)))
-        return 0
+        return one_size(args.one, args.reps, args.host_reps, args.warmup)
     res = {"n_coeffs": K, "n_points": P, "n_points_loss": P_FIT, "max_dist": MAX_DIST, "torch_chunk_rows": CHUNK,
            "commit": args.commit or commit_of_tree(), "shapes": {}}
-    for n, reps, host_reps in SIZES:
-        try:
-            p = subprocess.run([sys.executable, os.path.abspath(__file__), "--one", str(n), "--reps", str(reps), "--host-reps",
-                                str(host_reps), "--warmup", str(args.warmup)], capture_output=True, text=True, timeout=LIMIT_S)
-        except subprocess.TimeoutExpired:
-            print(f"N={n}: no result within {LIMIT_S} s; stopping")
-            return 1
-        rows = [ln[4:] for ln in p.stdout.splitlines() if ln.startswith("ROW ")]
-        if p.returncode != 0 or not rows:
-            print(f"N={n}: exit status {p.returncode}; stopping\n{p.stdout[-2000:]}\n{p.stderr[-2000:]}")
-            return 1
-        row = json.loads(rows[-1])
-        res["device"], res["build"] = row.pop("device"), row.pop("build")
-        res["shapes"][str(n)] = row
-        for name in ("fused_hausdorff", "torch_hausdorff", "ragged_host", "ragged_device", "fused_loss", "torch_loss"):
-            s = row[name]
-            print(f"N={n} {name:16s} median {s['median_us']:14.1f} us  quartiles {s['q1_us']:.1f} .. {s['q3_us']:.1f}  "
-                  f"range {s['min_us']:.1f} .. {s['max_us']:.1f}  ({s['reps']} repetitions)")
-        print(f"N={n} torch / fused: distances {row['torch_over_fused_hausdorff']:.2f}, loss {row['torch_over_fused_loss']:.2f}; ragged "
-              f"route / fused: device {row['ragged_device_over_fused']:.2f}, host {row['ragged_host_over_fused']:.1f}; "
-              f"{row['outline_points_mean']:.0f} outline points a row, {row['rows_served']} of {n} rows served; max_h differs from "
-              f"torch's by at most {row['max_abs_difference_max_h_torch']:.3g}, from the ragged route's by "
-              f"{row['max_abs_difference_max_h_ragged']:.3g}; the loss from torch's by {row['max_abs_difference_loss_torch']:.3g}")
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        json.dump(res, open(args.out, "w"), indent=1)
-    print("wrote", args.out)
-    return 0
+    sizes = [(n, ("--reps", reps, "--host-reps", host_reps, "--warmup", args.warmup)) for n, reps, host_reps in SIZES]
+    return drive(__file__, LIMIT_S, sizes, res, args.out, summary)
 
 
 if __name__ == "__main__":

@@ -18,5 +18,6 @@ from .curves import chamfer_distances, hausdorff_distances, lens_fit_loss, trace
 from .curves import (plus_fit_loss, plus_fit_terms, plus_hausdorff_distances, plus_outline_counts,  # noqa: F401,E402
                      plus_segments)
 from .curves import fit_lens_shapes, lens_fit_grad, lens_fit_starts  # noqa: F401,E402
+from .curves import fit_plus_shapes, plus_dominant_angle, plus_fit_grad, plus_fit_starts  # noqa: F401,E402
 
 __version__ = "0.1.0"

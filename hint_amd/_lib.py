@@ -75,6 +75,17 @@ class LensFitDesc(C.Structure):
                 ("grad", C.c_void_p), ("trace", C.c_void_p), ("max_groups", C.c_int32)]
 
 
+class PlusFitDesc(C.Structure):
+    """mirror of `hint_plusfit_desc` (include/hint_amd.h)"""
+    _fields_ = [("x", C.c_void_p), ("b_points", C.c_void_p), ("n_rows", C.c_int64), ("n_coeffs", C.c_int32),
+                ("n_points", C.c_int32), ("starts", C.c_void_p), ("n_starts", C.c_int32), ("n_steps", C.c_int32),
+                ("lr", C.c_double), ("angle_lr", C.c_double), ("gamma", C.c_double), ("momentum", C.c_double),
+                ("corner_weight", C.c_double), ("stop_loss", C.c_double), ("corner_decay", C.c_int32),
+                ("max_groups", C.c_int32), ("params", C.c_void_p), ("loss", C.c_void_p), ("best", C.c_void_p),
+                ("n_run", C.c_void_p), ("all_params", C.c_void_p), ("all_loss", C.c_void_p), ("grad", C.c_void_p),
+                ("trace", C.c_void_p)]
+
+
 _lib = None
 
 _PROTOS = {
@@ -160,6 +171,9 @@ _PROTOS = {
     "hint_lensfit_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32]),
     "hint_lensfit_run": (C.c_int, [C.POINTER(LensFitDesc), C.c_void_p]),
     "hint_lensfit_geometry": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
+    "hint_plusfit_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "hint_plusfit_run": (C.c_int, [C.POINTER(PlusFitDesc), C.c_void_p]),
+    "hint_plusfit_geometry": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
 }
 
 

@@ -10,10 +10,11 @@
 // hint_plus_kernel: the shape of hint_hausdorff_kernel - a persistent grid of G workgroups of 256 threads; workgroup w takes rows
 // w, w + G, ... one at a time; the twiddle table once per workgroup - built from the same core (hint_pointset.hpp: the trace, the
 // two-pass walk, the reductions), with a template that exists nowhere in memory:
-//   - per row, thread 0 turns the 9 parameters into the 8 clamped coordinates, cs, sn (double sincos, not inlined) and a finite
-//     flag in LDS; lanes 0..11 of wavefront 0 then each take one segment: its two local vertices (picked from the 8 coordinates by
-//     two packed index tables), the keep bit, the two placed vertices (written to `segments`), the loss's constants (a, n, L) and
-//     the outline's count (one double division); a ballot gives `keep`, a 12-lane shuffle scan the prefix sums of the counts;
+//   - per row (the geometry: hint_plusgeom.hpp, shared with hint_plusfit.hip), thread 0 turns the 9 parameters into the 8 clamped
+//     coordinates, cs, sn (double sincos, not inlined) and a finite flag in LDS; lanes 0..11 of wavefront 0 then each take one
+//     segment: its two local vertices (picked from the 8 coordinates by two packed index tables), the keep bit, the two placed
+//     vertices (written to `segments`), the loss's constants (a, n, L) and the outline's count (one double division); a ballot
+//     gives `keep`, a 12-lane shuffle scan the prefix sums of the counts;
 //   - B is traced or loaded into LDS (ps_stage_curve); each thread then holds its <= 4 B points in registers;
 //   - loss: the thread walks the kept segments (constants from LDS, every read a wavefront broadcast) over its own B points and
 //     keeps min_s d^2; the corner term is 12 workgroup-wide minima (thread, six xor-shuffles, four wavefronts through LDS);
@@ -22,68 +23,14 @@
 //   - ps_block_reduce over the two root sums, the segment term and the maximum.
 // Nothing is carried from row to row and no output is read back.  No float atomics, no counters, no workspace.  Untuned defaults
 // (tile size, points per thread, grid cap, prefix search, the serial parameter stage): DESIGN section 15.
-#include "hint_pointset.hpp"
+#include "hint_plusgeom.hpp"
 
 namespace hint {
 
 constexpr int PL_MAX_WG = 1024;                 // the grid cap: 256 CUs x 4 workgroups (113 VGPRs: 4 wavefronts a SIMD)
 constexpr double PL_Q_CAP = 8192.0;             // a quotient is cut here before it becomes an integer (12 x 8192 fits an int)
 
-// which of the 8 coordinates (0 xleft, 1 yleft, 2 yright, 3 xright; 4 xtop, 5 ytop, 6 xbottom, 7 ybottom) vertex s takes, 4 bits
-// a vertex
-constexpr unsigned long long PL_VX = 0x011223322110ULL;   // s = 0 is the lowest nibble: 0 1 1 2 2 3 3 2 2 1 1 0
-constexpr unsigned long long PL_VY = 0x667766445544ULL;   // 4 4 5 5 4 4 6 6 7 7 6 6
-
 }  // namespace hint
-
-// a row's state in LDS
-struct pl_row {
-    float c[8];                                  // the clamped coordinates, in the order of PL_VX / PL_VY
-    float cs, sn, xo, yo;
-    int finite;                                  // all 9 parameters are
-    float2 W[13];                                // placed vertices, W[12] = W[0]
-    float2 a[12], n[12];                         // per segment: first vertex, unit direction
-    float L[12];
-    int pre[16];                                 // exclusive prefix sums of the counts; pre[12] = M, pre[13..15] = INT_MAX
-    int keep, nk, M, bad;
-};
-
-// the row's 8 coordinates, cs, sn and the offsets to LDS, by one thread.  Not inlined, as ps_stage_pose and for the same
-// reason: the double-precision sincos holds some thirty registers of constants
-__device__ __noinline__ void pl_stage_params(const float* pr, pl_row* rw) {
-    const float xlength = pr[0], ylength = pr[1], xwidth = pr[2], ywidth = pr[3], xshift = pr[4], yshift = pr[5];
-    const float hxl = __fmul_rn(0.5f, xlength), hyl = __fmul_rn(0.5f, ylength);
-    const float xtop = __fmul_rn(0.5f, xwidth), xbottom = -xtop, yright = __fmul_rn(0.5f, ywidth), yleft = -yright;
-    float xleft = __fsub_rn(xshift, hxl), xright = __fadd_rn(xshift, hxl);
-    float ybottom = __fsub_rn(yshift, hyl), ytop = __fadd_rn(yshift, hyl);
-    const float c = 0.01f;
-    xleft = fminf(xleft, __fsub_rn(yleft, c));
-    xright = fmaxf(xright, __fadd_rn(yright, c));
-    ytop = fmaxf(ytop, __fadd_rn(xtop, c));
-    ybottom = fminf(ybottom, __fsub_rn(xbottom, c));
-    rw->c[0] = xleft;
-    rw->c[1] = yleft;
-    rw->c[2] = yright;
-    rw->c[3] = xright;
-    rw->c[4] = xtop;
-    rw->c[5] = ytop;
-    rw->c[6] = xbottom;
-    rw->c[7] = ybottom;
-    double sn, cs;
-    sincos((double)pr[8], &sn, &cs);
-    rw->cs = (float)cs;
-    rw->sn = (float)sn;
-    rw->xo = pr[6];
-    rw->yo = pr[7];
-    bool fin = true;
-    for (int i = 0; i < 9; ++i) fin = fin && isfinite(pr[i]);
-    rw->finite = fin ? 1 : 0;
-}
-
-__device__ __forceinline__ float2 pl_place(float vx, float vy, float cs, float sn, float xo, float yo) {
-    const float qx = __fmaf_rn(-vy, sn, __fmul_rn(vx, cs)), qy = __fmaf_rn(vy, cs, __fmul_rn(vx, sn));
-    return make_float2(__fadd_rn(qx, xo), __fadd_rn(qy, yo));
-}
 
 __global__ __launch_bounds__(256) void hint_plus_kernel(const float* __restrict__ x, const float* __restrict__ b_points, int n,
                                                         int K, int P, const float* __restrict__ params, float max_dist,
@@ -109,12 +56,10 @@ __global__ __launch_bounds__(256) void hint_plus_kernel(const float* __restrict_
         __syncthreads();
         // ---- the twelve segments, one a lane of wavefront 0 ----
         if (wv == 0) {
-            const int s = l < 12 ? l : 0, s1 = s == 11 ? 0 : s + 1;
-            const float cs = rw.cs, sn = rw.sn, xo = rw.xo, yo = rw.yo;
-            const float v0x = rw.c[(PL_VX >> (4 * s)) & 15], v0y = rw.c[(PL_VY >> (4 * s)) & 15];
-            const float v1x = rw.c[(PL_VX >> (4 * s1)) & 15], v1y = rw.c[(PL_VY >> (4 * s1)) & 15];
-            const bool kept = l < 12 && (v0x != v1x || v0y != v1y);
-            const float2 w0 = pl_place(v0x, v0y, cs, sn, xo, yo), w1 = pl_place(v1x, v1y, cs, sn, xo, yo);
+            float2 w0, w1;
+            bool differ;
+            pl_segment(rw, l < 12 ? l : 0, w0, w1, differ);
+            const bool kept = l < 12 && differ;
             // the outline's count of this edge: the quotient in double, cut before it becomes an integer
             const double ex = fabs((double)w1.x - (double)w0.x), ey = fabs((double)w1.y - (double)w0.y);
             const double q = (ex > ey ? ex : ey) / (double)max_dist;
@@ -132,13 +77,7 @@ __global__ __launch_bounds__(256) void hint_plus_kernel(const float* __restrict_
             const int M = __shfl(incl, 11, 64);
             const bool bad = wmask != 0 || rw.finite == 0 || M < 1 || M > PS_MAX_M;
             if (l < 12) {
-                const float nx = __fsub_rn(w1.x, w0.x), ny = __fsub_rn(w1.y, w0.y);
-                const float L = __fsqrt_rn(__fmaf_rn(ny, ny, __fmul_rn(nx, nx)));
-                rw.W[l] = w0;
-                if (l == 11) rw.W[12] = w1;
-                rw.a[l] = w0;
-                rw.n[l] = make_float2(__fdiv_rn(nx, L), __fdiv_rn(ny, L));
-                rw.L[l] = L;
+                pl_store_segment(rw, l, w0, w1);
                 rw.pre[l] = incl - cnt;
                 if (segments) {
                     float* sp = segments + 4 * ((size_t)row * 12 + l);

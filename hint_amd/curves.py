@@ -2,7 +2,8 @@
 evaluation loop on the kernel of hint_curve.hip; trace_fourier_curves / hausdorff_distances / chamfer_distances / lens_fit_loss:
 its shape-quality side on the kernel of hint_hausdorff.hip (below, after the simulator); plus_segments / plus_outline_counts /
 plus_fit_terms / plus_fit_loss / plus_hausdorff_distances: the plus shape's side on the kernel of hint_plus.hip; lens_fit_grad /
-lens_fit_starts / fit_lens_shapes: the lens shape's fit on the kernel of hint_lensfit.hip (at the end).
+lens_fit_starts / fit_lens_shapes: the lens shape's fit on the kernel of hint_lensfit.hip; plus_fit_grad / plus_dominant_angle /
+plus_fit_starts / fit_plus_shapes: the plus shape's fit on the kernel of hint_plusfit.hip (at the end).
 
     LensShapeModel.forward_process(x, noise=0.05)                      data.py:127-139 (over trace_fourier_curves, data.py:51-57)
     mean_target_distance(model, y_target, x)                           rejection_sampling.py:99-102, called at :204
@@ -26,7 +27,8 @@ from ._lib import HintAmdError
 __all__ = ["curve_features", "lens_forward_process", "target_distances", "mean_target_distance",
            "trace_fourier_curves", "hausdorff_distances", "chamfer_distances", "lens_fit_loss",
            "plus_segments", "plus_outline_counts", "plus_fit_terms", "plus_fit_loss", "plus_hausdorff_distances",
-           "lens_fit_grad", "lens_fit_starts", "fit_lens_shapes"]
+           "lens_fit_grad", "lens_fit_starts", "fit_lens_shapes",
+           "plus_fit_grad", "plus_dominant_angle", "plus_fit_starts", "fit_plus_shapes"]
 
 MAX_COEFFS = 25
 MIN_POINTS, MAX_POINTS = 2, 128
@@ -413,7 +415,8 @@ def lens_fit_loss(curve: torch.Tensor, prototype: torch.Tensor, params: torch.Te
 #     max_and_avg_hausdorff_distance_plus_shape(params, points)          best_shape_fit.py:153-156, per row at eval_shapes.py:82-95
 #     PlusShapeModel.densify_polyline(coords, max_dist)                  data.py:176-186
 # One launch of hint_plus_run per call.  The outline's points are generated inside the kernel: no template is built or uploaded
-# and there is no per-row host work.  The fits themselves (fit_plus_shape_to_points) and IoU / DICE stay on the host.
+# and there is no per-row host work.  The fit itself (fit_plus_shape_to_points) is fit_plus_shapes, at the end; IoU / DICE stay on
+# the host.
 PLUS_PARAMS = 9
 MAX_OUTLINE_POINTS = 4096
 
@@ -524,7 +527,7 @@ def plus_hausdorff_distances(curve: torch.Tensor, params: torch.Tensor, *, max_d
 #     fit_lens_shape_to_points(points)                                   best_shape_fit.py:230-261, per row at run_experiments.py:150-159
 #     points_to_lens_loss(prototype, points, params, w).backward()       best_shape_fit.py:203-209 (over :195-199)
 # One launch of hint_lensfit_run per call: no [N, S, P, M] tensor, no autograd graph, no per-row host work; the arithmetic, the
-# selected pairs, the order of the sums and the update rule are fixed (include/hint_amd.h).  The plus shape's fit stays on the host.
+# selected pairs, the order of the sums and the update rule are fixed (include/hint_amd.h).  The plus shape's fit follows below.
 MAX_PROTOTYPE_POINTS = 1024
 MAX_STARTS = 16
 MAX_FIT_STEPS = 1024
@@ -602,6 +605,19 @@ def lens_fit_grad(curve: torch.Tensor, prototype: torch.Tensor, params: torch.Te
     return res["all_loss"].reshape(n), res["grad"].reshape(n, 4)
 
 
+def _tree_sum(v: torch.Tensor) -> torch.Tensor:
+    """the sum of v [n, p, ...] over its second axis as a pairwise tree of elementwise sums (the count padded to a power of two
+    with zeros): a row's bits do not depend on the batch, as a library reduction's might"""
+    n, p = v.shape[0], v.shape[1]
+    width = 1 << (p - 1).bit_length() if p > 1 else 1
+    acc = torch.zeros((n, width) + tuple(v.shape[2:]), dtype=v.dtype, device=v.device)
+    acc[:, :p] = v
+    while width > 1:
+        width //= 2
+        acc = acc[:, :width] + acc[:, width:]
+    return acc[:, 0]
+
+
 def lens_fit_starts(curve: torch.Tensor) -> torch.Tensor:
     """[N, 2, 4] fp32: the two starts (x, y, scale, angle) of the reference's fit_lens_shape_to_points for every row, computed on
     the device - the centre is the mean of the curve's points (a traced curve's repeated end point included), the scale 2, the
@@ -633,15 +649,7 @@ def lens_fit_starts(curve: torch.Tensor) -> torch.Tensor:
         dx, dy = v[:, 0], v[:, 1]
     angle = -torch.atan2(dx, dy)
     second = torch.remainder(angle + torch.pi, 2 * torch.pi)
-    # the mean of the points as a pairwise tree of elementwise sums (the row count padded to a power of two with zeros): a
-    # row's bits do not depend on the batch, as a library reduction's might
-    width = 1 << (p - 1).bit_length()
-    acc = torch.zeros(n, width, 2, dtype=torch.float32, device=curve.device)
-    acc[:, :p] = pts
-    while width > 1:
-        width //= 2
-        acc = acc[:, :width] + acc[:, width:]
-    centre = acc[:, 0] / p
+    centre = _tree_sum(pts) / p
     out = torch.empty(n, 2, 4, dtype=torch.float32, device=curve.device)
     out[:, :, 0:2] = centre[:, None, :]
     out[:, :, 2] = 2.0
@@ -683,4 +691,185 @@ def fit_lens_shapes(curve: torch.Tensor, prototype: torch.Tensor, *, starts: Opt
         return res["params"], res["loss"]
     if return_trace and n_steps == 0:
         res["trace"] = torch.empty(n, starts.shape[1], 0, 9, dtype=torch.float32, device=curve.device)
+    return res["params"], res["loss"], {name: v for name, v in res.items() if name not in ("params", "loss")}
+
+
+# ---- the plus shape's fit: loss, gradient and the SGD loop over up to nine starts in one launch (hint_plusfit.hip) ----
+#     fit_plus_shape_to_points(points)                                   best_shape_fit.py:93-129, per row at eval_shapes.py:85-87
+#     points_to_plus_loss(points, params, corner_weight).backward()      best_shape_fit.py:54-65
+#     init_plus_params(angle, xshift, yshift, center)                    best_shape_fit.py:69-79, over the xyshifts of :100
+#     fit_line(points)                                                   best_shape_fit.py:83-97: RANSAC, random; here every pair
+# One launch of hint_plusfit_run per call: no autograd graph, no per-row host work; the arithmetic, the selected segments and
+# corner points, the order of the sums, the clamp-tie rule and the update rule are fixed (include/hint_amd.h).
+PLUS_STARTS = ((0.0, 0.0), (-1.5, -1.5), (-1.5, 0.0), (-1.5, 1.5), (0.0, -1.5), (0.0, 1.5), (1.5, -1.5), (1.5, 0.0), (1.5, 1.5))
+PLUS_FIT_STEPS = 400
+MAX_ANGLE_POINTS = 128     # plus_dominant_angle looks at every pair of points against every point
+ANGLE_RESIDUAL = 0.05      # fit_line's residual_threshold
+
+
+def _check_plus_starts_shape(shape, n_rows: int, who: str) -> int:
+    shape = tuple(shape)
+    if len(shape) != 3 or shape[0] != n_rows or shape[2] != PLUS_PARAMS or not 1 <= shape[1] <= MAX_STARTS:
+        raise HintAmdError(f"{who}: starts must have shape [{n_rows}, S, 9] with S 1..{MAX_STARTS}: xlength, ylength, xwidth, "
+                           f"ywidth, xshift, yshift, xoffset, yoffset, angle (got {shape})")
+    return shape[1]
+
+
+def _check_number(v, name: str, who: str) -> float:
+    """any number, NaN and the infinities included"""
+    if isinstance(v, bool) or not isinstance(v, (int, float)):
+        raise HintAmdError(f"{who}: {name} must be a number (got {type(v).__name__})")
+    return float(v)
+
+
+def _pf_run(curve: torch.Tensor, k: int, p: int, starts: torch.Tensor, n_steps: int = 0, lr: float = 0.1, angle_lr: float = 0.01,
+            gamma: float = 1.0, momentum: float = 0.0, corner_weight: float = 1.0, corner_decay: bool = False,
+            stop_loss: float = 0.0, want=("params", "loss", "best", "n_run", "all_params", "all_loss", "grad"),
+            max_groups: int = 0, out=None):
+    """one hint_plusfit_run on checked arguments: a dict of the outputs named in `want` (params [N, 9], loss [N], best [N] int32,
+    n_run [N] int32, all_params [N, S, 9], all_loss [N, S], grad [N, S, 9], trace [N, S, n_steps, 19]).  k = 0: curve is
+    [N, P, 2] points.  out: tensors to write into instead of new ones (the tests' guarded buffers)"""
+    lib = _lib.load()
+    n, dev, s = curve.shape[0], curve.device, starts.shape[1]
+    with torch.cuda.device(dev):
+        desc = _lib.PlusFitDesc()
+        _set_curve(desc, curve, n, k, p)
+        desc.starts, desc.n_starts, desc.n_steps = starts.data_ptr(), s, n_steps
+        desc.lr, desc.angle_lr, desc.gamma, desc.momentum = lr, angle_lr, gamma, momentum
+        desc.corner_weight, desc.stop_loss, desc.corner_decay = corner_weight, stop_loss, 1 if corner_decay else 0
+        res = _outputs(desc, dict(params=((n, 9), _F32), loss=((n,), _F32), best=((n,), _I32), n_run=((n,), _I32),
+                                  all_params=((n, s, 9), _F32), all_loss=((n, s), _F32), grad=((n, s, 9), _F32),
+                                  trace=((n, s, n_steps, 19), _F32)), want, out, dev)
+        desc.max_groups = max_groups
+        st = lib.hint_plusfit_run(desc, torch.cuda.current_stream(dev).cuda_stream)
+    _lib.check(st, "hint_plusfit_run")
+    return res
+
+
+def plus_fit_grad(curve: torch.Tensor, params: torch.Tensor, corner_weight: float = 1.0):
+    """the reference's points_to_plus_loss(points, params, corner_weight) and its autograd gradient by the nine parameters, for
+    every row: (loss [N], grad [N, 9]) fp32 - one launch, no autograd graph.  curve is [N, 4K] coefficients, traced at 100 points
+    as the fit's points are, or [N, P, 2] points; params [N, 9], [1, 9] or [9].  Where two segments (or curve points) are equally
+    near, the gradient is the one of the first; where a clamp's two arguments are equal, the one of the unclamped side"""
+    who = "plus_fit_grad"
+    weight = _check_real(corner_weight, "corner_weight", who, nonneg=False)
+    if params is None:
+        raise HintAmdError(f"{who}: params must be a tensor (got None)")
+    curve, n, k, p = _curve_arg(curve, FIT_POINTS, who)
+    starts = _plus_params(params, n, who, curve.device).reshape(n, 1, PLUS_PARAMS)
+    res = _pf_run(curve, k, p, starts, 0, corner_weight=weight, want=("all_loss", "grad"))
+    return res["all_loss"].reshape(n), res["grad"].reshape(n, PLUS_PARAMS)
+
+
+def _fit_points(curve: torch.Tensor, k: int, p: int) -> torch.Tensor:
+    """the curve's points [N, P, 2]: traced from coefficients, or the given ones"""
+    return _hd_run(curve, k, p, None, want_points=True)[3] if k else curve
+
+
+def plus_dominant_angle(curve: torch.Tensor) -> torch.Tensor:
+    """[N] fp32: the dominant angle of every row's points, the deterministic stand-in for the reference's fit_line (RANSAC with
+    residual_threshold 0.05 over 100 random minimal samples): here every minimal sample is looked at.  Candidates are all pairs
+    i < j of points with x_i != x_j; a pair's inliers are the points k with |y_k - line(x_k)| <= 0.05; the winner is the first
+    pair in row-major order with the most inliers; angle = atan(the slope of the least-squares line through the winner's inliers).
+    curve is [N, 4K] coefficients, traced at 100 points, or [N, P, 2] points with P <= 128 (plain torch on the [P, P, P]
+    residuals, at most 2^24 of them at a time).  A row without a candidate, or whose inliers share one x, gets 0; a row that
+    holds a value that is not finite gets an unspecified angle; no index comes from it and no other row is touched"""
+    who = "plus_dominant_angle"
+    curve, n, k, p = _curve_arg(curve, FIT_POINTS, who)
+    if p > MAX_ANGLE_POINTS:
+        raise HintAmdError(f"{who}: the angle looks at every pair of points against every point and serves at most "
+                           f"{MAX_ANGLE_POINTS} points a row (got {p}); pass angle to plus_fit_starts / fit_plus_shapes")
+    pts = _fit_points(curve, k, p)
+    dev = curve.device
+    out = torch.empty(n, dtype=torch.float32, device=dev)
+    flat = torch.arange(p * p, device=dev)
+    upper = (flat // p) < (flat % p)                                          # i < j
+    step = max(1, (1 << 24) // (p * p * p))
+    for a in range(0, n, step):
+        c = pts[a:a + step]
+        m = c.shape[0]
+        x, y = c[:, :, 0], c[:, :, 1]
+        dx, dy = x[:, None, :] - x[:, :, None], y[:, None, :] - y[:, :, None]             # [m, i, j]: point j - point i
+        valid = (upper.reshape(p, p)[None] & (dx != 0)).reshape(m, p * p)
+        slope = (dy / dx).reshape(m, p * p)
+        icpt = y[:, :, None].expand(m, p, p).reshape(m, p * p) - slope * x[:, :, None].expand(m, p, p).reshape(m, p * p)
+        resid = (y[:, None, :] - (slope[:, :, None] * x[:, None, :] + icpt[:, :, None])).abs()          # [m, pair, k]
+        cnt = torch.where(valid, (resid <= ANGLE_RESIDUAL).sum(2), -1)
+        first = torch.where(cnt == cnt.amax(1, keepdim=True), flat, p * p).amin(1).clamp_(max=p * p - 1)
+        rows = torch.arange(m, device=dev)
+        inl = ((resid[rows, first] <= ANGLE_RESIDUAL) & valid[rows, first][:, None]).to(torch.float32)   # [m, k]
+        cn = _tree_sum(inl)
+        xm, ym = _tree_sum(inl * x) / cn, _tree_sum(inl * y) / cn
+        sxx, sxy = _tree_sum(inl * (x - xm[:, None]) ** 2), _tree_sum(inl * (x - xm[:, None]) * (y - ym[:, None]))
+        out[a:a + step] = torch.where(sxx > 0, torch.atan(sxy / sxx), torch.zeros_like(sxx))
+    return out
+
+
+def _check_angle(angle, n_rows: int, device, who: str) -> torch.Tensor:
+    angle = _check_dev_tensor(angle, "angle", who, device)
+    if tuple(angle.shape) != (n_rows,):
+        raise HintAmdError(f"{who}: angle must have shape [{n_rows}] (got {tuple(angle.shape)})")
+    return angle
+
+
+def plus_fit_starts(curve: torch.Tensor, angle: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """[N, 9, 9] fp32: the nine starts of the reference's fit_plus_shape_to_points for every row, computed on the device -
+    init_plus_params for the nine (xshift, yshift) of its list, in its order: lengths 5, widths 2, the offsets at the mean of the
+    curve's points (a traced curve's repeated end point included; the batch-independent sum of lens_fit_starts) and the angle:
+    `angle` [N], or plus_dominant_angle(curve).  curve is [N, 4K] coefficients, traced at 100 points, or [N, P, 2] points"""
+    who = "plus_fit_starts"
+    curve, n, k, p = _curve_arg(curve, FIT_POINTS, who)
+    angle = plus_dominant_angle(curve) if angle is None else _check_angle(angle, n, curve.device, who)
+    centre = _tree_sum(_fit_points(curve, k, p)) / p
+    out = torch.empty(n, len(PLUS_STARTS), PLUS_PARAMS, dtype=torch.float32, device=curve.device)
+    out[:, :, 0:2] = 5.0
+    out[:, :, 2:4] = 2.0
+    out[:, :, 4:6] = torch.tensor(PLUS_STARTS, dtype=torch.float32, device=curve.device)[None]
+    out[:, :, 6:8] = centre[:, None, :]
+    out[:, :, 8] = angle[:, None]
+    return out
+
+
+def fit_plus_shapes(curve: torch.Tensor, *, starts: Optional[torch.Tensor] = None, angle: Optional[torch.Tensor] = None,
+                    n_steps: int = PLUS_FIT_STEPS, lr: float = 0.1, angle_lr: float = 0.01, momentum: float = 0.2,
+                    gamma: float = 0.1 ** (1 / 400), corner_weight: float = 1.0, corner_decay: bool = True,
+                    stop_loss: float = 0.005, return_all: bool = False, return_trace: bool = False):
+    """the reference's fit_plus_shape_to_points for every row in one launch: from each of the row's starts in turn
+    (plus_fit_starts(curve, angle) unless given, [N, S, 9], S <= 16) n_steps steps of SGD with momentum on the fit loss, the step
+    sizes lr (angle_lr for the angle) times gamma after every step, the corner weight corner_weight (1 - i / n_steps) at step i
+    (constant without corner_decay); a start whose last recorded loss is below stop_loss ends the row (stop_loss <= 0 or NaN:
+    every start runs); the start that ran with the smallest loss wins.  Returns (params [N, 9] = xlength, ylength, xwidth, ywidth,
+    xshift, yshift, xoffset, yoffset, angle; loss [N]) and, with return_all or return_trace, a dict as third value: best [N] int32,
+    n_run [N] int32 (the starts that ran), all_params [N, S, 9], all_loss [N, S] (return_all; a start that did not run holds
+    itself and +inf), trace [N, S, n_steps, 19] = the parameters, the loss and the gradient of every step (return_trace; NaN for
+    a start that did not run).  curve as in plus_fit_grad.  The loss is the one of the last step before its update, as the
+    reference records it; n_steps = 0 evaluates the starts at corner_weight"""
+    who = "fit_plus_shapes"
+    n_steps = _check_steps(n_steps, who)
+    lr, angle_lr = _check_real(lr, "lr", who), _check_real(angle_lr, "angle_lr", who)
+    momentum, gamma = _check_real(momentum, "momentum", who), _check_real(gamma, "gamma", who)
+    weight = _check_real(corner_weight, "corner_weight", who, nonneg=False)
+    stop_loss = _check_number(stop_loss, "stop_loss", who)
+    if not isinstance(corner_decay, bool):
+        raise HintAmdError(f"{who}: corner_decay must be a bool (got {type(corner_decay).__name__})")
+    curve, n, k, p = _curve_arg(curve, FIT_POINTS, who)
+    if starts is None:
+        starts = plus_fit_starts(curve, angle)
+    else:
+        if angle is not None:
+            raise HintAmdError(f"{who}: both starts and angle are given (the angle only makes the default starts)")
+        starts = _check_dev_tensor(starts, "starts", who, curve.device)
+        _check_plus_starts_shape(tuple(starts.shape), n, who)
+    want = ["params", "loss"]
+    if return_all or return_trace:
+        want += ["best", "n_run"]
+    if return_all:
+        want += ["all_params", "all_loss"]
+    if return_trace and n_steps > 0:
+        want.append("trace")
+    res = _pf_run(curve, k, p, starts, n_steps, lr, angle_lr, gamma, momentum, weight, corner_decay, stop_loss, want=tuple(want))
+    if not (return_all or return_trace):
+        return res["params"], res["loss"]
+    if return_trace and n_steps == 0:
+        res["trace"] = torch.empty(n, starts.shape[1], 0, 19, dtype=torch.float32, device=curve.device)
     return res["params"], res["loss"], {name: v for name, v in res.items() if name not in ("params", "loss")}

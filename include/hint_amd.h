@@ -717,6 +717,91 @@ size_t hint_lensfit_workspace_bytes(int64_t n_rows, int32_t n_coeffs, int32_t n_
 int hint_lensfit_run(const hint_lensfit_desc* desc, void* stream);
 int64_t hint_lensfit_geometry(int64_t n_rows, int32_t n_points, int32_t field);
 
+/* The plus-shape fit of a curve: the fit loss, its gradient by the nine parameters and the whole SGD loop of the reference's fit in
+ * one launch (eval_shapes.py:85-87 calls, per row, best_shape_fit.py:93-129 fit_plus_shape_to_points: up to nine starts of 400
+ * autograd steps of torch's SGD, best_shape_fit.py:108-118, on best_shape_fit.py:54-65 points_to_plus_loss with the corner weight of
+ * :115, the early stop of :123-124 and the selection of :129).  Per row n and start s the parameters p = (xlength, ylength, xwidth,
+ * ywidth, xshift, yshift, xoffset, yoffset, angle) begin at starts[n, s] and take n_steps steps; the curve B is hint_plus_desc's
+ * (traced from x [n_rows, 4 K] by the same rule and the same bits, or given as b_points [n_rows, P, 2]).  All arithmetic is fp32,
+ * each operation rounded once, unless said otherwise.
+ *   1. geometry at p: hint_plus_desc's items 1 - 3, the same operations and the same bits - the local vertices and their clamps,
+ *      the keep bits, the placed vertices W_0..W_11, and per kept segment s = (W_s, W_(s+1) mod 12) the constants a, n, L of its
+ *      item 4.  nk = the kept segments; a dropped (zero-length) segment takes part in nothing below.
+ *   2. segment term.  Per curve point p_j and kept segment s, in the order s = 0..11: ap, len, v and d2 as hint_plus_desc's item 4.
+ *      The point's segment is the first s with the smallest d2 (a d2 replaces the minimum only when strictly smaller; a NaN never
+ *      does; where nothing does, segment 0 with len = 0, v = 0).  With that segment's len and v: t = len / L (one fp32 division),
+ *      and the four fp32 products v.x (1 - t), v.y (1 - t) (1 - t rounded first) for vertex s and v.x t, v.y t for vertex s + 1
+ *      (mod 12).  |v|^2 has the derivative 2 v (1 - t) by W_s and 2 v t by W_(s+1) in all three cases of the clamp of len.
+ *   3. corner term.  Per kept s: D_j = fma(dy, dy, dx dx), (dx, dy) = W_s - B_j; the corner's point j* is the one with the smallest
+ *      D, the lowest j among equal D (a NaN D loses against every number).  Its derivative by W_s is 2 (W_s - B_j*), the fp32
+ *      difference recomputed.
+ *   4. sums, in double.  SEG = the sum over the P points of their minimum d2, in the association of hint_hausdorff_run's sums:
+ *      thread 64 v + l over its own points 256 c + 64 v + l, c ascending; a butterfly over the lanes, distances 32 .. 1; the four
+ *      wavefronts in order.  G_k [2] = for vertex k and either axis the sum of the products of item 2 that name the vertex, each
+ *      point adding at most one of them: eight partial sums, partial j over the points j, j + 8, j + 16, ... in ascending order,
+ *      then a butterfly over the eight (distances 4, 2, 1).  COR = the sum of the kept corners' minima over s ascending.
+ *   5. loss and gradient, in double, c = the corner weight of the evaluation: L = SEG / P + c (COR / nk), rounded once to fp32.
+ *      gW_k = (2 / P) G_k + [k kept] (2 c / nk) (W_k - B_j*).  With cs, sn the fp32 values of item 1 and V_k the local vertex:
+ *      q_k = V_k R, R = [[cs, sn], [-sn, cs]] (row vectors); then over k ascending d xoffset = sum gW_k.x, d yoffset = sum
+ *      gW_k.y, d angle = sum (gW_k.y q_k.x - gW_k.x q_k.y), and gV_k = gW_k R^T is added to the two of the eight clamped
+ *      coordinates V_k is made of.  xtop, xbottom give +- 1/2 to d xwidth and yright, yleft +- 1/2 to d ywidth.  Each of the four
+ *      clamped coordinates gives its derivative to the branch that was taken: unclamped, 1 to its shift and +- 1/2 to its length;
+ *      clamped, +- 1/2 to the other bar's width.  When the two arguments of a clamp are equal the derivative goes to the
+ *      unclamped side (torch's min / max split it equally there: a difference on a set of measure zero).  Each of the nine is
+ *      rounded once to fp32.  This is the autograd gradient of points_to_plus_loss wherever the minima are unique.
+ *   6. step i = 0 .. n_steps - 1 (torch's SGD with momentum and dampening 0 under StepLR with step_size 1): the corner weight is
+ *      c_i = corner_weight (1 - i / n_steps) in double if corner_decay is not 0, else corner_weight; evaluate (L_i, g_i) at p_i;
+ *      buf = g_0 at i = 0, else fma(momentum rounded to fp32, buf, g_i); p_(i+1) = fma(-lr_i, buf, p_i), where lr_i is the fp32
+ *      rounding of a double that starts at lr (at angle_lr for the angle) and is multiplied by gamma after every step.  The buffer
+ *      and the rates start afresh for every start and every row.
+ *   7. a start's result: all_params[n, s] = p_(n_steps); all_loss[n, s] = L_(n_steps - 1), the loss of the last step before its
+ *      update, as the reference records it; grad[n, s] = g_(n_steps - 1).  n_steps = 0 is one evaluation at corner_weight:
+ *      all_loss = L(p_0), grad = g(p_0), all_params = p_0.  trace[n, s, i] = (p_i [9], L_i, g_i [9]), 19 floats a step.
+ *   8. early stop: the starts run in order; when a start's loss (as a double) is < stop_loss, the row's remaining starts do not
+ *      run.  A stop_loss that is <= 0 or NaN never stops, nor does a NaN loss.  n_run[n] (int32) = the starts that ran.  A start
+ *      that did not run holds: all_params = the start itself, all_loss = +inf, grad and trace = quiet NaN (0x7fc00000) - every
+ *      word of every requested output is written by every launch.
+ *   9. a row's result: among the starts that ran the one with the smallest loss, the first one on a tie, gives params[n], loss[n]
+ *      and best[n] (int32).  A NaN compares as larger; if every loss is NaN, start 0 is taken.
+ *  10. A row's outputs do not depend on n_rows, on where the row stands, on max_groups or on what the outputs held; two runs agree
+ *      bit for bit.  No float atomics, no counters.  A row with non-finite input gives unspecified values, faults nothing and
+ *      disturbs no other row: every loop bound comes from the descriptor, and every index is a loop counter or a lane's number.
+ *   run              stream-ordered on the current device: one launch, no workspace, no host synchronisation, no allocation
+ *                    (capturable).  Each output may be NULL, not all eight.  max_groups: 0 = the default grid, otherwise the
+ *                    workgroups at most.  Rejects, before any device call and naming the field: a null starts; both or neither of
+ *                    x and b_points; no output; n_rows outside 1..2^30; with x, n_coeffs even or outside 1..25 (ignored with
+ *                    b_points); n_points outside 2..1024; n_starts outside 1..16; n_steps outside 0..1024; trace with n_steps = 0;
+ *                    lr, angle_lr, gamma or momentum not finite or negative; corner_weight not finite; max_groups < 0; a pointer
+ *                    that is not 4-byte aligned.
+ *   workspace_bytes  0: no workspace is needed, so the descriptor names none.  For sizes run would reject (n_coeffs = 0 stands
+ *                    for the given source) hint_last_error() says why, otherwise it is left empty.
+ *   geometry         host only, for the default grid: field 0 the workgroups, 1 the rows a workgroup has in flight (one), 2 the
+ *                    curve points a thread holds at most, 3 the grid cap, 4 the most starts.  Workgroup w of G takes rows w,
+ *                    w + G, ... and runs a row's starts one after the other.  -1 on an error.
+ * None of these has a caller's device buffer among its parameters: the buffers are named by the descriptor. */
+typedef struct hint_plusfit_desc {
+    const float* x;                        /* NULL, or [n_rows, 4 n_coeffs] row-major: the traced source */
+    const float* b_points;                 /* NULL, or device float[n_rows, n_points, 2]: the given source */
+    int64_t n_rows;
+    int32_t n_coeffs, n_points;            /* K odd 1..25 (traced source), P 2..1024 */
+    const float* starts;                   /* device float[n_rows, n_starts, 9] */
+    int32_t n_starts, n_steps;             /* S 1..16; 0..1024 */
+    double lr, angle_lr, gamma, momentum, corner_weight, stop_loss;
+    int32_t corner_decay;                  /* not 0: the corner weight falls linearly to 0 over the steps */
+    int32_t max_groups;
+    float* params;                         /* NULL, or device float[n_rows, 9] */
+    float* loss;                           /* NULL, or device float[n_rows] */
+    int32_t* best;                         /* NULL, or device int32[n_rows] */
+    int32_t* n_run;                        /* NULL, or device int32[n_rows] */
+    float* all_params;                     /* NULL, or device float[n_rows, n_starts, 9] */
+    float* all_loss;                       /* NULL, or device float[n_rows, n_starts] */
+    float* grad;                           /* NULL, or device float[n_rows, n_starts, 9] */
+    float* trace;                          /* NULL, or device float[n_rows, n_starts, n_steps, 19] */
+} hint_plusfit_desc;
+size_t hint_plusfit_workspace_bytes(int64_t n_rows, int32_t n_coeffs, int32_t n_points, int32_t n_starts, int32_t n_steps);
+int hint_plusfit_run(const hint_plusfit_desc* desc, void* stream);
+int64_t hint_plusfit_geometry(int64_t n_rows, int32_t n_points, int32_t field);
+
 int hint_abi_version(void);
 const char* hint_last_error(void);
 /* what the library binary was built with and runs with: "libhint_amd abi N, gfx950, HIP x.y.z, clang ..., src <12 hex digits: hash

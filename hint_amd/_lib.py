@@ -109,6 +109,9 @@ _PROTOS = {
     "hint_plan_dispatch": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.c_int32]),
     "hint_plan_check_dispatch": (C.c_int, [C.POINTER(NodeDesc), C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32,
                                            C.c_int32, C.POINTER(C.c_int32), C.c_int32]),
+    "hint_plan_paths": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.c_int32]),
+    "hint_plan_check_paths": (C.c_int, [C.POINTER(NodeDesc), C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32,
+                                        C.c_int32, C.POINTER(C.c_int32), C.c_int32]),
     "hint_plan_check_digest": (C.c_int, [C.POINTER(NodeDesc), C.c_int32, C.c_int32, C.c_int32, C.c_float,
                                          C.POINTER(C.c_uint64), C.c_int32]),
     "hint_block_pack": (C.c_int, [C.c_void_p] * 4),

@@ -244,6 +244,17 @@ int dispatch_out(const hint_plan* P, int B, int32_t* out, int32_t n_out) {
     return 0;
 }
 
+// which of the planner's attempts the variant for B came from and how it stages its tables (the exports' layout: include/hint_amd.h)
+int paths_out(const hint_plan* P, int B, int32_t* out, int32_t n_out) {
+    const hint_plan* V = variant(P, B);
+    auto thin_mode = [](int lds, int grp) { return lds <= 0 ? 0 : grp > 0 ? 2 : 1; };
+    const int32_t v[HINT_PATH_FIELDS] = {V->tile_cap, V->unit_waves, V->n_groups, V->n_levels, thin_mode(V->thin_lds_f, V->thin_grp_f),
+                                         thin_mode(V->thin_lds_b, V->thin_grp_b), V->thin_spill_f, V->thin_spill_b,
+                                         V->lops_off >= 0 ? 1 : 0, V->rowdw_lds > 0 ? 1 : 0, cdiv(V->max_r, 16), cdiv(V->max_cin, 16)};
+    for (int i = 0; i < n_out && i < HINT_PATH_FIELDS; ++i) out[i] = v[i];
+    return 0;
+}
+
 // part A (row-parallel, bit 0 of `parts`) and part B (weight gradients, bit 1) of the backward pass of
 // one block or a chain
 int run_backward(const hint_plan* P, const ChainBlock& one, const ChainBlock* chain, const ChainBlock* chain_host, int n_chain,
@@ -385,6 +396,11 @@ int hint_plan_describe(const hint_plan* P, int32_t B, int32_t* out) {
 int hint_plan_dispatch(const hint_plan* P, int32_t B, int32_t* out, int32_t n_out) {
     if (!P || !out || B < 1 || n_out < 1) return fail("hint_plan_dispatch: bad arguments");
     return dispatch_out(P, B, out, n_out);
+}
+
+int hint_plan_paths(const hint_plan* P, int32_t B, int32_t* out, int32_t n_out) {
+    if (!P || !out || B < 1 || n_out < 1) return fail("hint_plan_paths: bad arguments");
+    return paths_out(P, B, out, n_out);
 }
 
 int hint_block_pack(const hint_plan* P, const float* params, float* packed, void* stream) {

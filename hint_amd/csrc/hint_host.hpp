@@ -186,6 +186,11 @@ struct hint_plan {
     // host-only plans: one digest per emitted table (hint_plan_check_digest).  A NEW FIELD above that a kernel or a launch site
     // reads goes into digest_scalars (hint_plan.cpp), so that tests/test_plan_digest_cpu.py sees it move.
     std::vector<uint64_t> digests;
+    // which of plan_for's attempts was accepted and what it came to (hint_plan_paths; reported only: no kernel or launch site reads
+    // these, and they stay out of the digests)
+    int tile_cap = 0, unit_waves = 0;           // build_plan's two settings
+    int thin_spill_f = 0, thin_spill_b = 0;     // per-group thin staging: some group's slice exceeds the buffer and reads from L2
+    int max_r = 0, max_cin = 0;                 // widest subnet output / input
     ~hint_plan();                               // frees alt4, the level plans and the device tables (hint_plan.cpp)
 };
 
@@ -223,6 +228,7 @@ struct Dispatch {
 };
 Dispatch dispatch(const hint_plan* P, int B, int n_chain = 1);
 int dispatch_out(const hint_plan* P, int B, int32_t* out, int32_t n_out);     // (the exports' layout: include/hint_amd.h)
+int paths_out(const hint_plan* P, int B, int32_t* out, int32_t n_out);        // (hint_plan_paths / hint_plan_check_paths)
 int lds_with_perms(const hint_plan* P, int lds_plan, int n_blocks, bool any_perm, KArgs* a, bool backward = false);     // (backward: which slot of hint_debug_last_lds_bytes the launch's size goes to)
 KArgs make_args(const hint_plan* P, int B, bool backward);
 void split_workspace(const hint_plan* P, int B, void* workspace, ChainBlock* b);

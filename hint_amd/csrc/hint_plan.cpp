@@ -302,6 +302,7 @@ struct PlanBuild {
         P->n_nodes = n_nodes;
         P->n_levels = max_depth + 1;
         P->nw = nw;
+        P->tile_cap = tile_cap; P->unit_waves = unit_waves;
         P->alpha = (float)((double)clamp * 0.636);   // hint.py:57,60 (python float product, then fp32)
         P->xld = d | 1;                              // odd strides: 16 rows hit 16 different LDS banks
         P->cld = dc > 0 ? (dc | 1) : 0;
@@ -609,7 +610,10 @@ static int plan_lane_ops_and_sizes(PlanBuild& b) {
     b.lops = build_lane_ops(b.groups, b.units, b.d);
     P->lop_cnt = (int)b.rng.size();
     for (size_t bd = 0; bd <= b.groups.size(); ++bd) b.rng.push_back(b.lops[bd * (size_t)b.d].pad >> 16);
-    for (const Unit& u : b.units) P->max_h = std::max(P->max_h, (int)u.h);
+    for (const Unit& u : b.units) {
+        P->max_h = std::max(P->max_h, (int)u.h);
+        P->max_r = std::max(P->max_r, (int)u.r); P->max_cin = std::max(P->max_cin, (int)u.cin);
+    }
     P->n_groups = (int)b.groups.size();
     P->n_units = (int)b.units.size();
     P->WT = b.wcol;
@@ -801,7 +805,7 @@ static int plan_lds_sizes(PlanBuild& b, bool* retry_smaller) {
     //  and read one bias vector per tile - keep reading from L2)
     auto avail = [&](int lds) { return lds > LDS_LIMIT / 2 ? LDS_LIMIT - lds : LDS_LIMIT / 2 - lds; };
     const int av_f = avail(P->lds_fwd) / 4, av_b = avail(P->lds_bwd) / 4;
-    int gmax_f = 0, gmax_b = 0;
+    int gmax_f = 0, gmax_b = 0, gall_f = 0, gall_b = 0;      // the largest slice that fits; the largest slice
     for (const Group& g : b.groups) {
         const int t0 = g.tile_begin, t1 = t0 + g.ntiles;
         if (t0 >= t1) continue;
@@ -809,9 +813,10 @@ static int plan_lds_sizes(PlanBuild& b, bool* retry_smaller) {
         const int sf = (f1 - b.thin_f[t0].voff + 3) / 4 * 4, sb = (b1 - b.thin_b[t0].voff + 3) / 4 * 4;
         if (sf <= av_f) gmax_f = std::max(gmax_f, sf);
         if (sb <= av_b) gmax_b = std::max(gmax_b, sb);
+        gall_f = std::max(gall_f, sf); gall_b = std::max(gall_b, sb);
     }
-    if (P->thin_lds_f == 0 && gmax_f > 0) { P->thin_lds_f = P->lds_fwd / 4; P->thin_grp_f = gmax_f; P->lds_fwd += 4 * gmax_f; }
-    if (P->thin_lds_b == 0 && gmax_b > 0) { P->thin_lds_b = P->lds_bwd / 4; P->thin_grp_b = gmax_b; P->lds_bwd += 4 * gmax_b; }
+    if (P->thin_lds_f == 0 && gmax_f > 0) { P->thin_lds_f = P->lds_fwd / 4; P->thin_grp_f = gmax_f; P->lds_fwd += 4 * gmax_f; P->thin_spill_f = gall_f > gmax_f; }
+    if (P->thin_lds_b == 0 && gmax_b > 0) { P->thin_lds_b = P->lds_bwd / 4; P->thin_grp_b = gmax_b; P->lds_bwd += 4 * gmax_b; P->thin_spill_b = gall_b > gmax_b; }
     if (P->lds_bwd > LDS_LIMIT || P->lds_fwd > LDS_LIMIT) {
         *retry_smaller = b.tile_cap > 8 && P->abuf_tiles > 0 && P->n_groups < (int)b.order.size();
         fail("hint_plan_create: block needs %d bytes of LDS (> %d); d/dc/h too large", std::max(P->lds_bwd, P->lds_fwd), LDS_LIMIT);
@@ -1050,6 +1055,7 @@ static std::vector<uint64_t> table_digests(const PlanBuild& b) {
 }
 
 // Every field of hint_plan that is neither a pointer nor a container, except device and num_cu (the machine's, not the planner's)
+// and what only hint_plan_paths reports (tile_cap, unit_waves, thin_spill_*, max_r, max_cin: nothing launched reads them)
 static uint64_t digest_scalars(const hint_plan* P) {
     uint32_t alpha_bits, clamp_bits;
     std::memcpy(&alpha_bits, &P->alpha, 4); std::memcpy(&clamp_bits, &P->clamp, 4);
@@ -1259,6 +1265,17 @@ int hint_plan_check_digest(const hint_node_desc* nodes, int32_t n_nodes, int32_t
         all[v * N_DIGESTS + N_TABLE_DIGESTS] = digest_scalars(both[v]);
     }
     std::copy(all, all + std::min<int>(n_out, 2 * N_DIGESTS), out);
+    return 0;
+}
+
+int hint_plan_check_paths(const hint_node_desc* nodes, int32_t n_nodes, int32_t d, int32_t dc, float clamp, int32_t B,
+                          int32_t num_cu, int32_t* out, int32_t n_out) {
+    if (!out || B < 1 || num_cu < 1 || n_out < 1) return fail("hint_plan_check_paths: bad arguments");
+    std::unique_ptr<hint_plan> P;
+    if (int st = host_plan(nodes, n_nodes, d, dc, clamp, &P)) return st;
+    P->num_cu = num_cu;
+    if (P->alt4) P->alt4->num_cu = num_cu;
+    paths_out(P.get(), B, out, n_out);
     return 0;
 }
 

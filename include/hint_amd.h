@@ -131,6 +131,24 @@ int hint_plan_dispatch(const hint_plan* plan, int32_t B, int32_t* out, int32_t n
 /* The same for a host-only plan (as hint_plan_check builds it: no device needed) on a device of num_cu CUs. */
 int hint_plan_check_dispatch(const hint_node_desc* nodes, int32_t n_nodes, int32_t d, int32_t dc, float clamp, int32_t B,
                              int32_t num_cu, int32_t* out, int32_t n_out);
+/* Which of the planner's attempts a plan came from and how it stages its tables, for the variant a batch of B >= 1 rows runs on (the
+ * planner tries smaller groups, then fewer wavefronts per unit, until the block fits the LDS; thresholds decide what rides in LDS).
+ * Writes the first min(n_out, HINT_PATH_FIELDS) of:
+ *   [0] fragment tiles per group the accepted attempt allowed (64, 48, 32 or 16)
+ *   [1] wavefronts that may share one unit's rows in the accepted attempt (the variant's wavefront count, halved down to 1)
+ *   [2] groups    [3] tree levels
+ *   [4] the thin layers' vectors, forward: 0 read from L2, 1 the whole blob staged in LDS, 2 one group's slice at a time
+ *   [5] the same, backward
+ *   [6] 1 when, in mode 2, some group's slice is larger than the buffer and that group reads from L2 (forward)    [7] backward
+ *   [8] the backward's slot table: 1 in LDS, 0 in global memory
+ *   [9] 1 when rows of the backward kernel compute dW1 | db1 (rowdw)
+ *   [10] tail tiles (16 outputs each) of the widest r    [11] tail tiles (16 inputs each) of the widest cin.
+ * Reported only: no kernel and no launch reads these values, and they are no part of hint_plan_check_digest. */
+#define HINT_PATH_FIELDS 12
+int hint_plan_paths(const hint_plan* plan, int32_t B, int32_t* out, int32_t n_out);
+/* The same for a host-only plan (as hint_plan_check builds it: no device needed) on a device of num_cu CUs. */
+int hint_plan_check_paths(const hint_node_desc* nodes, int32_t n_nodes, int32_t d, int32_t dc, float clamp, int32_t B,
+                          int32_t num_cu, int32_t* out, int32_t n_out);
 /* Host-only as well: one 64-bit digest per table the planner emits, first for the plan, then for its 4-wavefront variant (zeros
  * when there is none).  Per plan HINT_PLAN_DIGESTS values: meta blob, slot table, thin records, row records, bias map, real-element
  * map, weight-gradient jobs, first-layer-gradient map, pack segments, pack tiles, unit_w23, the plan's scalar fields.  Writes the

@@ -50,6 +50,8 @@ EXCLUDED = {
     "hint_plan_dispatch": "writes a host int32 array",
     "hint_plan_check_dispatch": "host-only: writes a host int32 array",
     "hint_plan_check_digest": "host-only: writes a host uint64 array",
+    "hint_plan_paths": "writes a host int32 array",
+    "hint_plan_check_paths": "host-only: writes a host int32 array",
     "hint_pack_group_create": "records the packed pointers (written by hint_pack_group_run*); copies a table it allocates",
     "hint_chain_create": "host out-parameter (the chain handle)",
     "hint_chain_set_block_io": "records pointers only; the chain's part B reads them",

@@ -19,5 +19,7 @@ from .curves import (plus_fit_loss, plus_fit_terms, plus_hausdorff_distances, pl
                      plus_segments)
 from .curves import fit_lens_shapes, lens_fit_grad, lens_fit_starts  # noqa: F401,E402
 from .curves import fit_plus_shapes, plus_dominant_angle, plus_fit_grad, plus_fit_starts  # noqa: F401,E402
+from .curves import (lens_iou_dice, lens_shape_scores, plus_iou_dice, plus_shape_scores,  # noqa: F401,E402
+                     polygon_overlap)
 
 __version__ = "0.1.0"

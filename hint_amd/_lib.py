@@ -86,6 +86,14 @@ class PlusFitDesc(C.Structure):
                 ("trace", C.c_void_p)]
 
 
+class OverlapDesc(C.Structure):
+    """mirror of `hint_overlap_desc` (include/hint_amd.h)"""
+    _fields_ = [("x", C.c_void_p), ("b_points", C.c_void_p), ("n_rows", C.c_int64), ("n_coeffs", C.c_int32),
+                ("n_points", C.c_int32), ("a_points", C.c_void_p), ("a_offsets", C.c_void_p), ("a_params", C.c_void_p),
+                ("n_template", C.c_int64), ("plus_params", C.c_void_p), ("areas", C.c_void_p), ("iou", C.c_void_p),
+                ("dice", C.c_void_p), ("crossings", C.c_void_p), ("max_groups", C.c_int32)]
+
+
 _lib = None
 
 _PROTOS = {
@@ -177,6 +185,9 @@ _PROTOS = {
     "hint_plusfit_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "hint_plusfit_run": (C.c_int, [C.POINTER(PlusFitDesc), C.c_void_p]),
     "hint_plusfit_geometry": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
+    "hint_overlap_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32, C.c_int64]),
+    "hint_overlap_run": (C.c_int, [C.POINTER(OverlapDesc), C.c_void_p]),
+    "hint_overlap_geometry": (C.c_int64, [C.c_int64, C.c_int32, C.c_int64, C.c_int32]),
 }
 
 

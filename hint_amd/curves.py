@@ -3,7 +3,9 @@ evaluation loop on the kernel of hint_curve.hip; trace_fourier_curves / hausdorf
 its shape-quality side on the kernel of hint_hausdorff.hip (below, after the simulator); plus_segments / plus_outline_counts /
 plus_fit_terms / plus_fit_loss / plus_hausdorff_distances: the plus shape's side on the kernel of hint_plus.hip; lens_fit_grad /
 lens_fit_starts / fit_lens_shapes: the lens shape's fit on the kernel of hint_lensfit.hip; plus_fit_grad / plus_dominant_angle /
-plus_fit_starts / fit_plus_shapes: the plus shape's fit on the kernel of hint_plusfit.hip (at the end).
+plus_fit_starts / fit_plus_shapes: the plus shape's fit on the kernel of hint_plusfit.hip; polygon_overlap / lens_iou_dice /
+plus_iou_dice: IoU and DICE on the kernel of hint_overlap.hip, and lens_shape_scores / plus_shape_scores: the evaluation loop's
+four columns composed of the above (at the end).
 
     LensShapeModel.forward_process(x, noise=0.05)                      data.py:127-139 (over trace_fourier_curves, data.py:51-57)
     mean_target_distance(model, y_target, x)                           rejection_sampling.py:99-102, called at :204
@@ -17,6 +19,7 @@ generator; here eps is an argument, or torch.randn on the device.  No gradient i
 """
 from __future__ import annotations
 
+from collections import namedtuple
 from typing import Optional
 
 import torch
@@ -28,7 +31,8 @@ __all__ = ["curve_features", "lens_forward_process", "target_distances", "mean_t
            "trace_fourier_curves", "hausdorff_distances", "chamfer_distances", "lens_fit_loss",
            "plus_segments", "plus_outline_counts", "plus_fit_terms", "plus_fit_loss", "plus_hausdorff_distances",
            "lens_fit_grad", "lens_fit_starts", "fit_lens_shapes",
-           "plus_fit_grad", "plus_dominant_angle", "plus_fit_starts", "fit_plus_shapes"]
+           "plus_fit_grad", "plus_dominant_angle", "plus_fit_starts", "fit_plus_shapes",
+           "polygon_overlap", "lens_iou_dice", "plus_iou_dice", "lens_shape_scores", "plus_shape_scores"]
 
 MAX_COEFFS = 25
 MIN_POINTS, MAX_POINTS = 2, 128
@@ -221,7 +225,7 @@ def mean_target_distance(x: torch.Tensor, y_target, noise: float = 0.05, *, eps:
 #     lens_points_from_params(prototype, params)                         best_shape_fit.py:195-199
 #     points_to_lens_loss(prototype, points, params, lens_fit_weight)    best_shape_fit.py:203-209
 # One launch of hint_hausdorff_run per call: no [N, P, M] tensor, no host synchronisation, the arithmetic and the order of the sums
-# fixed (include/hint_amd.h).  The shape fits, IoU / DICE and the template generators stay on the host.
+# fixed (include/hint_amd.h).  The shape fits and IoU / DICE follow below; the template generators stay on the host.
 MAX_DENSE_POINTS = 1024
 MAX_TEMPLATE_POINTS = 4096
 
@@ -415,8 +419,8 @@ def lens_fit_loss(curve: torch.Tensor, prototype: torch.Tensor, params: torch.Te
 #     max_and_avg_hausdorff_distance_plus_shape(params, points)          best_shape_fit.py:153-156, per row at eval_shapes.py:82-95
 #     PlusShapeModel.densify_polyline(coords, max_dist)                  data.py:176-186
 # One launch of hint_plus_run per call.  The outline's points are generated inside the kernel: no template is built or uploaded
-# and there is no per-row host work.  The fit itself (fit_plus_shape_to_points) is fit_plus_shapes, at the end; IoU / DICE stay on
-# the host.
+# and there is no per-row host work.  The fit itself (fit_plus_shape_to_points) is fit_plus_shapes and IoU / DICE plus_iou_dice,
+# at the end.
 PLUS_PARAMS = 9
 MAX_OUTLINE_POINTS = 4096
 
@@ -873,3 +877,135 @@ def fit_plus_shapes(curve: torch.Tensor, *, starts: Optional[torch.Tensor] = Non
     if return_trace and n_steps == 0:
         res["trace"] = torch.empty(n, starts.shape[1], 0, 19, dtype=torch.float32, device=curve.device)
     return res["params"], res["loss"], {name: v for name, v in res.items() if name not in ("params", "loss")}
+
+
+# ---- IoU / DICE of a curve and a fitted shape, and the evaluation loop's four columns (hint_overlap.hip) ----
+#     iou_and_dice_lens_shape(prototype, params, points)                 best_shape_fit.py:265-271, per row at run_experiments.py:150-159
+#     iou_and_dice_plus_shape(params, points)                            best_shape_fit.py:133-139, per row at eval_shapes.py:88-95
+# One launch of hint_overlap_run per call: the area of the intersection as a sum over pairs of edges - no clipping, no host loop,
+# no host synchronisation; the arithmetic and the order of the sums are fixed (include/hint_amd.h).  A curve that crosses itself
+# (crossings > 0) gets the winding-weighted value, where the reference rebuilds the polygon with shapely's buffer(0): send those
+# rows, and only those, to shapely if its rule matters.  get_lens_prototype stays on the host; the prototype is the caller's.
+MIN_POLYGON_POINTS = 3
+Overlap = namedtuple("Overlap", ["iou", "dice", "areas", "crossings"])
+ShapeScores = namedtuple("ShapeScores", ["iou", "dice", "max_h", "avg_h", "crossings", "params"])
+
+
+def _polygon_curve(curve, n_points, who: str):
+    curve, n, k, p = _curve_arg(curve, n_points, who)
+    if p < MIN_POLYGON_POINTS:
+        raise HintAmdError(f"{who}: a closed curve needs {MIN_POLYGON_POINTS}..{MAX_DENSE_POINTS} points (got {p})")
+    return curve, n, k, p
+
+
+def _ov_run(curve: torch.Tensor, k: int, p: int, polygon: Optional[torch.Tensor] = None, offsets: Optional[torch.Tensor] = None,
+            params: Optional[torch.Tensor] = None, plus_params: Optional[torch.Tensor] = None,
+            want=("areas", "iou", "dice", "crossings"), max_groups: int = 0, out=None):
+    """one hint_overlap_run on checked arguments: a dict of the outputs named in `want` (areas [N, 3] = area of the template, of
+    the curve, of the intersection; iou [N]; dice [N]; crossings [N] int32).  k = 0: curve is [N, P, 2] points.  The template is
+    polygon (with offsets, params as in _hd_run) or the outline of plus_params [N, 9]; neither: crossings alone.
+    out: tensors to write into instead of new ones (the tests' guarded buffers)"""
+    lib = _lib.load()
+    n, dev = curve.shape[0], curve.device
+    with torch.cuda.device(dev):
+        desc = _lib.OverlapDesc()
+        _set_curve(desc, curve, n, k, p)
+        desc.a_points = polygon.data_ptr() if polygon is not None else None
+        desc.n_template = polygon.shape[0] if polygon is not None else 0
+        desc.a_offsets = offsets.data_ptr() if offsets is not None else None
+        desc.a_params = params.data_ptr() if params is not None else None
+        desc.plus_params = plus_params.data_ptr() if plus_params is not None else None
+        res = _outputs(desc, dict(areas=((n, 3), _F32), iou=((n,), _F32), dice=((n,), _F32), crossings=((n,), _I32)), want, out, dev)
+        desc.max_groups = max_groups
+        st = lib.hint_overlap_run(desc, torch.cuda.current_stream(dev).cuda_stream)
+    _lib.check(st, "hint_overlap_run")
+    return res
+
+
+def _overlap_args(curve, polygon, params, offsets, n_points, who: str):
+    curve, n, k, p = _polygon_curve(curve, n_points, who)
+    polygon = _check_dev_tensor(polygon, "polygon", who, curve.device)
+    t_pts = _check_template_shape(tuple(polygon.shape), offsets is not None, who)
+    if t_pts < MIN_POLYGON_POINTS:
+        raise HintAmdError(f"{who}: polygon must hold at least {MIN_POLYGON_POINTS} points (got shape {tuple(polygon.shape)})")
+    if offsets is not None:
+        offsets = _check_offsets(offsets, n, t_pts, who).to(curve.device)
+    if params is not None:
+        params = _check_dev_tensor(params, "params", who, curve.device)
+        _check_params_shape(tuple(params.shape), n, who)
+        params = params.reshape(-1, 4).expand(n, 4).contiguous()
+    return curve, k, p, polygon, offsets, params
+
+
+def polygon_overlap(curve: torch.Tensor, polygon: torch.Tensor, params: Optional[torch.Tensor] = None, *, offsets=None,
+                    n_points: int = 100) -> Overlap:
+    """the overlap of every row's closed curve with a closed polygon: Overlap(iou [N], dice [N], areas [N, 3] = the area of the
+    polygon, of the curve and of their intersection, crossings [N] int32 = the proper self-crossings of the curve), fp32.
+
+    curve     [N, 4K] coefficients, traced at n_points here, or [N, P, 2] points, 3 <= P <= 1024 (n_points is then ignored);
+              the last point is joined to the first
+    polygon   [M, 2] vertices in order, 3 <= M <= 4096, either orientation, shared by all rows; or, with offsets (int64 [N + 1],
+              ascending from 0 to T, on the host or the device), [T, 2] of which row n owns polygon[offsets[n]:offsets[n + 1]]
+    params    None, or [N, 4] (or [4]) = x, y, scale, angle: the polygon is first moved as lens_points_from_params does
+
+    For simple polygons the intersection is the one shapely computes; a curve with crossings > 0 counts every region by the
+    product of the two winding numbers.  A row with a value that is not finite, or with a bad offsets range, gets NaN and -1"""
+    who = "polygon_overlap"
+    curve, k, p, polygon, offsets, params = _overlap_args(curve, polygon, params, offsets, n_points, who)
+    res = _ov_run(curve, k, p, polygon, offsets, params)
+    return Overlap(res["iou"], res["dice"], res["areas"], res["crossings"])
+
+
+def lens_iou_dice(curve: torch.Tensor, prototype: torch.Tensor, params: torch.Tensor):
+    """the reference's iou_and_dice_lens_shape(prototype, params, points) for every row: (iou [N], dice [N], crossings [N] int32).
+    curve is [N, 4K] coefficients, traced at 100 points as the reference's are, or [N, P, 2] points; prototype [M, 2], the
+    outline's vertices in order, 3 <= M <= 4096; params [N, 4], [1, 4] or [4] = x, y, scale, angle.  Where crossings is 0 the
+    curve is simple and the values are the reference's; elsewhere see polygon_overlap"""
+    who = "lens_iou_dice"
+    if params is None:
+        raise HintAmdError(f"{who}: params must be a tensor (got None)")
+    curve, k, p, prototype, _, params = _overlap_args(curve, prototype, params, None, FIT_POINTS, who)
+    res = _ov_run(curve, k, p, prototype, None, params, want=("iou", "dice", "crossings"))
+    return res["iou"], res["dice"], res["crossings"]
+
+
+def plus_iou_dice(curve: torch.Tensor, params: torch.Tensor):
+    """the reference's iou_and_dice_plus_shape(params, points) for every row: (iou [N], dice [N], crossings [N] int32).  The
+    polygon is the plus shape's outline, placed inside the kernel: the twelve vertices plus_segments(params)[0][:, :, 0] (a
+    dropped segment repeats a vertex, which changes no area).  curve as in lens_iou_dice; params [N, 9], [1, 9] or [9]"""
+    who = "plus_iou_dice"
+    curve, n, k, p = _polygon_curve(curve, FIT_POINTS, who)
+    params = _plus_params(params, n, who, curve.device)
+    res = _ov_run(curve, k, p, plus_params=params, want=("iou", "dice", "crossings"))
+    return res["iou"], res["dice"], res["crossings"]
+
+
+def _scores_x(x, who: str) -> torch.Tensor:
+    if isinstance(x, torch.Tensor):
+        _check_no_grad(x, "x", who)
+    return _check_x(x, who)
+
+
+def lens_shape_scores(x: torch.Tensor, prototype: torch.Tensor) -> ShapeScores:
+    """the body of the reference's lens-shape evaluation loop (run_experiments.py:144-167) for all rows of x [N, 4K]:
+    fit_lens_shapes on the curve at 100 points, lens_iou_dice on the same points, hausdorff_distances of the curve at 1000 points
+    to the fitted prototype.  ShapeScores(iou, dice, max_h, avg_h, crossings, params [N, 4]), all [N] on x's device; no host
+    synchronisation - the means are the caller's to take"""
+    who = "lens_shape_scores"
+    x = _scores_x(x, who)
+    params, _ = fit_lens_shapes(x, prototype)
+    iou, dice, crossings = lens_iou_dice(x, prototype, params)
+    max_h, avg_h = hausdorff_distances(x, prototype, params, n_points=1000)
+    return ShapeScores(iou, dice, max_h, avg_h, crossings, params)
+
+
+def plus_shape_scores(x: torch.Tensor) -> ShapeScores:
+    """the body of the reference's plus-shape evaluation loop (eval_shapes.py:82-103) for all rows of x [N, 4K]: fit_plus_shapes
+    on the curve at 100 points, plus_iou_dice on the same points, plus_hausdorff_distances of the curve at 1000 points to the
+    fitted outline.  ShapeScores(iou, dice, max_h, avg_h, crossings, params [N, 9]); no host synchronisation"""
+    who = "plus_shape_scores"
+    x = _scores_x(x, who)
+    params, _ = fit_plus_shapes(x)
+    iou, dice, crossings = plus_iou_dice(x, params)
+    max_h, avg_h = plus_hausdorff_distances(x, params, n_points=1000)
+    return ShapeScores(iou, dice, max_h, avg_h, crossings, params)

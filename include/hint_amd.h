@@ -820,6 +820,89 @@ size_t hint_plusfit_workspace_bytes(int64_t n_rows, int32_t n_coeffs, int32_t n_
 int hint_plusfit_run(const hint_plusfit_desc* desc, void* stream);
 int64_t hint_plusfit_geometry(int64_t n_rows, int32_t n_points, int32_t field);
 
+/* IoU and DICE of a curve and a fitted shape: the first two columns of the reference's shape evaluation (run_experiments.py:144-167
+ * and eval_shapes.py:82-103 call, per row, best_shape_fit.py:265-271 iou_and_dice_lens_shape or best_shape_fit.py:133-139
+ * iou_and_dice_plus_shape: two shapely polygons, their intersection's and their union's area).  Per row n two closed polygons are
+ * compared, with no clipping, no point-in-polygon test, no sorting and no topology.
+ *   C, the curve, P = n_points vertices, 3 <= P <= 1024, from exactly one source, as hint_hausdorff_desc's B: traced from
+ *     x [n_rows, 4 K] by the same rule and the same bits, or given as b_points [n_rows, P, 2].  Edge i runs from vertex i to vertex
+ *     (i + 1) mod P; a traced curve's vertex P - 1 repeats vertex 0, so its edge P - 1 has no length.
+ *   T, the template, M_n vertices, from exactly one source:
+ *     a_points [n_template, 2], with a_offsets and a_params of hint_hausdorff_desc's meaning and placement (shared or ragged; cs, sn
+ *       = sincos in double of the fp32 angle, rounded; q = (fma(-a.y, sn, a.x cs), fma(a.y, cs, a.x sn)); vertex = (fma(q.x, scale,
+ *       x), fma(q.y, scale, y))), 3 <= M_n <= 4096;
+ *     plus_params [n_rows, 9]: the twelve placed vertices W_0..W_11 of hint_plus_desc's items 1 and 3, the bits hint_plus_run
+ *       writes to segments[n, s, 0]; M_n = 12.  All twelve are used: a dropped segment is an edge of no length.
+ *   All arithmetic below is fp32, each operation rounded once, unless said otherwise.
+ *   1. baseline.  y0 = the smallest y of all P + M_n vertices of the row (exact).  A vertex (x, y) is used as (x, h), h = y - y0
+ *      >= 0.  An edge is (x0, h0, x1, h1) with dx = x1 - x0 and r = 1 / dx (a correctly rounded division).
+ *   2. areas.  An edge's area term is (0.5 dx) (h0 + h1).  area_C = |the sum of the curve's P terms|, area_T = |the sum of the
+ *      template's M_n terms|, the sums in double.
+ *   3. the height of an edge at an abscissa q inside its x-range: u1 = min((q - x0) r, 1), u0 = min((x1 - q) r, 1),
+ *      h = fma(u1, h1, u0 h0), then cut to the edge's own heights: max(min(h0, h1), min(max(h0, h1), h)).  Both weights are
+ *      non-negative, so no slope, however steep, takes a height out of the edge's own range.
+ *   4. the term of a curve edge e and a template edge f.  a = max(min(e.x0, e.x1), min(f.x0, f.x1)), b = min(max(e.x0, e.x1),
+ *      max(f.x0, f.x1)); unless a < b the term is exactly 0 (so an edge with x1 = x0 contributes nothing).  w = b - a; ea, eb, fa,
+ *      fb = the heights of e and f at a and at b; da = ea - fa, db = eb - fb; ma = min(ea, fa), mb = min(eb, fb).  When da and db
+ *      have strictly opposite signs the heights cross inside: den = da - db, ta = da / den, tb = (-db) / den (two divisions),
+ *      hc = fma(ta, eb, tb ea), sum = hc + fma(ta, ma, tb mb); otherwise sum = ma + mb.  term = (0.5 w) sum, negated when exactly
+ *      one of e.x1 < e.x0 and f.x1 < f.x0 holds.  This is sign_e sign_f times the integral over [a, b] of the smaller height.
+ *   5. I = |the sum of the P M_n terms| in double, then cut to [0, min(area_C, area_T)].  For simple polygons of either orientation
+ *      this is the area of their intersection: the integral of the product of the two winding numbers.
+ *   6. outputs, from the doubles: areas[n] = (area_T, area_C, I), iou[n] = I / (area_C + area_T - I), dice[n] = 2 I / (area_C +
+ *      area_T), each rounded once to fp32; NaN where the denominator is 0.
+ *   7. crossings[n] (int32) = the unordered pairs of curve edges (i, j), i + 1 < j, (i, j) not (0, P - 1) - pairs that share a
+ *      vertex index are never tested - that cross properly: with det(p, q, s) = fma(q.x - p.x, s.y - p.y, -((q.y - p.y) (s.x -
+ *      p.x))), edge i = (a0, a1) and edge j = (b0, b1), det(a0, a1, b0) and det(a0, a1, b1) have strictly opposite signs and so
+ *      have det(b0, b1, a0) and det(b0, b1, a1).  An edge of no length never crosses.  crossings = 0 says that the curve is
+ *      simple, and the row's I is then the reference's intersection.area; otherwise I is the winding-weighted value of item 5 (the
+ *      reference rebuilds such a polygon by a rule of shapely's that is not restated here).  crossings reads no template.
+ *   8. the association of the double sums is hint_hausdorff_run's.  Thread 64 v + l owns the curve edges i = 256 c + 64 v + l (c
+ *      ascending) and, of every tile of 1024 template edges g = 1024 k + i, the edges i of the same form.  It adds to 0: for
+ *      area_C its own curve edges' terms, c ascending; for area_T its own template edges' terms, tile after tile, c ascending;
+ *      for I the pair terms in the order template edge g ascending and within it its own curve edges c ascending; for the
+ *      crossings (an integer) the order does not matter.  The 64 lanes of a wavefront are added by a butterfly (lane distances
+ *      32, 16, 8, 4, 2, 1); the four wavefronts are added in order.  The closing edge M_n - 1 -> 0 and every edge across a tile
+ *      seam belong to the tile of their first vertex.  No float atomics, no counters.
+ *   9. A row's outputs do not depend on n_rows, on where the row stands, on max_groups or on what the outputs held; two runs agree
+ *      bit for bit.  A row with a value that is not finite among its curve points, its placed template vertices or its parameters,
+ *      or whose ragged range is not 3..4096 points inside a_points, gets NaN in areas, iou and dice and -1 in crossings; it reads
+ *      nothing outside its buffers, faults nothing and disturbs no other row.
+ *   run              stream-ordered on the current device: one launch, no workspace, no host synchronisation, no allocation
+ *                    (capturable).  Each output may be NULL, not all four.  When only crossings is asked the template is not
+ *                    read: a_points and plus_params may then both be NULL.  max_groups: 0 = the default grid, otherwise the
+ *                    workgroups at most.  Rejects, before any device call and naming the field: no output; both of a_points and
+ *                    plus_params; neither when areas, iou or dice is asked; a_offsets or a_params without a_points; both or neither
+ *                    of x and b_points; n_rows outside 1..2^30; with x, n_coeffs even or outside 1..25 (ignored with b_points);
+ *                    n_points outside 3..1024; n_template < 3; a shared template of more than 4096 points, ragged ones of more
+ *                    than 4096 n_rows in all; max_groups < 0; a pointer that is not 4-byte (a_offsets: 8-byte) aligned.
+ *   workspace_bytes  0: no workspace is needed, so the descriptor names none.  For sizes run would reject (n_coeffs = 0 stands
+ *                    for the given source; max_template_points is the largest M_n, 12 for plus_params) hint_last_error() says
+ *                    why, otherwise it is left empty.
+ *   geometry         host only, for the default grid: field 0 the workgroups, 1 the rows a workgroup has in flight (one), 2 the
+ *                    template edges of an LDS tile, 3 the grid cap, 4 the tiles of max_template_points.  Workgroup w of G takes
+ *                    rows w, w + G, ...  -1 on an error.
+ * None of these has a caller's device buffer among its parameters: the buffers are named by the descriptor. */
+typedef struct hint_overlap_desc {
+    const float* x;                        /* NULL, or [n_rows, 4 n_coeffs] row-major: the traced source */
+    const float* b_points;                 /* NULL, or device float[n_rows, n_points, 2]: the given source */
+    int64_t n_rows;
+    int32_t n_coeffs, n_points;            /* K odd 1..25 (traced source), P 3..1024 */
+    const float* a_points;                 /* NULL, or device float[n_template, 2] */
+    const int64_t* a_offsets;              /* NULL (shared template), or device int64[n_rows + 1], 8-byte aligned */
+    const float* a_params;                 /* NULL, or device float[n_rows, 4]: x, y, scale, angle */
+    int64_t n_template;                    /* T: points in a_points */
+    const float* plus_params;              /* NULL, or device float[n_rows, 9]: the template is the plus shape's outline */
+    float* areas;                          /* NULL, or device float[n_rows, 3]: area_T, area_C, I */
+    float* iou;                            /* NULL, or device float[n_rows] */
+    float* dice;                           /* NULL, or device float[n_rows] */
+    int32_t* crossings;                    /* NULL, or device int32[n_rows] */
+    int32_t max_groups;
+} hint_overlap_desc;
+size_t hint_overlap_workspace_bytes(int64_t n_rows, int32_t n_coeffs, int32_t n_points, int64_t max_template_points);
+int hint_overlap_run(const hint_overlap_desc* desc, void* stream);
+int64_t hint_overlap_geometry(int64_t n_rows, int32_t n_points, int64_t max_template_points, int32_t field);
+
 int hint_abi_version(void);
 const char* hint_last_error(void);
 /* what the library binary was built with and runs with: "libhint_amd abi N, gfx950, HIP x.y.z, clang ..., src <12 hex digits: hash

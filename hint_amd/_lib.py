@@ -122,6 +122,8 @@ _PROTOS = {
                                         C.c_int32, C.POINTER(C.c_int32), C.c_int32]),
     "hint_plan_check_digest": (C.c_int, [C.POINTER(NodeDesc), C.c_int32, C.c_int32, C.c_int32, C.c_float,
                                          C.POINTER(C.c_uint64), C.c_int32]),
+    "hint_plan_check_wjob": (C.c_int64, [C.POINTER(NodeDesc), C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_int64,
+                                         C.c_int32]),
     "hint_block_pack": (C.c_int, [C.c_void_p] * 4),
     "hint_pack_group_create": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
                                          C.c_int32, C.POINTER(C.c_void_p)]),

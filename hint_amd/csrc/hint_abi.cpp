@@ -35,6 +35,7 @@ static Knobs read_knobs() {
     if (get("HINT_NO_BWD_FLY", &v)) k.no_bwd_fly = v != 0;
     if (get("HINT_DW_SPLITS", &v)) k.dw_splits = v;
     if (get("HINT_DW_SMALL", &v)) k.dw_small = v != 0 ? 1 : 0;
+    if (get("HINT_DW3_ROWS", &v)) k.dw3_rows = v != 0 ? 1 : 0;
     if (get("HINT_ABLATION_OK", &v)) k.ablation_ok = v != 0;
     return k;
 }
@@ -288,7 +289,7 @@ int run_backward(const hint_plan* P, const ChainBlock& one, const ChainBlock* ch
     }
     if (!(parts & 2)) return 0;
     const int splits = D.dw_splits, rows_per_wg = D.dw_rows;   // (the whole chain's count: a bucketed launch sums in the same order)
-    HIP_TRY(launch_wgrad(P->d_wjobs, P->n_wjobs, P->wsorted ? -P->n_wsmall - 1 : P->n_wsmall, splits, one, chain, n_chain, cb0, P->WT, P->ST, P->d, P->dc, P->n_levels, B,
+    HIP_TRY(launch_wgrad(P->d_wjobs, P->n_ljobs, P->wsorted ? -P->n_lsmall - 1 : P->n_lsmall, P->n_rowj, splits, one, chain, n_chain, cb0, P->WT, P->ST, P->d, P->dc, P->n_levels, B,
                          rows_padded(B), rows_per_wg, act_stride(P, B), P->lean ? 0 : act_stride(P, B),
                          (P->lean ? 1 : 2) * act_stride(P, B) * 4 + bits_stride(P, B), P->param_floats, x, c, P->d_real,
                          accumulate, P->fuse_dw1 ? P->d_twmap : nullptr, P->tw_floats, ws_thin_off(P, B), D.grid,

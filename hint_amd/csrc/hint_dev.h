@@ -151,7 +151,11 @@ static_assert(sizeof(LaneOp) == 16, "LaneOp must be 16 bytes");
 // Lean plans (every unit has 1..4 inputs, no condition, and at most 4 outputs) keep neither a1 nor g2 in HBM: the
 // dW2 jobs rebuild their operands from what feeds the thin layers (WSRC_A1R: relu(W1 v + b1) from the level's lanes;
 // WSRC_G2R: relu'(a2) (W3^T g_st) from a2 and the coupling gradients) - a few FMAs per element instead of 4 bytes.
-enum { WSRC_G1 = 0, WSRC_G2 = 1, WSRC_GST = 2, WSRC_A1 = 3, WSRC_A2 = 4, WSRC_X = 5, WSRC_C = 6, WSRC_A1R = 7, WSRC_G2R = 8 };
+// Row jobs (psrc = WSRC_GSTR; the launch list only, never the planner's wjobs table): dW3 | db3 of a unit with r <= 4 as
+// 4x4x1 MFMAs, one wavefront per (job, split) walking the split's rows in order - M = r, pcol = gcol, qcol / N: up to
+// DW3R_COLS columns of the unit's a2, nw = ceil(N / 64) accumulator quads.
+enum { WSRC_G1 = 0, WSRC_G2 = 1, WSRC_GST = 2, WSRC_A1 = 3, WSRC_A2 = 4, WSRC_X = 5, WSRC_C = 6, WSRC_A1R = 7, WSRC_G2R = 8, WSRC_GSTR = 9 };
+constexpr int DW3R_COLS = 256;
 struct WJob {
     int32_t psrc, pcol, M, mw;      // operand array, first column, valid outputs (<= 16*mw), 16-wide tiles (1..3)
     int32_t qsrc, qcol, N, nw;      // N may be 0 (bias only)

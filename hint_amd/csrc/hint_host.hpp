@@ -38,7 +38,7 @@ hipError_t launch_apply(bool rev, bool fly, const KArgs& a, int lds_bytes, int g
 hipError_t launch_bwd(const KArgs& a, int lds_bytes, int grid, const ChainBlock& one, const ChainBlock* chain,
                       int n_chain, const float* x, const float* c, const float* g_z, const float* g_J,
                       float* g_x, float* g_c, float gz_scale, float gJ_const, hipStream_t stream);
-hipError_t launch_wgrad(const WJob* jobs, int n_jobs, int n_small, int splits, const ChainBlock& one, const ChainBlock* chain,
+hipError_t launch_wgrad(const WJob* jobs, int n_jobs, int n_small, int n_rowj, int splits, const ChainBlock& one, const ChainBlock* chain,
                         int n_chain, int cb0, int WT, int ST, int d, int dc, int n_levels, int B, int Bp, int rows_per_wg,
                         int64_t act_stride, int64_t a2_off, int64_t bits_a2_off, int64_t param_floats, const float* x,
                         const float* c, const uint8_t* real, int accumulate, const int32_t* twmap, int tw_floats,
@@ -118,6 +118,8 @@ struct Knobs {
     bool no_bwd_fly = false;    // HINT_NO_BWD_FLY=1  plans with lean general groups on the shared backward kernel
     int dw_splits = 0;          // HINT_DW_SPLITS=n   batch splits of part B
     int dw_small = -1;          // HINT_DW_SMALL=0|1  single-tile part-B jobs one per wavefront of a shared workgroup: never / always (-1: trees with subtree groups)
+    int dw3_rows = -1;          // HINT_DW3_ROWS=0|1  dW3 | db3 of units with r <= 4 as row jobs (4x4x1 MFMAs, one wavefront per job and split): never / on every
+                                //                    plan (-1: plans without subtree groups; MINIBOONE's own A/B was inside its spread - NOTES.md section 16)
     int leanw_max = 12;         // HINT_LEANW_MAX=n   widest thin layer (inputs / outputs) of a lean-wide group: 5 .. 28 (default 12: three k-blocks;
                                 //                    wider ones cost part B more MFMAs than their a1 / g2 traffic is worth - NOTES.md section 10)
     bool ablation_ok = false;   // HINT_ABLATION_OK=1 lets an ablation build (-DHINT_ABLATE_STORE) run a backward pass (its gradients are wrong: timing only)
@@ -186,6 +188,11 @@ struct hint_plan {
     // host-only plans: one digest per emitted table (hint_plan_check_digest).  A NEW FIELD above that a kernel or a launch site
     // reads goes into digest_scalars (hint_plan.cpp), so that tests/test_plan_digest_cpu.py sees it move.
     std::vector<uint64_t> digests;
+    // part B's LAUNCH list (hint_plan.cpp plan_launch_jobs; what d_wjobs holds): the wjobs table - minus, with HINT_DW3_ROWS on, the
+    // dW3 jobs of the units with r <= 4 - followed by the row jobs that cover those units.  Derived from the digested tables and the
+    // knob alone; n_wjobs / n_wsmall above stay the planner's (wgrad_splits and the kernel instance follow them).  hint_plan_check_wjob reads it.
+    std::vector<WJob> ljobs;
+    int n_ljobs = 0, n_lsmall = 0, n_rowj = 0;  // all jobs of the list; the single-tile jobs among them; the row jobs at its end
     // which of plan_for's attempts was accepted and what it came to (hint_plan_paths; reported only: no kernel or launch site reads
     // these, and they stay out of the digests)
     int tile_cap = 0, unit_waves = 0;           // build_plan's two settings

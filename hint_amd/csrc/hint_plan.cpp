@@ -1017,6 +1017,43 @@ static void plan_wgrad_jobs(PlanBuild& b) {
     P->n_wjobs = (int)wjobs.size();
 }
 
+// ---- stage 9b: part B's launch list.  With HINT_DW3_ROWS on (default: every plan without subtree groups - there the deep units'
+//      dW3 jobs are single-tile jobs that share workgroups already, and MINIBOONE's A/B was inside its spread) the dW3 | db3 of every
+//      unit with r <= 4 comes from row jobs (hint_wgrad.hip dw_rows: one wavefront per job and split, a job per DW3R_COLS columns
+//      of the unit's a2) instead of the unit's WSRC_GST x WSRC_A2 jobs, which are dropped from the list.  The wjobs table itself
+//      (digested, and what HINT_DW3_ROWS=0 launches byte for byte) is not touched. ----
+static void plan_launch_jobs(PlanBuild& b) {
+    hint_plan* P = b.P.get();
+    const bool rows_on = knobs().dw3_rows >= 0 ? knobs().dw3_rows != 0 : P->n_sub == 0;
+    auto covered = [&](const WJob& j) { return rows_on && j.psrc == WSRC_GST && j.qsrc == WSRC_A2 && j.r_r <= 4; };
+    P->ljobs.clear();
+    P->n_lsmall = 0;
+    for (size_t i = 0; i < b.wjobs.size(); ++i) {
+        if (covered(b.wjobs[i])) continue;
+        P->ljobs.push_back(b.wjobs[i]);
+        if ((int)i >= P->n_wjobs - P->n_wsmall) ++P->n_lsmall;
+    }
+    P->n_rowj = 0;
+    for (size_t ui = 0; rows_on && ui < b.units.size(); ++ui) {
+        const Unit& u = b.units[ui];
+        const hint_node_desc& n = b.nodes[b.unit_node[ui]];
+        if (n.r > 4) continue;
+        const int64_t* po = n.p_off + (int)(ui & 1) * 6;
+        for (int c0 = 0; c0 < n.h; c0 += DW3R_COLS) {
+            WJob j{};
+            j.psrc = WSRC_GSTR; j.pcol = u.gcol; j.M = n.r; j.mw = 1;
+            j.qsrc = WSRC_A2; j.qcol = u.wcol + c0; j.N = std::min(DW3R_COLS, n.h - c0); j.nw = cdiv(j.N, 64);
+            j.ldo = n.h; j.pmax = P->ST - 1; j.qmax = P->WT - 1;
+            j.wofs = po[HINT_W3] + c0;
+            j.bofs = c0 == 0 ? po[HINT_B3] : -1;
+            j.r_r = n.r; j.r_gcol = u.gcol; j.r_h = n.h; j.r_wcol = u.wcol;
+            P->ljobs.push_back(j);
+            ++P->n_rowj;
+        }
+    }
+    P->n_ljobs = (int)P->ljobs.size();
+}
+
 // ---- stage 10: the tables as the device takes them ----
 static void finish_tables(PlanBuild& b) {
     hint_plan* P = b.P.get();
@@ -1093,7 +1130,7 @@ static int upload_plan(PlanBuild& b) {
     upload((void**)&P->d_recs, b.recs);
     upload((void**)&P->d_bmap, b.bmap);
     upload((void**)&P->d_real, b.real);
-    upload((void**)&P->d_wjobs, b.wjobs);
+    upload((void**)&P->d_wjobs, P->ljobs);
     if (!b.twmap.empty()) upload((void**)&P->d_twmap, b.twmap);
     upload((void**)&P->d_segs, b.segs);
     upload((void**)&P->d_ptiles, b.ptiles);
@@ -1127,6 +1164,7 @@ static int build_plan(const hint_node_desc* nodes, int32_t n_nodes, int32_t d, i
     if (int st = plan_lds_sizes(b, retry_smaller)) return st;
     if (int st = check_plan(b)) return st;
     plan_wgrad_jobs(b);
+    plan_launch_jobs(b);
     finish_tables(b);
     if (host_only) b.P->digests = table_digests(b);
     else if (int st = upload_plan(b)) return st;
@@ -1277,6 +1315,25 @@ int hint_plan_check_paths(const hint_node_desc* nodes, int32_t n_nodes, int32_t 
     if (P->alt4) P->alt4->num_cu = num_cu;
     paths_out(P.get(), B, out, n_out);
     return 0;
+}
+
+int64_t hint_plan_check_wjob(const hint_node_desc* nodes, int32_t n_nodes, int32_t d, int32_t dc, float clamp, int32_t variant,
+                             int64_t j, int32_t field) {
+    std::unique_ptr<hint_plan> P;
+    if (host_plan(nodes, n_nodes, d, dc, clamp, &P)) return INT64_MIN;
+    const hint_plan* V = variant ? P->alt4 : P.get();
+    if (!V) { fail("hint_plan_check_wjob: the plan has no 4-wavefront variant"); return INT64_MIN; }
+    if (j == -1 && field >= 0 && field < 5) {
+        const int64_t v[5] = {V->n_ljobs, V->n_lsmall, V->n_rowj, V->n_wjobs, V->n_wsmall};
+        return v[field];
+    }
+    if (j < 0 || j >= V->n_ljobs || field < 0 || field >= HINT_WJOB_FIELDS) {
+        fail("hint_plan_check_wjob: no job %lld / field %d (%d jobs)", (long long)j, field, V->n_ljobs);
+        return INT64_MIN;
+    }
+    const WJob& w = V->ljobs[(size_t)j];
+    const int64_t v[HINT_WJOB_FIELDS] = {w.psrc, w.pcol, w.M, w.mw, w.qsrc, w.qcol, w.N, w.nw, w.ldo, w.wofs, w.bofs, w.r_r, w.r_gcol, w.r_h, w.r_wcol};
+    return v[field];
 }
 
 void hint_plan_destroy(hint_plan* P) { delete P; }

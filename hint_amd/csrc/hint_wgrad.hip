@@ -435,13 +435,94 @@ __device__ __forceinline__ void dw_solo8(f32x4 (&acc)[3][3], float (&psum)[3], c
     cx.bb0 = bb;
 }
 
+// ---- row jobs (WSRC_GSTR): dW3 | db3 of a unit with r <= 4 ----
+// dW3 = g_st^T a2 has M = r <= 4 rows: as a 16x16x4 product 12 of the 16 output rows are padding.  v_mfma_f32_4x4x1_16B_f32 does
+// sixteen independent 4 x 4 outer products, K = 1: with cbsz:4 the A block `abid` (lanes 4 abid .. 4 abid + 3) is broadcast to all
+// sixteen, lane l supplies B of column l, and accumulator register i of lane l is out[i][l] - per batch row ONE 8-cycle
+// instruction per 64 columns, the rows added in row order.  A: one load per 16-row step (lane l: g_st[row l>>2][gcol + (l&3)], the
+// lanes with (l&3) >= r past the bound = zero), row k of the step is abid k.  B: a2[row][qcol + 64 q + l], a coalesced 256-byte
+// segment per wavefront and quad; the lanes past the job's last column read past the bound = zero, so that neither a neighbouring
+// unit's columns nor anything behind column WT is touched.  The rows of a split are all inside [0, Bp): no row is read that the
+// generic jobs would not read.  One wavefront per (job, split): nothing to combine, straight to the split's slab.
+template <int NQ, int AB>
+__device__ __forceinline__ void row_mma(f32x4 (&acc)[NQ], float a, const float (&b)[NQ]) {
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) acc[q] = __builtin_amdgcn_mfma_f32_4x4x1f32(a, b[q], acc[q], 4, AB, 0);
+}
+// rows per load group: two groups (2 x 8 x NQ loads, 48 at NQ = 3) are in flight, within the 6-bit vmcnt up to NQ = 3.  A ring of 48 loads
+// at every NQ (6 / NQ groups) was no faster: the row workgroups start the launch and end under the dW2 products (NOTES.md section 16)
+constexpr int DW_ROWS_HALF = 8;
+template <int NQ>
+__device__ __forceinline__ void dw_rows(const WJob& job, const GBlock& blk, GLOBAL_AS float* slab, int b_begin, int b_end, int WT,
+                                        int ST, int64_t a2_off, int lane) {
+    constexpr int H = DW_ROWS_HALF;
+    f32x4 acc[NQ];
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) acc[q] = zero4();
+    float asum = 0.f;
+    const int voff_a = (lane & 3) < job.M ? ((lane >> 2) * ST + job.pcol + (lane & 3)) * 4 : BUF_OOB;
+    int voff_b[NQ];
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) voff_b[q] = 64 * q + lane < job.N ? (job.qcol + 64 * q + lane) * 4 : BUF_OOB;
+    const GLOBAL_AS float* gp = blk.wsGST;
+    const GLOBAL_AS float* ap = blk.actA1 + a2_off;
+    struct Half { float b[H][NQ]; };
+    // (descriptors of the 16 rows of a step, re-based by the scalar unit; the row inside the step rides in the scalar offset)
+    auto load_a = [&](int bb) {
+        return buf_f32(__builtin_amdgcn_make_buffer_rsrc((void*)(gp + (size_t)bb * ST), 0, 16 * ST * 4, BUF_FLAGS), voff_a);
+    };
+    auto load_b = [&](int bb, int half) {
+        Half h;
+        const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc((void*)(ap + (size_t)bb * WT), 0, 16 * WT * 4, BUF_FLAGS);
+#pragma unroll
+        for (int k = 0; k < H; ++k)
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) h.b[k][q] = as_f32(__builtin_amdgcn_raw_buffer_load_b32(r, voff_b[q], (H * half + k) * WT * 4, 0));
+        return h;
+    };
+#define DW_ROWS_MMA(A_, H_, AB0_) \
+    row_mma<NQ, AB0_ + 0>(acc, A_, H_.b[0]); row_mma<NQ, AB0_ + 1>(acc, A_, H_.b[1]); row_mma<NQ, AB0_ + 2>(acc, A_, H_.b[2]); \
+    row_mma<NQ, AB0_ + 3>(acc, A_, H_.b[3]); row_mma<NQ, AB0_ + 4>(acc, A_, H_.b[4]); row_mma<NQ, AB0_ + 5>(acc, A_, H_.b[5]); \
+    row_mma<NQ, AB0_ + 6>(acc, A_, H_.b[6]); row_mma<NQ, AB0_ + 7>(acc, A_, H_.b[7]);
+    static_assert(H == 8, "DW_ROWS_MMA names eight rows");
+    if (b_begin < b_end) {            // (the rows of a split: a multiple of 16)
+        const int last_bb = b_end - 16;
+        float a = load_a(b_begin);
+        Half h0 = load_b(b_begin, 0);
+        for (int bb = b_begin; bb < b_end; bb += 16) {
+            const Half h1 = load_b(bb, 1);
+            DW_ROWS_MMA(a, h0, 0)
+            const int nb = min(bb + 16, last_bb);      // (never under a branch: behind the last step it is loaded again)
+            const float an = load_a(nb);
+            h0 = load_b(nb, 0);
+            DW_ROWS_MMA(a, h1, 8)
+            asum += a;
+            a = an;
+        }
+    }
+#undef DW_ROWS_MMA
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+        if (64 * q + lane >= job.N) continue;
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            if (i < job.M) slab[job.wofs + (size_t)i * job.ldo + 64 * q + lane] = acc[q][i];
+    }
+    if (job.bofs >= 0) {              // db3: lane l holds the sum of column l & 3 over the rows l >> 2 of every step
+        asum += __shfl_xor(asum, 4, 64);
+        asum += __shfl_xor(asum, 8, 64);
+        asum += __shfl_xor(asum, 16, 64);
+        asum += __shfl_xor(asum, 32, 64);
+        if (lane < job.M) slab[job.bofs + lane] = asum;
+    }
+}
 
 // SMALL: the job list ends in single-tile jobs that share workgroups (n_small > 0); plans without them (the wave-local ones)
 // run the instance that holds none of that code
 // WIDE: the plan has lean-wide groups (dw_leanw); the other plans run the instances without that code
 template <bool SMALL, bool WIDE>
 __global__ __launch_bounds__(DW_WAVES * 64 HINT_DW_BOUND) void hint_wgrad_kernel(
-    const WJob* __restrict__ jobs, int n_jobs, int n_small, int splits, ChainBlock one, const ChainBlock* __restrict__ chain,
+    const WJob* __restrict__ jobs, int n_jobs, int n_small, int n_rowj, int splits, ChainBlock one, const ChainBlock* __restrict__ chain,
     int grid_pb, int cb0, int WT, int ST, int d, int dc, int n_levels, int B, int Bp, int rows_per_wg, int64_t act_stride,
     int64_t a2_off, int64_t bits_a2_off, int64_t param_floats, const float* __restrict__ x, const float* __restrict__ c
 #ifdef HINT_STAMPS
@@ -460,7 +541,11 @@ __global__ __launch_bounds__(DW_WAVES * 64 HINT_DW_BOUND) void hint_wgrad_kernel
     // The last n_small jobs of the list are single-tile jobs (deep levels of narrow trees: an 8 x 8 matrix): eight of them share a
     // workgroup, one (job, split) per WAVEFRONT over all rows of the split - no combine, no barrier: a workgroup per such job
     // spends its time in the fixed costs (MINIBOONE d = 43: 12 000 workgroups for 60 MFLOP)
-    const int n_big = n_jobs - n_small, items = n_big + (n_small + DW_WAVES - 1) / DW_WAVES;
+    // The last n_rowj jobs of the list (behind the single-tile ones) are row jobs (dw_rows): DW_WAVES of them share a workgroup the
+    // same way.  Their wavefronts walk all rows of a split alone - the longest latency chains of the launch - so their
+    // workgroups take the FIRST item numbers: they start with the launch and end under the dW2 products
+    const int row_items = (n_rowj + DW_WAVES - 1) / DW_WAVES;
+    const int n_big = n_jobs - n_small - n_rowj, items = row_items + n_big + (n_small + DW_WAVES - 1) / DW_WAVES;
     // grid_pb > 0: the chain's blocks one after the other; < 0 (jobs sorted longest first: narrow trees): job j of ALL blocks
     // next to each other, so that the order is longest-first over the whole launch
     int cbi, bid;
@@ -492,6 +577,23 @@ __global__ __launch_bounds__(DW_WAVES * 64 HINT_DW_BOUND) void hint_wgrad_kernel
     }
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = rfl(tid >> 6);
+    if (item < row_items) {
+        const int jr = n_jobs - n_rowj + item * DW_WAVES + wave;
+        if (jr >= n_jobs) return;       // (a spare wavefront of the last shared workgroup: no barrier on this path)
+        const WJob job = jobs[jr];
+        const int b_begin = split * rows_per_wg, b_end = min(Bp, b_begin + rows_per_wg);
+        GLOBAL_AS float* slab = blk.wsSlab + (size_t)split * param_floats;
+        switch (job.nw) {
+            case 1: dw_rows<1>(job, blk, slab, b_begin, b_end, WT, ST, a2_off, lane); break;
+            case 2: dw_rows<2>(job, blk, slab, b_begin, b_end, WT, ST, a2_off, lane); break;
+            case 3: dw_rows<3>(job, blk, slab, b_begin, b_end, WT, ST, a2_off, lane); break;
+            default: dw_rows<4>(job, blk, slab, b_begin, b_end, WT, ST, a2_off, lane); break;
+        }
+        DW_STAMP_WAIT(5)
+        DW_STAMP_FLUSH()
+        return;
+    }
+    item -= row_items;
     const bool solo = SMALL && item >= n_big;
     const int jidx = solo ? n_big + (item - n_big) * DW_WAVES + wave : item;
     if (jidx >= n_jobs) return;         // (a spare wavefront of the last shared workgroup: that path has no barrier)
@@ -770,7 +872,7 @@ __global__ __launch_bounds__(256) void hint_wreduce_kernel(ChainBlock one, const
 
 namespace hint {
 
-hipError_t launch_wgrad(const WJob* jobs, int n_jobs, int n_small, int splits, const ChainBlock& one, const ChainBlock* chain,
+hipError_t launch_wgrad(const WJob* jobs, int n_jobs, int n_small, int n_rowj, int splits, const ChainBlock& one, const ChainBlock* chain,
                         int n_chain, int cb0, int WT, int ST, int d, int dc, int n_levels, int B, int Bp, int rows_per_wg,
                         int64_t act_stride, int64_t a2_off, int64_t bits_a2_off, int64_t param_floats, const float* x,
                         const float* c, const uint8_t* real, int accumulate, const int32_t* twmap, int tw_floats,
@@ -779,18 +881,18 @@ hipError_t launch_wgrad(const WJob* jobs, int n_jobs, int n_small, int splits, c
     const bool interleave = n_small < 0;       // (flag in the sign: the planner sorted the jobs)
     if (interleave) n_small = -n_small - 1;
 #ifdef HINT_DW_SOLO_ALL
-    n_small = n_jobs;                          // (experiment: one (job, split) per wavefront for every job)
+    n_small = n_jobs - n_rowj;                          // (experiment: one (job, split) per wavefront for every job)
     small = n_jobs > 0;
 #endif
-    const int used = (n_jobs - n_small + (n_small + DW_WAVES - 1) / DW_WAVES) * splits;
+    const int used = (n_jobs - n_small - n_rowj + (n_small + DW_WAVES - 1) / DW_WAVES + (n_rowj + DW_WAVES - 1) / DW_WAVES) * splits;
     const int grid_pb = n_chain > 1 ? (used + 7) / 8 * 8 : used;
     if (used > 0) {
         const int gpb = (interleave && n_chain > 1 && (splits & 7) == 0) ? -grid_pb : grid_pb;
 #ifdef HINT_STAMPS
-#define HINT_DW_LAUNCH(S_, W_) hipLaunchKernelGGL((hint_wgrad_kernel<S_, W_>), dim3(grid_pb * n_chain), dim3(DW_WAVES * 64), 0, stream, jobs, n_jobs, n_small, splits, \
+#define HINT_DW_LAUNCH(S_, W_) hipLaunchKernelGGL((hint_wgrad_kernel<S_, W_>), dim3(grid_pb * n_chain), dim3(DW_WAVES * 64), 0, stream, jobs, n_jobs, n_small, n_rowj, splits, \
                                one, chain, gpb, cb0, WT, ST, d, dc, n_levels, B, Bp, rows_per_wg, act_stride, a2_off, bits_a2_off, param_floats, x, c, h_dw_stamps)
 #else
-#define HINT_DW_LAUNCH(S_, W_) hipLaunchKernelGGL((hint_wgrad_kernel<S_, W_>), dim3(grid_pb * n_chain), dim3(DW_WAVES * 64), 0, stream, jobs, n_jobs, n_small, splits, \
+#define HINT_DW_LAUNCH(S_, W_) hipLaunchKernelGGL((hint_wgrad_kernel<S_, W_>), dim3(grid_pb * n_chain), dim3(DW_WAVES * 64), 0, stream, jobs, n_jobs, n_small, n_rowj, splits, \
                                one, chain, gpb, cb0, WT, ST, d, dc, n_levels, B, Bp, rows_per_wg, act_stride, a2_off, bits_a2_off, param_floats, x, c)
 #endif
         // (small, wide: dispatch() in hint_abi.cpp - small is n_small > 0)

@@ -156,6 +156,17 @@ int hint_plan_check_paths(const hint_node_desc* nodes, int32_t n_nodes, int32_t 
 #define HINT_PLAN_DIGESTS 12
 int hint_plan_check_digest(const hint_node_desc* nodes, int32_t n_nodes, int32_t d, int32_t dc, float clamp, uint64_t* out,
                            int32_t n_out);
+/* Host-only as well: part B's launch list of the plan (variant 0) or of its 4-wavefront variant (1) - the weight-gradient jobs
+ * table, minus the dW3 jobs that row jobs replace (HINT_DW3_ROWS: units with at most 4 outputs), followed by those row jobs.
+ * j = -1: field 0 the jobs of the list, 1 the single-tile jobs among them, 2 the row jobs at its end, 3 and 4 the jobs and the
+ * single-tile jobs of the table itself.  j >= 0, one value of job j: [0] P operand (2 g_st, 8 rebuilt g2, 9 g_st of a row job, ..)
+ * [1] its first column  [2] output rows M  [3] 16-row tiles of M  [4] Q operand (4 a2, ..)  [5] its first column  [6] output
+ * columns N  [7] 16-column tiles of N (row jobs: 64-column quads)  [8] row stride of the output  [9] float offset of out[0][0] in the
+ * flat gradient  [10] float offset of the bias gradient or -1  [11] [12] [13] [14] the unit's outputs r, its first g_st column, its
+ * hidden width, its first a2 column.  INT64_MIN on error (hint_last_error). */
+#define HINT_WJOB_FIELDS 15
+int64_t hint_plan_check_wjob(const hint_node_desc* nodes, int32_t n_nodes, int32_t d, int32_t dc, float clamp, int32_t variant,
+                             int64_t j, int32_t field);
 
 /* Re-pack the flat parameters into `packed` (hint_plan_packed_floats floats).  Must be called
  * after every change of the parameters and before the next forward / inverse / backward that

@@ -9,7 +9,8 @@
 // hint_lensfit_kernel: the shape of hint_hausdorff_kernel - a persistent grid of G workgroups of 256 threads; workgroup w takes
 // rows w, w + G, ... one at a time and runs the row's S starts one after the other, so the selection needs no second launch and
 // no traffic between workgroups.  Built on hint_pointset.hpp: the trace, the own points, the placement, the walk in its form
-// that keeps the index of the minimum, the reduction.  This file adds the gradient's terms and the update rule:
+// that keeps the index of the minimum, the reduction; and on hint_fit.hpp: the driver around an evaluation (the state, the trace
+// record, the update rule, the selection over the starts).  This file adds the evaluation - the gradient's terms:
 //   - once per workgroup: the P - 1 twiddles and the untransformed prototype (M <= 1024: one tile) to LDS;
 //   - per row: the coefficients; B traced or loaded into LDS; each thread holds its <= 4 B points in registers;
 //   - per step: thread 0 stages the pose of the parameters (ps_stage_pose); every thread places its <= 4 prototype points
@@ -17,25 +18,21 @@
 //     points, both keeping the index of the minimum; the selected pairs' terms are recomputed in fp32 (q by ps_rotate from the
 //     prototype in LDS: the same operations, the same bits) and added in double; ten double sums - the loss term and the four
 //     gradient terms of either side, kept apart because the weights are applied after the sums - go through ps_block_reduce;
-//     thread 0 forms the loss and the gradient, writes the trace and takes the step.  Three barriers a step.
+//     thread 0 forms the loss and the gradient, then records and takes the step (fit_step).  Three barriers a step.
 // The state of a fit (parameters, momentum buffer, the two learning rates) lives in LDS and is set afresh for every start.
 // Nothing is carried from row to row and no output is read back.  No float atomics, no counters, no workspace.
 // Untuned defaults (a workgroup per row although at P = 100, M = 130 only 130 threads hold a point; starts in sequence): DESIGN
 // section 16.
 #include "hint_pointset.hpp"
+#include "hint_fit.hpp"
 
 namespace hint {
-constexpr int LF_MAX_WG = 1024;                 // the grid cap: 256 CUs x 4 workgroups (32.8 KiB of LDS each)
-constexpr int LF_MAX_M = PS_TILE, LF_MAX_S = 16, LF_MAX_STEPS = 1024;
+constexpr int LF_MAX_M = PS_TILE;
 }
 
-// a fit's state in LDS
-struct lf_state {
-    float p[4], buf[4];                          // x, y, scale, angle; the momentum buffer
+// a fit's state in LDS: p = x, y, scale, angle
+struct lf_state : fit_state<4> {
     ps_pose pose;                                // of p, staged before every evaluation
-    double lr, alr;                              // the learning rates before their fp32 rounding
-    float best_p[4], best_l;
-    int best;
 };
 
 // the terms of a selected pair (e = A_i - B_j, q = the rotated prototype point) onto five double sums
@@ -67,7 +64,7 @@ __global__ __launch_bounds__(256) void hint_lensfit_kernel(const float* __restri
     const int t = threadIdx.x, C = 4 * K;
     const bool traced = x != nullptr;
     const int ncA = (M + PS_THREADS - 1) / PS_THREADS, ncB = (P + PS_THREADS - 1) / PS_THREADS;
-    const int evals = n_steps > 0 ? n_steps : 1;             // n_steps = 0: one evaluation, no update
+    const int evals = fit_evals(n_steps);
     if (traced) ps_twiddles(tw, P, t);
     for (int i = t; i < M; i += PS_THREADS) ps_load_point(A0[i], a_points + 2 * (size_t)i);
     for (int row = blockIdx.x; row < n; row += gridDim.x) {                  // (n <= 2^30)
@@ -80,13 +77,8 @@ __global__ __launch_bounds__(256) void hint_lensfit_kernel(const float* __restri
 #pragma unroll 1
         for (int s = 0; s < S; ++s) {
             const size_t rs = (size_t)row * S + s;
-            if (t == 0) {                                    // the fit starts afresh
-                for (int k = 0; k < 4; ++k) {
-                    st.p[k] = starts[4 * rs + k];
-                    st.buf[k] = 0.f;
-                }
-                st.lr = lr0;
-                st.alr = alr0;
+            if (t == 0) {
+                fit_begin(st, starts, rs, lr0, alr0);
                 ps_stage_pose(st.p, &st.pose);
             }
             float L = 0.f, g[4] = {0.f, 0.f, 0.f, 0.f};      // of the last evaluation (thread 0)
@@ -148,45 +140,14 @@ __global__ __launch_bounds__(256) void hint_lensfit_kernel(const float* __restri
                     g[2] = (float)(2.0 * (sm[3] / dP + weight * (sm[8] / dM)));
                     g[3] = (float)(2.0 * (double)ps.scale * (sm[4] / dP + weight * (sm[9] / dM)));
                     if (n_steps > 0) {
-                        if (trace) {
-                            float* tr = trace + 9 * (rs * (size_t)n_steps + it);
-                            for (int k = 0; k < 4; ++k) {
-                                tr[k] = st.p[k];
-                                tr[5 + k] = g[k];
-                            }
-                            tr[4] = L;
-                        }
-                        const float lr = (float)st.lr, alr = (float)st.alr;
-                        for (int k = 0; k < 4; ++k) {
-                            const float b = it == 0 ? g[k] : __fmaf_rn(momentum, st.buf[k], g[k]);
-                            st.buf[k] = b;
-                            st.p[k] = __fmaf_rn(-(k == 3 ? alr : lr), b, st.p[k]);
-                        }
-                        st.lr *= gamma;
-                        st.alr *= gamma;
+                        fit_step(st, trace, rs * (size_t)n_steps + it, it, L, g, momentum, gamma);
                         if (it + 1 < evals) ps_stage_pose(st.p, &st.pose);
                     }
                 }
             }
-            if (t == 0) {                                    // the start's result, and the row's best so far
-                if (all_params)
-                    for (int k = 0; k < 4; ++k) all_params[4 * rs + k] = st.p[k];
-                if (all_loss) all_loss[rs] = L;
-                if (grad)
-                    for (int k = 0; k < 4; ++k) grad[4 * rs + k] = g[k];
-                if (s == 0 || L < st.best_l || (st.best_l != st.best_l && L == L)) {     // (a NaN compares as larger)
-                    for (int k = 0; k < 4; ++k) st.best_p[k] = st.p[k];
-                    st.best_l = L;
-                    st.best = s;
-                }
-            }
+            if (t == 0) fit_close_start(st, s, rs, L, g, all_params, all_loss, grad);
         }
-        if (t == 0) {
-            if (params)
-                for (int k = 0; k < 4; ++k) params[4 * (size_t)row + k] = st.best_p[k];
-            if (loss) loss[row] = st.best_l;
-            if (best) best[row] = st.best;
-        }
+        if (t == 0) fit_close_row(st, (size_t)row, params, loss, best);
         // (the next row's first barrier comes before anything of this row in LDS is overwritten but coef, which no one reads now)
     }
 }
@@ -194,18 +155,11 @@ __global__ __launch_bounds__(256) void hint_lensfit_kernel(const float* __restri
 // ---- the C ABI ----
 using namespace hint;
 
-static int lf_check_sizes(const char* who, int64_t n_rows, int32_t n_coeffs, int32_t n_points, int64_t n_template, int32_t n_starts,
-                          int32_t n_steps, bool traced) {
+// the sizes that come before the fit's own (fit_check, fit_check_sizes)
+static int lf_check_sizes(const char* who, int64_t n_rows, int32_t n_coeffs, int32_t n_points, int64_t n_template, bool traced) {
     if (ps_check_sizes(who, n_rows, n_coeffs, n_points, traced)) return 1;
     if (n_template < 1 || n_template > LF_MAX_M)
         return fail("%s: n_template must be 1..%d (got %lld)", who, LF_MAX_M, (long long)n_template);
-    if (n_starts < 1 || n_starts > LF_MAX_S) return fail("%s: n_starts must be 1..%d (got %d)", who, LF_MAX_S, n_starts);
-    if (n_steps < 0 || n_steps > LF_MAX_STEPS) return fail("%s: n_steps must be 0..%d (got %d)", who, LF_MAX_STEPS, n_steps);
-    return 0;
-}
-
-static int lf_check_rate(const char* who, const char* name, double v) {
-    if (!std::isfinite(v) || v < 0.0) return fail("%s: %s must be finite and >= 0 (got %g)", who, name, v);
     return 0;
 }
 
@@ -214,8 +168,9 @@ extern "C" {
 size_t hint_lensfit_workspace_bytes(int64_t n_rows, int32_t n_coeffs, int32_t n_points, int64_t n_template, int32_t n_starts,
                                     int32_t n_steps) {
     // n_coeffs = 0 stands for the given-points source, which has no coefficients
-    if (lf_check_sizes("hint_lensfit_workspace_bytes", n_rows, n_coeffs, n_points, n_template, n_starts, n_steps, n_coeffs != 0))
-        return 0;
+    const char* who = "hint_lensfit_workspace_bytes";
+    if (lf_check_sizes(who, n_rows, n_coeffs, n_points, n_template, n_coeffs != 0)) return 0;
+    if (fit_check_sizes(who, n_starts, n_steps)) return 0;
     last_error_ref().clear();
     return 0;                                                // the kernel needs none
 }
@@ -227,7 +182,7 @@ int64_t hint_lensfit_geometry(int64_t n_rows, int32_t n_points, int32_t field) {
              "3 the grid cap, 4 the most prototype points)", field);
         return -1;
     }
-    const int64_t out[5] = {ps_grid(n_rows, 0, LF_MAX_WG), 1, PS_TILE, LF_MAX_WG, LF_MAX_M};
+    const int64_t out[5] = {ps_grid(n_rows, 0, FIT_MAX_WG), 1, PS_TILE, FIT_MAX_WG, LF_MAX_M};
     return out[field];
 }
 
@@ -239,13 +194,8 @@ int hint_lensfit_run(const hint_lensfit_desc* desc, void* stream) {
     if (ps_check_source(who, desc->x, desc->b_points, "the curve needs a source")) return 1;
     if (!desc->params && !desc->loss && !desc->best && !desc->all_params && !desc->all_loss && !desc->grad && !desc->trace)
         return fail("%s: no output requested (params, loss, best, all_params, all_loss, grad and trace are all null)", who);
-    if (lf_check_sizes(who, desc->n_rows, desc->n_coeffs, desc->n_points, desc->n_template, desc->n_starts, desc->n_steps,
-                       desc->x != nullptr))
-        return 1;
-    if (desc->trace && desc->n_steps == 0) return fail("%s: trace holds a record per step, and n_steps is 0", who);
-    if (lf_check_rate(who, "lr", desc->lr) || lf_check_rate(who, "angle_lr", desc->angle_lr) ||
-        lf_check_rate(who, "gamma", desc->gamma) || lf_check_rate(who, "momentum", desc->momentum))
-        return 1;
+    if (lf_check_sizes(who, desc->n_rows, desc->n_coeffs, desc->n_points, desc->n_template, desc->x != nullptr)) return 1;
+    if (fit_check(who, desc->n_starts, desc->n_steps, desc->lr, desc->angle_lr, desc->gamma, desc->momentum, desc->trace)) return 1;
     if (!std::isfinite(desc->weight)) return fail("%s: weight must be finite (got %g)", who, desc->weight);
     if (ps_check_groups(who, desc->max_groups)) return 1;
     if (ps_check_aligned(who, {{"x", desc->x, 3}, {"b_points", desc->b_points, 3}, {"a_points", desc->a_points, 3},
@@ -253,7 +203,7 @@ int hint_lensfit_run(const hint_lensfit_desc* desc, void* stream) {
                                {"best", desc->best, 3}, {"all_params", desc->all_params, 3}, {"all_loss", desc->all_loss, 3},
                                {"grad", desc->grad, 3}, {"trace", desc->trace, 3}}))
         return 1;
-    const int grid = ps_grid(desc->n_rows, desc->max_groups, LF_MAX_WG);
+    const int grid = ps_grid(desc->n_rows, desc->max_groups, FIT_MAX_WG);
     hipLaunchKernelGGL(hint_lensfit_kernel, dim3(grid), dim3(PS_THREADS), 0, (hipStream_t)stream, desc->x, desc->b_points,
                        (int)desc->n_rows, desc->x ? desc->n_coeffs : 1, desc->n_points, desc->a_points, (int)desc->n_template,
                        desc->starts, desc->n_starts, desc->n_steps, desc->lr, desc->angle_lr, desc->gamma, (float)desc->momentum,

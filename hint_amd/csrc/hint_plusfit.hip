@@ -10,7 +10,8 @@
 //
 // hint_plusfit_kernel: the shape of hint_lensfit_kernel - a persistent grid of G workgroups of 256 threads; workgroup w takes rows
 // w, w + G, ... one at a time and runs the row's S starts one after the other.  Built on hint_pointset.hpp (the trace, the own
-// points, the reduction) and hint_plusgeom.hpp (the row's geometry: the operations and the bits of hint_plus_kernel):
+// points, the reduction), hint_plusgeom.hpp (the row's geometry: the operations and the bits of hint_plus_kernel) and hint_fit.hpp
+// (the driver the two fits share).  This file adds the evaluation, the weight schedule, the early stop and the not-run fill:
 //   - once per workgroup: the P - 1 twiddles; per row: the coefficients; B traced or loaded into LDS; each thread holds its <= 4
 //     B points in registers;
 //   - per step: thread 0 has staged the parameters (pl_stage_params); lanes 0..11 of wavefront 0 stage the twelve segments;
@@ -19,26 +20,22 @@
 //     minimum is the nearest point, the lowest index among equals); per point (v, t = len / L, the segment) goes to LDS, and
 //     192 threads - 8 a sum - add the products v (1 - t), v t onto the 24 vertex sums in double, in index order (no indexed
 //     register array, no scratch); the segment term goes through ps_block_reduce; thread 0 adds the corner term, chains the 24
-//     vertex derivatives to the nine parameters through LDS, writes the trace, takes the step and stages the next parameters.
+//     vertex derivatives to the nine parameters through LDS, records and takes the step (fit_step) and stages the next parameters.
 //     Four barriers a step.
 // The state of a fit (parameters, momentum buffer, the two learning rates) lives in LDS and is set afresh for every start.
 // Nothing is carried from row to row and no output is read back.  No float atomics, no counters, no workspace.
 // Untuned defaults (a workgroup per row although at P = 100 only 100 threads hold a point; the serial chain by thread 0; starts in
 // sequence): DESIGN section 17.
 #include "hint_plusgeom.hpp"
+#include "hint_fit.hpp"
 
 namespace hint {
-constexpr int PF_MAX_WG = 1024;                 // the grid cap: 256 CUs x 4 workgroups
-constexpr int PF_MAX_S = 16, PF_MAX_STEPS = 1024;
 constexpr int PF_NP = 9, PF_REC = 19;           // parameters; floats of a trace record (p [9], L, g [9])
 }
 
 // a fit's state in LDS
-struct pf_state {
-    float p[9], buf[9];                          // the parameters; the momentum buffer
-    double lr, alr;                              // the learning rates before their fp32 rounding
-    float best_p[9], best_l;
-    int best, n_run, stop;
+struct pf_state : fit_state<hint::PF_NP> {
+    int n_run, stop;
     double sm[25];                               // the workgroup's sums of a step: the segment term, 12 vertices x (x, y)
     double gw[24];                               // dL / dW: vertex k at [2 k], [2 k + 1]
     double gc[8];                                // dL / d the clamped coordinates, in the order of PL_VX / PL_VY
@@ -168,7 +165,7 @@ __global__ __launch_bounds__(256) void hint_plusfit_kernel(const float* __restri
     __shared__ float gout[PF_NP + 1];                        // thread 0's loss and gradient of the last evaluation
     const int t = threadIdx.x, l = t & 63, wv = t >> 6, C = 4 * K;
     const bool traced = x != nullptr;
-    const int evals = n_steps > 0 ? n_steps : 1;             // n_steps = 0: one evaluation, no update
+    const int evals = fit_evals(n_steps);
     const float qnan = __int_as_float(0x7fc00000);
     if (traced) ps_twiddles(tw, P, t);
     for (int row = blockIdx.x; row < n; row += gridDim.x) {                  // (n <= 2^30)
@@ -195,13 +192,8 @@ __global__ __launch_bounds__(256) void hint_plusfit_kernel(const float* __restri
                     for (int i = t; i < PF_REC * n_steps; i += PS_THREADS) trace[PF_REC * rs * (size_t)n_steps + i] = qnan;
                 continue;
             }
-            if (t == 0) {                                    // the fit starts afresh
-                for (int k = 0; k < PF_NP; ++k) {
-                    st.p[k] = starts[PF_NP * rs + k];
-                    st.buf[k] = 0.f;
-                }
-                st.lr = lr0;
-                st.alr = alr0;
+            if (t == 0) {
+                fit_begin(st, starts, rs, lr0, alr0);
                 pl_stage_params(st.p, &rw);
             }
 #pragma unroll 1
@@ -301,51 +293,21 @@ __global__ __launch_bounds__(256) void hint_plusfit_kernel(const float* __restri
                                                                   : corner_weight;
                     st.sm[0] = sm[0];
                     pf_chain(redk, Bp, P, &rw, &st, cw, gout);
-                    const float* g = gout;
-                    const float L = gout[PF_NP];
                     if (n_steps > 0) {
-                        if (trace) {
-                            float* tr = trace + PF_REC * (rs * (size_t)n_steps + it);
-                            for (int k = 0; k < PF_NP; ++k) {
-                                tr[k] = st.p[k];
-                                tr[PF_NP + 1 + k] = g[k];
-                            }
-                            tr[PF_NP] = L;
-                        }
-                        const float lr = (float)st.lr, alr = (float)st.alr;
-                        for (int k = 0; k < PF_NP; ++k) {
-                            const float b = it == 0 ? g[k] : __fmaf_rn(momentum, st.buf[k], g[k]);
-                            st.buf[k] = b;
-                            st.p[k] = __fmaf_rn(-(k == PF_NP - 1 ? alr : lr), b, st.p[k]);
-                        }
-                        st.lr *= gamma;
-                        st.alr *= gamma;
+                        fit_step(st, trace, rs * (size_t)n_steps + it, it, gout[PF_NP], gout, momentum, gamma);
                         if (it + 1 < evals) pl_stage_params(st.p, &rw);
                     }
                 }
             }
-            if (t == 0) {                                    // the start's result, and the row's best so far
-                const float L = gout[PF_NP];
-                if (all_params)
-                    for (int k = 0; k < PF_NP; ++k) all_params[PF_NP * rs + k] = st.p[k];
-                if (all_loss) all_loss[rs] = L;
-                if (grad)
-                    for (int k = 0; k < PF_NP; ++k) grad[PF_NP * rs + k] = gout[k];
-                if (s == 0 || L < st.best_l || (st.best_l != st.best_l && L == L)) {     // (a NaN compares as larger)
-                    for (int k = 0; k < PF_NP; ++k) st.best_p[k] = st.p[k];
-                    st.best_l = L;
-                    st.best = s;
-                }
+            if (t == 0) {
+                fit_close_start(st, s, rs, gout[PF_NP], gout, all_params, all_loss, grad);
                 st.n_run = s + 1;
-                if (stop_loss > 0.0 && (double)L < stop_loss) st.stop = 1;               // (a NaN on either side never stops)
+                if (stop_loss > 0.0 && (double)gout[PF_NP] < stop_loss) st.stop = 1;     // (a NaN on either side never stops)
             }
             __syncthreads();                                 // st.stop is the workgroup's
         }
         if (t == 0) {
-            if (params)
-                for (int k = 0; k < PF_NP; ++k) params[PF_NP * (size_t)row + k] = st.best_p[k];
-            if (loss) loss[row] = st.best_l;
-            if (best) best[row] = st.best;
+            fit_close_row(st, (size_t)row, params, loss, best);
             if (n_run) n_run[row] = st.n_run;
         }
         // (the next row's first barrier comes before anything of this row in LDS is overwritten but coef, which no one reads now)
@@ -355,24 +317,12 @@ __global__ __launch_bounds__(256) void hint_plusfit_kernel(const float* __restri
 // ---- the C ABI ----
 using namespace hint;
 
-static int pf_check_sizes(const char* who, int64_t n_rows, int32_t n_coeffs, int32_t n_points, int32_t n_starts, int32_t n_steps,
-                          bool traced) {
-    if (ps_check_sizes(who, n_rows, n_coeffs, n_points, traced)) return 1;
-    if (n_starts < 1 || n_starts > PF_MAX_S) return fail("%s: n_starts must be 1..%d (got %d)", who, PF_MAX_S, n_starts);
-    if (n_steps < 0 || n_steps > PF_MAX_STEPS) return fail("%s: n_steps must be 0..%d (got %d)", who, PF_MAX_STEPS, n_steps);
-    return 0;
-}
-
-static int pf_check_rate(const char* who, const char* name, double v) {
-    if (!std::isfinite(v) || v < 0.0) return fail("%s: %s must be finite and >= 0 (got %g)", who, name, v);
-    return 0;
-}
-
 extern "C" {
 
 size_t hint_plusfit_workspace_bytes(int64_t n_rows, int32_t n_coeffs, int32_t n_points, int32_t n_starts, int32_t n_steps) {
     // n_coeffs = 0 stands for the given-points source, which has no coefficients
-    if (pf_check_sizes("hint_plusfit_workspace_bytes", n_rows, n_coeffs, n_points, n_starts, n_steps, n_coeffs != 0)) return 0;
+    const char* who = "hint_plusfit_workspace_bytes";
+    if (ps_check_sizes(who, n_rows, n_coeffs, n_points, n_coeffs != 0) || fit_check_sizes(who, n_starts, n_steps)) return 0;
     last_error_ref().clear();
     return 0;                                                // the kernel needs none
 }
@@ -384,7 +334,7 @@ int64_t hint_plusfit_geometry(int64_t n_rows, int32_t n_points, int32_t field) {
              "3 the grid cap, 4 the most starts)", field);
         return -1;
     }
-    const int64_t out[5] = {ps_grid(n_rows, 0, PF_MAX_WG), 1, PS_PER, PF_MAX_WG, PF_MAX_S};
+    const int64_t out[5] = {ps_grid(n_rows, 0, FIT_MAX_WG), 1, PS_PER, FIT_MAX_WG, FIT_MAX_S};
     return out[field];
 }
 
@@ -396,12 +346,8 @@ int hint_plusfit_run(const hint_plusfit_desc* desc, void* stream) {
     if (!desc->params && !desc->loss && !desc->best && !desc->n_run && !desc->all_params && !desc->all_loss && !desc->grad &&
         !desc->trace)
         return fail("%s: no output requested (params, loss, best, n_run, all_params, all_loss, grad and trace are all null)", who);
-    if (pf_check_sizes(who, desc->n_rows, desc->n_coeffs, desc->n_points, desc->n_starts, desc->n_steps, desc->x != nullptr))
-        return 1;
-    if (desc->trace && desc->n_steps == 0) return fail("%s: trace holds a record per step, and n_steps is 0", who);
-    if (pf_check_rate(who, "lr", desc->lr) || pf_check_rate(who, "angle_lr", desc->angle_lr) ||
-        pf_check_rate(who, "gamma", desc->gamma) || pf_check_rate(who, "momentum", desc->momentum))
-        return 1;
+    if (ps_check_sizes(who, desc->n_rows, desc->n_coeffs, desc->n_points, desc->x != nullptr)) return 1;
+    if (fit_check(who, desc->n_starts, desc->n_steps, desc->lr, desc->angle_lr, desc->gamma, desc->momentum, desc->trace)) return 1;
     if (!std::isfinite(desc->corner_weight)) return fail("%s: corner_weight must be finite (got %g)", who, desc->corner_weight);
     if (ps_check_groups(who, desc->max_groups)) return 1;
     if (ps_check_aligned(who, {{"x", desc->x, 3}, {"b_points", desc->b_points, 3}, {"starts", desc->starts, 3},
@@ -409,7 +355,7 @@ int hint_plusfit_run(const hint_plusfit_desc* desc, void* stream) {
                                {"n_run", desc->n_run, 3}, {"all_params", desc->all_params, 3}, {"all_loss", desc->all_loss, 3},
                                {"grad", desc->grad, 3}, {"trace", desc->trace, 3}}))
         return 1;
-    const int grid = ps_grid(desc->n_rows, desc->max_groups, PF_MAX_WG);
+    const int grid = ps_grid(desc->n_rows, desc->max_groups, FIT_MAX_WG);
     hipLaunchKernelGGL(hint_plusfit_kernel, dim3(grid), dim3(PS_THREADS), 0, (hipStream_t)stream, desc->x, desc->b_points,
                        (int)desc->n_rows, desc->x ? desc->n_coeffs : 1, desc->n_points, desc->starts, desc->n_starts,
                        desc->n_steps, desc->lr, desc->angle_lr, desc->gamma, (float)desc->momentum, desc->corner_weight,

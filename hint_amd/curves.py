@@ -569,27 +569,64 @@ def _fit_args(curve, prototype, who: str):
     return curve, n, k, p, prototype
 
 
+def _fit_run(desc_cls, entry: str, n_params: int, fields: dict, curve: torch.Tensor, k: int, p: int, starts: torch.Tensor,
+             n_steps: int, lr: float, angle_lr: float, gamma: float, momentum: float, want, max_groups: int, out):
+    """one run of a fit's entry point on checked arguments, what _lf_run and _pf_run share: a dict of the outputs named in `want`.
+    fields: the descriptor's fields beside the curve, the starts and the schedule (a trace record is 2 n_params + 1 floats)"""
+    lib = _lib.load()
+    n, dev, s = curve.shape[0], curve.device, starts.shape[1]
+    with torch.cuda.device(dev):
+        desc = desc_cls()
+        _set_curve(desc, curve, n, k, p)
+        desc.starts, desc.n_starts, desc.n_steps = starts.data_ptr(), s, n_steps
+        desc.lr, desc.angle_lr, desc.gamma, desc.momentum = lr, angle_lr, gamma, momentum
+        for name, v in fields.items():
+            setattr(desc, name, v)
+        table = dict(params=((n, n_params), _F32), loss=((n,), _F32), best=((n,), _I32), all_params=((n, s, n_params), _F32),
+                     all_loss=((n, s), _F32), grad=((n, s, n_params), _F32), trace=((n, s, n_steps, 2 * n_params + 1), _F32))
+        if hasattr(desc, "n_run"):
+            table["n_run"] = ((n,), _I32)
+        res = _outputs(desc, table, want, out, dev)
+        desc.max_groups = max_groups
+        st = getattr(lib, entry)(desc, torch.cuda.current_stream(dev).cuda_stream)
+    _lib.check(st, entry)
+    return res
+
+
+def _check_schedule(n_steps, lr, angle_lr, momentum, gamma, weight, weight_name: str, who: str):
+    """a fit's n_steps, lr, angle_lr, momentum, gamma and weight, checked in this order"""
+    return (_check_steps(n_steps, who), _check_real(lr, "lr", who), _check_real(angle_lr, "angle_lr", who),
+            _check_real(momentum, "momentum", who), _check_real(gamma, "gamma", who),
+            _check_real(weight, weight_name, who, nonneg=False))
+
+
+def _fit_result(run, starts: torch.Tensor, n_steps: int, return_all: bool, return_trace: bool, extra=()):
+    """what a fit returns, from run(want) -> the dict of the outputs named in want: (params, loss) and, with return_all or
+    return_trace, a dict of the others (best and `extra`; all_params, all_loss; trace, empty for n_steps = 0)"""
+    want = ["params", "loss"]
+    if return_all or return_trace:
+        want += ["best", *extra]
+    if return_all:
+        want += ["all_params", "all_loss"]
+    if return_trace and n_steps > 0:
+        want.append("trace")
+    res = run(tuple(want))
+    if not (return_all or return_trace):
+        return res["params"], res["loss"]
+    if return_trace and n_steps == 0:
+        res["trace"] = torch.empty(*starts.shape[:2], 0, 2 * starts.shape[2] + 1, dtype=torch.float32, device=starts.device)
+    return res["params"], res["loss"], {name: v for name, v in res.items() if name not in ("params", "loss")}
+
+
 def _lf_run(curve: torch.Tensor, k: int, p: int, prototype: torch.Tensor, starts: torch.Tensor, n_steps: int = 0, lr: float = 0.1,
             angle_lr: float = 0.01, gamma: float = 1.0, momentum: float = 0.0, weight: float = 1.0,
             want=("params", "loss", "best", "all_params", "all_loss", "grad"), max_groups: int = 0, out=None):
     """one hint_lensfit_run on checked arguments: a dict of the outputs named in `want` (params [N, 4], loss [N], best [N] int32,
     all_params [N, S, 4], all_loss [N, S], grad [N, S, 4], trace [N, S, n_steps, 9]).  k = 0: curve is [N, P, 2] points.
     out: tensors to write into instead of new ones (the tests' guarded buffers)"""
-    lib = _lib.load()
-    n, dev, s = curve.shape[0], curve.device, starts.shape[1]
-    with torch.cuda.device(dev):
-        desc = _lib.LensFitDesc()
-        _set_curve(desc, curve, n, k, p)
-        desc.a_points, desc.n_template = prototype.data_ptr(), prototype.shape[0]
-        desc.starts, desc.n_starts, desc.n_steps = starts.data_ptr(), s, n_steps
-        desc.lr, desc.angle_lr, desc.gamma, desc.momentum, desc.weight = lr, angle_lr, gamma, momentum, weight
-        res = _outputs(desc, dict(params=((n, 4), _F32), loss=((n,), _F32), best=((n,), _I32), all_params=((n, s, 4), _F32),
-                                  all_loss=((n, s), _F32), grad=((n, s, 4), _F32), trace=((n, s, n_steps, 9), _F32)),
-                       want, out, dev)
-        desc.max_groups = max_groups
-        st = lib.hint_lensfit_run(desc, torch.cuda.current_stream(dev).cuda_stream)
-    _lib.check(st, "hint_lensfit_run")
-    return res
+    fields = dict(a_points=prototype.data_ptr(), n_template=prototype.shape[0], weight=weight)
+    return _fit_run(_lib.LensFitDesc, "hint_lensfit_run", 4, fields, curve, k, p, starts, n_steps, lr, angle_lr, gamma, momentum,
+                    want, max_groups, out)
 
 
 def lens_fit_grad(curve: torch.Tensor, prototype: torch.Tensor, params: torch.Tensor, lens_fit_weight: float = 1.0):
@@ -673,29 +710,16 @@ def fit_lens_shapes(curve: torch.Tensor, prototype: torch.Tensor, *, starts: Opt
     (return_trace).  curve and prototype as in lens_fit_grad.  The loss is the one of the last step before its update, as the
     reference records it; n_steps = 0 evaluates the starts"""
     who = "fit_lens_shapes"
-    n_steps = _check_steps(n_steps, who)
-    lr, angle_lr = _check_real(lr, "lr", who), _check_real(angle_lr, "angle_lr", who)
-    momentum, gamma = _check_real(momentum, "momentum", who), _check_real(gamma, "gamma", who)
-    weight = _check_real(lens_fit_weight, "lens_fit_weight", who, nonneg=False)
+    n_steps, lr, angle_lr, momentum, gamma, weight = _check_schedule(n_steps, lr, angle_lr, momentum, gamma, lens_fit_weight,
+                                                                     "lens_fit_weight", who)
     curve, n, k, p, prototype = _fit_args(curve, prototype, who)
     if starts is None:
         starts = lens_fit_starts(curve)
     else:
         starts = _check_dev_tensor(starts, "starts", who, curve.device)
         _check_starts_shape(tuple(starts.shape), n, who)
-    want = ["params", "loss"]
-    if return_all or return_trace:
-        want.append("best")
-    if return_all:
-        want += ["all_params", "all_loss"]
-    if return_trace and n_steps > 0:
-        want.append("trace")
-    res = _lf_run(curve, k, p, prototype, starts, n_steps, lr, angle_lr, gamma, momentum, weight, want=tuple(want))
-    if not (return_all or return_trace):
-        return res["params"], res["loss"]
-    if return_trace and n_steps == 0:
-        res["trace"] = torch.empty(n, starts.shape[1], 0, 9, dtype=torch.float32, device=curve.device)
-    return res["params"], res["loss"], {name: v for name, v in res.items() if name not in ("params", "loss")}
+    return _fit_result(lambda want: _lf_run(curve, k, p, prototype, starts, n_steps, lr, angle_lr, gamma, momentum, weight, want),
+                       starts, n_steps, return_all, return_trace)
 
 
 # ---- the plus shape's fit: loss, gradient and the SGD loop over up to nine starts in one launch (hint_plusfit.hip) ----
@@ -733,21 +757,9 @@ def _pf_run(curve: torch.Tensor, k: int, p: int, starts: torch.Tensor, n_steps: 
     """one hint_plusfit_run on checked arguments: a dict of the outputs named in `want` (params [N, 9], loss [N], best [N] int32,
     n_run [N] int32, all_params [N, S, 9], all_loss [N, S], grad [N, S, 9], trace [N, S, n_steps, 19]).  k = 0: curve is
     [N, P, 2] points.  out: tensors to write into instead of new ones (the tests' guarded buffers)"""
-    lib = _lib.load()
-    n, dev, s = curve.shape[0], curve.device, starts.shape[1]
-    with torch.cuda.device(dev):
-        desc = _lib.PlusFitDesc()
-        _set_curve(desc, curve, n, k, p)
-        desc.starts, desc.n_starts, desc.n_steps = starts.data_ptr(), s, n_steps
-        desc.lr, desc.angle_lr, desc.gamma, desc.momentum = lr, angle_lr, gamma, momentum
-        desc.corner_weight, desc.stop_loss, desc.corner_decay = corner_weight, stop_loss, 1 if corner_decay else 0
-        res = _outputs(desc, dict(params=((n, 9), _F32), loss=((n,), _F32), best=((n,), _I32), n_run=((n,), _I32),
-                                  all_params=((n, s, 9), _F32), all_loss=((n, s), _F32), grad=((n, s, 9), _F32),
-                                  trace=((n, s, n_steps, 19), _F32)), want, out, dev)
-        desc.max_groups = max_groups
-        st = lib.hint_plusfit_run(desc, torch.cuda.current_stream(dev).cuda_stream)
-    _lib.check(st, "hint_plusfit_run")
-    return res
+    fields = dict(corner_weight=corner_weight, stop_loss=stop_loss, corner_decay=1 if corner_decay else 0)
+    return _fit_run(_lib.PlusFitDesc, "hint_plusfit_run", PLUS_PARAMS, fields, curve, k, p, starts, n_steps, lr, angle_lr, gamma,
+                    momentum, want, max_groups, out)
 
 
 def plus_fit_grad(curve: torch.Tensor, params: torch.Tensor, corner_weight: float = 1.0):
@@ -849,10 +861,8 @@ def fit_plus_shapes(curve: torch.Tensor, *, starts: Optional[torch.Tensor] = Non
     a start that did not run).  curve as in plus_fit_grad.  The loss is the one of the last step before its update, as the
     reference records it; n_steps = 0 evaluates the starts at corner_weight"""
     who = "fit_plus_shapes"
-    n_steps = _check_steps(n_steps, who)
-    lr, angle_lr = _check_real(lr, "lr", who), _check_real(angle_lr, "angle_lr", who)
-    momentum, gamma = _check_real(momentum, "momentum", who), _check_real(gamma, "gamma", who)
-    weight = _check_real(corner_weight, "corner_weight", who, nonneg=False)
+    n_steps, lr, angle_lr, momentum, gamma, weight = _check_schedule(n_steps, lr, angle_lr, momentum, gamma, corner_weight,
+                                                                     "corner_weight", who)
     stop_loss = _check_number(stop_loss, "stop_loss", who)
     if not isinstance(corner_decay, bool):
         raise HintAmdError(f"{who}: corner_decay must be a bool (got {type(corner_decay).__name__})")
@@ -864,19 +874,9 @@ def fit_plus_shapes(curve: torch.Tensor, *, starts: Optional[torch.Tensor] = Non
             raise HintAmdError(f"{who}: both starts and angle are given (the angle only makes the default starts)")
         starts = _check_dev_tensor(starts, "starts", who, curve.device)
         _check_plus_starts_shape(tuple(starts.shape), n, who)
-    want = ["params", "loss"]
-    if return_all or return_trace:
-        want += ["best", "n_run"]
-    if return_all:
-        want += ["all_params", "all_loss"]
-    if return_trace and n_steps > 0:
-        want.append("trace")
-    res = _pf_run(curve, k, p, starts, n_steps, lr, angle_lr, gamma, momentum, weight, corner_decay, stop_loss, want=tuple(want))
-    if not (return_all or return_trace):
-        return res["params"], res["loss"]
-    if return_trace and n_steps == 0:
-        res["trace"] = torch.empty(n, starts.shape[1], 0, 19, dtype=torch.float32, device=curve.device)
-    return res["params"], res["loss"], {name: v for name, v in res.items() if name not in ("params", "loss")}
+    return _fit_result(lambda want: _pf_run(curve, k, p, starts, n_steps, lr, angle_lr, gamma, momentum, weight, corner_decay,
+                                            stop_loss, want),
+                       starts, n_steps, return_all, return_trace, extra=("n_run",))
 
 
 # ---- IoU / DICE of a curve and a fitted shape, and the evaluation loop's four columns (hint_overlap.hip) ----

@@ -186,9 +186,10 @@ def starts64(b):
     return np.array([[c[0], c[1], 2.0, ang], [c[0], c[1], 2.0, (ang + np.pi) % (2 * np.pi)]])
 
 
-def _select(losses):
+def _select(losses, n_run=None):
+    """the first smallest loss, a NaN larger than a number, among the first n_run starts (all of them unless given)"""
     best = 0
-    for s in range(1, len(losses)):
+    for s in range(1, len(losses) if n_run is None else n_run):
         if losses[s] < losses[best] or (np.isnan(losses[best]) and not np.isnan(losses[s])):
             best = s
     return best
@@ -346,17 +347,18 @@ def compare_evaluations(a32, b, dB, w, params, losses, grads):
 def check_update_rule(trace, all_params, lr=LR, angle_lr=ANGLE_LR, momentum=MOMENTUM, gamma=GAMMA):
     """the update rule on a traced fit of one start, every step: p_(i+1) - recorded as the next step's parameters, the last one
     as all_params - against fma(-lr_i, buf_i, p_i) with buf rebuilt from the traced gradients: the largest error in units of
-    one fp32 ulp of the larger magnitude"""
+    one fp32 ulp of the larger magnitude.  A record is p, L, g: the number of parameters is read from its width, and the last
+    one is the angle"""
     trace = np.asarray(trace, np.float32).astype(np.float64)
-    n = len(trace)
-    nxt = np.concatenate([trace[1:, :4], np.asarray(all_params, np.float32).astype(np.float64)[None]])
-    rates = np.array([lr, lr, lr, angle_lr], np.float64)
+    n, npar = len(trace), (trace.shape[1] - 1) // 2
+    nxt = np.concatenate([trace[1:, :npar], np.asarray(all_params, np.float32).astype(np.float64)[None]])
+    rates = np.array([lr] * (npar - 1) + [angle_lr], np.float64)
     mom = float(np.float32(momentum))
     buf, worst = None, 0.0
     for i in range(n):
-        g = trace[i, 5:]
+        g = trace[i, npar + 1:]
         buf = g.copy() if i == 0 else _fma(mom, buf, g)
-        want = _fma(-_f32(rates), buf, trace[i, :4])
+        want = _fma(-_f32(rates), buf, trace[i, :npar])
         big = np.maximum(np.abs(want), np.abs(nxt[i]))
         ulp = np.spacing(big.astype(np.float32)).astype(np.float64)
         err = np.abs(nxt[i] - want) / ulp

@@ -43,6 +43,7 @@ import curve_oracle as co
 import lensfit_oracle as lfo
 import plus_oracle as po
 from curve_oracle import _f32, _fma
+from lensfit_oracle import _select  # noqa: F401  (the tests' too)
 
 U = 2.0 ** -24
 LR, ANGLE_LR, MOMENTUM, GAMMA, N_STEPS, STOP = 0.1, 0.01, 0.2, 0.1 ** (1 / 400), 400, 0.005
@@ -258,14 +259,6 @@ def angle64(b, tol=1e-5):
     return (float(np.arctan(sxy / sxx)) if sxx > 0 else 0.0), decided
 
 
-def _select(losses, n_run):
-    best = 0
-    for s in range(1, n_run):
-        if losses[s] < losses[best] or (np.isnan(losses[best]) and not np.isnan(losses[s])):
-            best = s
-    return best
-
-
 def corner_weight(c, i, n_steps, decay=True, wrong=None):
     if not decay or n_steps == 0 or wrong == "corner weight constant":
         return c
@@ -405,25 +398,8 @@ def compare_evaluations(b, dB, c, params, losses, grads):
 
 
 def check_update_rule(trace, all_params, lr=LR, angle_lr=ANGLE_LR, momentum=MOMENTUM, gamma=GAMMA):
-    """the update rule on a traced fit of one start, every step: p_(i+1) - recorded as the next step's parameters, the last one
-    as all_params - against fma(-lr_i, buf_i, p_i) with buf rebuilt from the traced gradients: the largest error in units of
-    one fp32 ulp of the larger magnitude"""
-    trace = np.asarray(trace, np.float32).astype(np.float64)
-    n = len(trace)
-    nxt = np.concatenate([trace[1:, :9], np.asarray(all_params, np.float32).astype(np.float64)[None]])
-    rates = np.array([lr] * 8 + [angle_lr], np.float64)
-    mom = float(np.float32(momentum))
-    buf, worst = None, 0.0
-    for i in range(n):
-        g = trace[i, 10:]
-        buf = g.copy() if i == 0 else _fma(mom, buf, g)
-        want = _fma(-_f32(rates), buf, trace[i, :9])
-        big = np.maximum(np.abs(want), np.abs(nxt[i]))
-        ulp = np.spacing(big.astype(np.float32)).astype(np.float64)
-        err = np.abs(nxt[i] - want) / ulp
-        worst = max(worst, float(np.where(np.isfinite(err), err, np.inf).max()))
-        rates = rates * gamma
-    return worst
+    """lensfit_oracle's, which reads the nine parameters from the trace's width, at this fit's schedule"""
+    return lfo.check_update_rule(trace, all_params, lr, angle_lr, momentum, gamma)
 
 
 # the rows of the evaluation tests: (name, source, P, N, S, corner weight, rows of zero width, rows with active clamps).  At P =

@@ -1,7 +1,7 @@
-"""The cases of tests/golden/pointset_bits.npz: small launches of hint_hausdorff_run, hint_plus_run and hint_lensfit_run whose
-output bits were recorded once (tests/golden/make_pointset_bits.py) and must never move again (tests/test_gpu_pointset_bits.py).
-Every operation of the three kernels is a correctly rounded intrinsic in an order that include/hint_amd.h fixes, so a change that
-only moves code changes no bit.
+"""The cases of tests/golden/pointset_bits.npz and tests/golden/plusfit_bits.npz: small launches of hint_hausdorff_run,
+hint_plus_run, hint_lensfit_run and hint_plusfit_run whose output bits were recorded once (tests/golden/make_pointset_bits.py) and
+must never move again (tests/test_gpu_pointset_bits.py).  Every operation of the four kernels is a correctly rounded intrinsic in
+an order that include/hint_amd.h fixes, so a change that only moves code changes no bit.
 
 Every case has 5 rows on 2 workgroups: a workgroup takes 2-3 rows in turn and reuses its LDS between them.  The inputs come from
 the oracles' seeded generators; the fixture keeps a sha256 of each, so that a drift of a generator is reported as such and not as
@@ -12,7 +12,10 @@ edges come in pairs of equal count, so its size is always even: 1025 does not ex
 row may have, next to a row that is past it.  Lens fit (K, P, M, S starts, n_steps, weight): every K of 0 (given points), 1, 5, 25;
 every number 1..4 of points a thread holds of the curve (P = 2, 100 / 257 / 600 / 1024) and of the prototype (M = 1, 130 / 300 /
 700 / 1023, 1024); 1, 2 and 16 starts; the evaluation alone (n_steps 0, no trace), one step and five; both weights; all outputs,
-and params and loss alone."""
+and params and loss alone.  Plus fit (K, P, S starts, n_steps, corner weight, its decay, stop_loss): every K of 0, 1, 5, 25; every
+number 1..4 of curve points a thread holds (P = 2, 100 / 257 / 600 / 1024); 1, 2, 3 and 16 starts; the evaluation alone, one step
+and five; a row of zero width (ten kept segments) and a clamped row under the pinned steps; the decaying corner weight; an early
+stop after one, two and three starts, with the starts that did not run; all outputs, and params and loss alone."""
 import hashlib
 
 import numpy as np
@@ -21,6 +24,7 @@ import curve_oracle as co
 import hausdorff_oracle as ho
 import lensfit_oracle as lo
 import plus_oracle as po
+import plusfit_oracle as pfo
 
 ROWS, GROUPS = 5, 2
 RAGGED = (1, 1023, 1024, 1025, 4096)
@@ -55,6 +59,19 @@ LENSFIT = {
     "lf_k5_p600_m300_s1_n1_w025": (25, 5, 600, 300, 1, 1, 0.25, "gauss", LENSFIT_ALL),
     "lf_k5_p100_m700_s2_n5_params_loss_alone": (26, 5, 100, 700, 2, 5, 1.0, "lens", ("params", "loss")),
 }
+PLUSFIT_ALL = ("params", "loss", "best", "n_run", "all_params", "all_loss", "grad", "trace")
+# name -> (seed, K (0: given points), P, starts, n_steps, corner_weight, corner_decay, stop_loss, outputs)
+PLUSFIT = {
+    "pf_k1_p2_s1_eval": (431, 1, 2, 1, 0, 1.0, False, 0.0, PLUSFIT_ALL[:-1]),           # (n_steps 0 has no trace)
+    "pf_k5_p100_s2_n5_decay": (441, 5, 100, 2, 5, 1.0, True, 0.0, PLUSFIT_ALL),
+    "pf_k25_p257_s3_n1_stop": (432, 25, 257, 3, 1, 1.0, False, 0.1, PLUSFIT_ALL),
+    "pf_given_p1024_s16_n1_w037": (451, 0, 1024, 16, 1, 0.37, False, 0.0, PLUSFIT_ALL),
+    "pf_k5_p600_s2_n5_params_loss_alone": (461, 5, 600, 2, 5, 1.0, True, 0.0, ("params", "loss")),
+}
+# what a case's rows hold beside plusfit_oracle.eval_params' draw: rows of zero width and clamped rows, and (row, start, the move
+# of xoffset) that puts a start's loss far above the stop case's stop_loss
+PLUSFIT_ROWS = {"pf_k5_p100_s2_n5_decay": dict(zero_width=(1,), clamped=(3,))}
+PLUSFIT_MOVES = {"pf_k25_p257_s3_n1_stop": ((0, 0, 0.6), (2, 0, 0.6), (2, 1, 0.6))}
 HASHED = ("points", "segments")          # outputs the fixture keeps as a sha256
 
 
@@ -83,6 +100,13 @@ def inputs(name):
         return dict(curve=x if K else co.points64(x, P).astype(np.float32),
                     prototype=lo.lens_prototype(M) if M > 1 else np.array([[0.75, -0.5]], np.float32),
                     starts=lo.golden_grad_params(seed, ROWS * S).reshape(ROWS, S, 4))
+    if name in PLUSFIT:
+        seed, K, P, S = PLUSFIT[name][:4]
+        x, base = pfo.plus_rows(seed, ROWS, K or 5)
+        starts = np.stack([pfo.eval_params(base, seed + 1 + s, **PLUSFIT_ROWS.get(name, {})) for s in range(S)], 1)
+        for r, s, move in PLUSFIT_MOVES.get(name, ()):
+            starts[r, s, 6] += np.float32(move)
+        return dict(curve=x if K else co.points64(x, P).astype(np.float32), starts=starts)
     seed, K, P, size, zero, over, _ = PLUS[name]
     pr = po.draw_params(200 + seed, ROWS, (), zero=zero)
     if over is not None:
@@ -104,6 +128,29 @@ def check_plus_rows(name, inp):
         assert (ref["counts"][r] == 0).sum() == 2 * len(cols), (name, r, ref["counts"][r])
 
 
+def check_plusfit_rows(name, inp):
+    """the CPU conditions of a plus-fit case: with every start run in float64 no loss lies within a factor 1.5 of stop_loss, the
+    float32 emulation and float64 agree on the starts that run, every emulated word of a start that runs is finite, and the stop
+    case ends its rows after one, two and three starts.  Returns n_run [ROWS]"""
+    _, K, P, S, n_steps, cw, decay, stop, _ = PLUSFIT[name]
+    kw = dict(n_steps=n_steps, c=cw, decay=decay)
+    n_run = []
+    for r in range(ROWS):
+        b32 = (co.points64(inp["curve"][r:r + 1], P)[0] if K else inp["curve"][r]).astype(np.float32).astype(np.float64)
+        losses = pfo.fit64(b32, inp["starts"][r], stop_loss=0.0, **kw)["all_loss"]
+        assert np.isfinite(losses).all() and not ((losses > stop / 1.5) & (losses < stop * 1.5)).any(), (name, r, losses)
+        f64, f32 = pfo.fit64(b32, inp["starts"][r], stop_loss=stop, **kw), pfo.emulate32(b32, inp["starts"][r], stop_loss=stop, **kw)
+        assert f64["n_run"] == f32["n_run"] and f64["best"] == f32["best"], (name, r, f64["n_run"], f32["n_run"])
+        k = f32["n_run"]
+        assert all(np.isfinite(f32[o][:k]).all() for o in ("all_params", "all_loss", "grad", "trace")), (name, r)
+        n_run.append(k)
+    if stop > 0:
+        assert set(n_run) == {1, 2, 3}, (name, n_run)
+    if name in PLUSFIT_ROWS:
+        assert (inp["starts"][list(PLUSFIT_ROWS[name]["zero_width"]), :, 2] == 0).all()
+    return np.array(n_run)
+
+
 def run(name, inp):
     """the case on the device: a dict of its outputs as numpy arrays"""
     import torch
@@ -119,6 +166,10 @@ def run(name, inp):
         _, K, P, _, _, n_steps, w, _, want = LENSFIT[name]
         out = curves._lf_run(dev(inp["curve"]), K, P, dev(inp["prototype"]), dev(inp["starts"]), n_steps, lo.LR, lo.ANGLE_LR,
                              lo.GAMMA, lo.MOMENTUM, w, want, GROUPS)
+    elif name in PLUSFIT:
+        _, K, P, _, n_steps, cw, decay, stop, want = PLUSFIT[name]
+        out = curves._pf_run(dev(inp["curve"]), K, P, dev(inp["starts"]), n_steps, pfo.LR, pfo.ANGLE_LR, pfo.GAMMA, pfo.MOMENTUM, cw,
+                             decay, stop, want, GROUPS)
     else:
         _, K, P, _, _, _, want = PLUS[name]
         out = curves._plus_run(dev(inp["params"]), dev(inp["curve"]), K, P, float(inp["max_dist"]), want, GROUPS)

@@ -96,6 +96,12 @@ def test_symbols_declared_exported_and_bound_abi_still_8():
     for src in ("hint_plus.hip", "hint_plusfit.hip"):
         text = open(os.path.join(ROOT, "hint_amd", "csrc", src)).read()
         assert '#include "hint_plusgeom.hpp"' in text and "PL_VX =" not in text and "pl_segment(rw" in text, src
+    # both fits take the driver - the state, the trace record, the update rule, the selection - from the one header
+    assert "hint_fit.hpp" in re.search(r"^HDRS\s*:=(.*)$", makefile, re.M).group(1)
+    assert "__fmaf_rn(momentum" in open(os.path.join(ROOT, "hint_amd", "csrc", "hint_fit.hpp")).read()
+    for src in ("hint_lensfit.hip", "hint_plusfit.hip"):
+        text = open(os.path.join(ROOT, "hint_amd", "csrc", src)).read()
+        assert '#include "hint_fit.hpp"' in text and "__fmaf_rn(momentum" not in text and "fit_step(st" in text, src
 
 
 def test_run_rejects_bad_arguments_before_any_device_call():

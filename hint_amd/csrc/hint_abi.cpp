@@ -91,6 +91,10 @@ int64_t tape_act_off(const hint_plan* P, int B) {
 }
 int64_t act_stride(const hint_plan* P, int B) { return (int64_t)rows_padded(B) * P->WT + WS_SLACK; }
 int64_t bits_stride(const hint_plan* P, int B) { return (int64_t)rows_padded(B) / ROWS * (P->WT / 16) * 64; }   // bytes
+// [Bp x WT + slack] arrays in front of the tape's sign bytes (a1, a2) and of the workspace's g_st (g1, g2): lean plans keep no a1 / g2
+static int act_arrays(const hint_plan* P) { return P->lean ? 1 : 2; }
+static int64_t tape_a2_off(const hint_plan* P, int B) { return (act_arrays(P) - 1) * act_stride(P, B); }      // floats from ChainBlock::actA1
+static int64_t tape_bits_off(const hint_plan* P, int B) { return act_arrays(P) * act_stride(P, B); }          // .. of a1's sign bytes; a2's follow bits_stride bytes later
 
 // batch split of part B: a multiple of 8 splits (one XCD each), enough workgroups to cover the chip,
 // every workgroup reducing at least 128 rows
@@ -109,7 +113,7 @@ void wgrad_splits(const hint_plan* P, int B, int n_chain, int* splits_out, int* 
 }
 
 // Workspace layout (floats): [g1: Bp x WT + slack][g2: same][g_st: Bp x ST + slack, padded to 4][slabs: splits x param_floats]
-int64_t ws_gst_off(const hint_plan* P, int B) { return (P->lean ? 1 : 2) * act_stride(P, B); }      // (lean plans: no g2 array)
+int64_t ws_gst_off(const hint_plan* P, int B) { return act_arrays(P) * act_stride(P, B); }
 int64_t ws_slab_off(const hint_plan* P, int B) {
     return ws_gst_off(P, B) + ((int64_t)rows_padded(B) * P->ST + WS_SLACK + 3) / 4 * 4;
 }
@@ -133,9 +137,6 @@ bool l2_prefetch_on() {
     }
     return v != 0;
 }
-static int perm_lds_cap() { return PERM_LDS_MAX; }
-static bool plan_dump() { return knobs().plan_dump; }
-static bool no_bwd_fly() { return knobs().no_bwd_fly; }
 
 // the 256-byte sink of the general kernels' L2 warm-up (hint_device.hpp prefetch_consumer) behind everything else of the launch
 static int add_sink(const hint_plan* P, int total, KArgs* a) {
@@ -148,13 +149,14 @@ static int add_sink(const hint_plan* P, int total, KArgs* a) {
 }
 
 // LDS bytes of the launch: the plan's, plus the chain's permutation matrices when they fit behind it
-int lds_with_perms(const hint_plan* P, int lds_plan, int n_blocks, bool any_perm, KArgs* a, bool backward) {
+// (backward: which slot of hint_debug_last_lds_bytes the launch's size goes to)
+static int lds_with_perms(const hint_plan* P, int lds_plan, int n_blocks, bool any_perm, KArgs* a, bool backward) {
     const long extra = (long)n_blocks * P->d * P->d * (long)sizeof(float);
     a->perm_lds = 0;
-    const int cap = perm_lds_cap();
-    if (plan_dump()) fprintf(stderr, "[hint plan] lds %d + perms %ld (cap %d)\n", lds_plan, extra, cap);
+    const bool dump = knobs().plan_dump;
+    if (dump) fprintf(stderr, "[hint plan] lds %d + perms %ld (cap %d)\n", lds_plan, extra, PERM_LDS_MAX);
     int total = lds_plan;
-    if (any_perm && extra <= cap && lds_plan + extra <= LDS_LIMIT) {
+    if (any_perm && extra <= PERM_LDS_MAX && lds_plan + extra <= LDS_LIMIT) {
         a->perm_lds = lds_plan / (int)sizeof(float);
         total += (int)extra;
     }
@@ -165,11 +167,11 @@ int lds_with_perms(const hint_plan* P, int lds_plan, int n_blocks, bool any_perm
     // issuing wavefront's own loads wait for it (+14 / +9 us); as straight-line code - a `buffer_load ... lds` every wavefront
     // always issues, with an out-of-bound offset for the lanes that are not to touch anything - +2 / +6 us
     total = add_sink(P, total, a);
-    if (plan_dump()) fprintf(stderr, "[hint plan] packed lines %d: sink at %d, lds %d\n", a->packed_lines, a->sink_lds, total);
+    if (dump) fprintf(stderr, "[hint plan] packed lines %d: sink at %d, lds %d\n", a->packed_lines, a->sink_lds, total);
     g_last_lds[backward ? 1 : 0].store(total, std::memory_order_relaxed);
     return total;
 }
-KArgs make_args(const hint_plan* P, int B, bool backward) {
+static KArgs make_args(const hint_plan* P, int B, bool backward) {
     KArgs a{};
     a.meta = P->d_meta; a.meta_bytes = P->meta_bytes; a.recs = P->d_recs; a.total_rows = P->total_rows; a.thins = P->d_thins; a.total_tiles = P->total_tiles;
     a.units_off = P->units_off; a.tmap_off = P->tmap_off; a.ents_off = P->ents_off; a.rng_off = P->rng_off;
@@ -185,7 +187,7 @@ KArgs make_args(const hint_plan* P, int B, bool backward) {
     a.thin_grp = backward ? P->thin_grp_b : P->thin_grp_f;
     a.act_stride = act_stride(P, B); a.bits_stride = bits_stride(P, B);
     a.fuse_dw1 = P->fuse_dw1; a.tw_floats = P->tw_floats; a.thin_slab_off = ws_thin_off(P, B);
-    a.lean = P->lean; a.a2_off = P->lean ? 0 : a.act_stride; a.bits_off = (P->lean ? 1 : 2) * a.act_stride;
+    a.lean = P->lean; a.a2_off = tape_a2_off(P, B); a.bits_off = tape_bits_off(P, B);
     a.alpha = P->alpha; a.B = B; a.stamps = g_stamp_buf;
     a.rowdw_lds = backward ? P->rowdw_lds : 0;
     a.n_sub = P->n_sub;
@@ -228,7 +230,7 @@ Dispatch dispatch(const hint_plan* P, int B, int n_chain) {
     D.grid = grid_for(P, B);
     D.passes = D.grid > 0 ? (D.groups + D.grid - 1) / D.grid : 0;
     D.fwd = P->wl ? FWD_WL : P->has_fly ? FWD_FLY : FWD_GEN;
-    D.bwd = P->wl ? BWD_WL : P->has_fly && !no_bwd_fly() ? BWD_FLY : P->row_ntt <= 3 && P->rowdw_lds == 0 ? BWD_N3 : BWD_GEN;
+    D.bwd = P->wl ? BWD_WL : P->has_fly && !knobs().no_bwd_fly ? BWD_FLY : P->row_ntt <= 3 && P->rowdw_lds == 0 ? BWD_N3 : BWD_GEN;
     D.dw_small = P->n_wsmall > 0;
     D.dw_wide = P->has_leanw != 0;
     if (B > 0) wgrad_splits(P, B, n_chain, &D.dw_splits, &D.dw_rows);
@@ -256,76 +258,73 @@ int paths_out(const hint_plan* P, int B, int32_t* out, int32_t n_out) {
     return 0;
 }
 
+// What a row kernel is launched with, forward / inverse or backward part A: the kernel arguments, the LDS size with the chain's
+// permutation matrices behind the plan's when they fit, and the wave-local kernels' offsets with the place of those matrices.
+// (The general backward kernels leave the matrices in global memory: one d x d product per block.  Their L2 warm-up has its sink like
+//  the forward's - round 5: until then KArgs::sink_lds was 0 there and the block in hint_bwd.hip dead code.)
+static RowLaunch row_launch(const Dispatch& D, int B, bool backward, const BlockSet& bs) {
+    const hint_plan* P = D.P;
+    RowLaunch L{make_args(P, B, backward), WlArgs{}, 0, D.grid};
+    const bool perms_in_lds = any_perm(bs) && (P->wl || !backward);
+    L.lds = lds_with_perms(P, plan_lds(P, backward, D.nr), bs.n_chain, perms_in_lds, &L.a, backward);
+    if (P->wl) {
+        L.w = (backward ? P->wl_b : P->wl_f)[D.nr - 1];
+        L.w.off_perm = L.a.perm_lds;
+    }
+    return L;
+}
+
+int launch_rows_fwd(const hint_plan* P, int B, bool rev, const BlockSet& bs, const FwdIO& io, hipStream_t s) {
+    const Dispatch D = dispatch(P, B);
+    const RowLaunch L = row_launch(D, B, false, bs);
+    if (D.fwd == FWD_WL) HIP_TRY(launch_wl_apply(rev, L, bs, io, s));
+    else HIP_TRY(launch_apply(rev, D.fwd == FWD_FLY, L, bs, io, s));
+    return 0;
+}
+
+// part B's launch: the job list, the batch split, and where its kernels find the activations and their sign bytes
+static WgradLaunch wgrad_launch(const Dispatch& D, int B) {
+    const hint_plan* P = D.P;
+    return {.jobs = P->d_wjobs, .n_jobs = P->n_ljobs, .n_small = P->n_lsmall, .n_rowj = P->n_rowj, .interleave = P->wsorted != 0,
+            .splits = D.dw_splits, .rows_per_wg = D.dw_rows,     // (the whole chain's count: a bucketed launch sums in the same order)
+            .WT = P->WT, .ST = P->ST, .d = P->d, .dc = P->dc, .n_levels = P->n_levels, .B = B, .Bp = rows_padded(B),
+            .act_stride = act_stride(P, B), .a2_off = tape_a2_off(P, B), .bits_a2_off = tape_bits_off(P, B) * 4 + bits_stride(P, B),
+            .param_floats = P->param_floats, .real = P->d_real, .twmap = P->fuse_dw1 ? P->d_twmap : nullptr, .tw_floats = P->tw_floats,
+            .thin_slab_off = ws_thin_off(P, B), .thin_slabs = D.grid, .num_cu = P->num_cu, .small = D.dw_small, .wide = D.dw_wide};
+}
+
+static BwdLaunch* const BWD_LAUNCH[] = {launch_wl_bwd, launch_bwd, launch_bwd_n3, launch_bwd_fly};      // [Dispatch::bwd]
+
 // part A (row-parallel, bit 0 of `parts`) and part B (weight gradients, bit 1) of the backward pass of
 // one block or a chain
-int run_backward(const hint_plan* P, const ChainBlock& one, const ChainBlock* chain, const ChainBlock* chain_host, int n_chain,
-                 int cb0, int n_total, const float* x, const float* c, const float* g_z, const float* g_J, float* g_x, float* g_c,
-                 float gz_scale, float gJ_const, int B, int accumulate, int parts, hipStream_t s, const AdamFuse* adam) {
+int run_backward(const hint_plan* P, const BlockSet& bs, const BwdIO& io, int B, int accumulate, int parts, hipStream_t s,
+                 const AdamFuse* adam) {
 #ifdef HINT_ABLATE_STORE
     // (a diagnostic build whose row kernels keep no activations cannot train: only with HINT_ABLATION_OK=1 in the environment -
     //  the timing scripts set it - does it launch a backward pass at all)
     if (!knobs().ablation_ok) return fail("this is an ablation build (HINT_ABLATE_STORE): its gradients are wrong; set HINT_ABLATION_OK=1 for timing runs");
 #endif
 
-    const Dispatch D = dispatch(P, B, n_total);
-    P = D.P;
-    if ((parts & 1) && D.bwd == BWD_WL) {
-        KArgs a = make_args(P, B, true);
-        const int nr = D.nr;
-        WlArgs w = P->wl_b[nr - 1];
-        bool any_perm = one.perm != nullptr;
-        if (chain_host) for (int i = 0; i < n_chain; ++i) any_perm = any_perm || chain_host[i].perm != nullptr;
-        const int lds = lds_with_perms(P, plan_lds(P, true, nr), n_chain, any_perm, &a, true);
-        w.off_perm = a.perm_lds;
-        HIP_TRY(launch_wl_bwd(a, w, lds, D.grid, one, chain, n_chain, x, g_z, g_J, g_x, gz_scale, gJ_const, s));
-    } else if (parts & 1) {
-        // (the permutation matrices stay in global memory here: one d x d product per block)
-        // (round 5: the backward's L2 warm-up gets its sink too - until then KArgs::sink_lds was 0 here and the block in hint_bwd.hip dead code)
-        KArgs a = make_args(P, B, true);
-        const int lds = add_sink(P, P->lds_bwd, &a);
-        g_last_lds[1].store(lds, std::memory_order_relaxed);
-        HIP_TRY((D.bwd == BWD_FLY ? launch_bwd_fly : D.bwd == BWD_N3 ? launch_bwd_n3 : launch_bwd)(a, lds, D.grid, one, chain, n_chain, x, c,
-                                                               g_z, g_J, g_x, g_c, gz_scale, gJ_const, s));
-    }
-    if (!(parts & 2)) return 0;
-    const int splits = D.dw_splits, rows_per_wg = D.dw_rows;   // (the whole chain's count: a bucketed launch sums in the same order)
-    HIP_TRY(launch_wgrad(P->d_wjobs, P->n_ljobs, P->wsorted ? -P->n_lsmall - 1 : P->n_lsmall, P->n_rowj, splits, one, chain, n_chain, cb0, P->WT, P->ST, P->d, P->dc, P->n_levels, B,
-                         rows_padded(B), rows_per_wg, act_stride(P, B), P->lean ? 0 : act_stride(P, B),
-                         (P->lean ? 1 : 2) * act_stride(P, B) * 4 + bits_stride(P, B), P->param_floats, x, c, P->d_real,
-                         accumulate, P->fuse_dw1 ? P->d_twmap : nullptr, P->tw_floats, ws_thin_off(P, B), D.grid,
-                         P->num_cu, adam, D.dw_small, D.dw_wide, s));
+    const Dispatch D = dispatch(P, B, bs.n_total);
+    if (parts & 1) HIP_TRY(BWD_LAUNCH[D.bwd](row_launch(D, B, true, bs), bs, io, s));
+    if (parts & 2) HIP_TRY(launch_wgrad(wgrad_launch(D, B), bs, io.x, io.c, accumulate, adam, s));
     return 0;
 }
 
 }  // namespace hint
 
-static int apply(const hint_plan* P, bool rev, const float* params, const float* packed, const float* x,
-                 const float* c, float* z, float* J, float* tape, const float* perm, const float* J_in,
-                 float* loss_acc, int32_t B, void* stream, float noise = 0.f, const uint64_t* rng_state = nullptr,
-                 float* x_noisy = nullptr) {
+static int apply(const hint_plan* P, bool rev, const float* params, const float* packed, float* tape, const float* perm,
+                 const FwdIO& io, int32_t B, void* stream) {
     const char* what = rev ? "inverse" : "forward";
-    if (!P || !params || !packed || !x || !z || !J) return fail("hint_block_%s: null argument", what);
-    if (P->dc > 0 && !c) return fail("hint_block_%s: plan has dc=%d but c is NULL", what, P->dc);
+    if (!P || !params || !packed || !io.x || !io.z || !io.J) return fail("hint_block_%s: null argument", what);
+    if (P->dc > 0 && !io.c) return fail("hint_block_%s: plan has dc=%d but c is NULL", what, P->dc);
     if (B < 0) return fail("negative batch");
     if (B == 0) return 0;
-    const Dispatch D = dispatch(P, B);
-    P = D.P;
+    P = variant(P, B);
     ChainBlock one{};
     one.params = params; one.packed = packed; one.perm = perm;
     bind_tape(P, B, rev ? nullptr : tape, &one);
-    KArgs a = make_args(P, B, false);
-    const int nr = D.nr;
-    const int lds = lds_with_perms(P, plan_lds(P, false, nr), 1, perm != nullptr, &a);
-    if (D.fwd == FWD_WL) {
-        WlArgs w = P->wl_f[nr - 1];
-        w.off_perm = a.perm_lds;
-        HIP_TRY(launch_wl_apply(rev, a, w, lds, D.grid, one, nullptr, 1, x, z, J, J_in, loss_acc, noise,
-                                (const unsigned long long*)rng_state, x_noisy, (hipStream_t)stream));
-        return 0;
-    }
-    HIP_TRY(launch_apply(rev, D.fwd == FWD_FLY, a, lds, D.grid, one, nullptr, 1, x, c, z, J, J_in, loss_acc, noise,
-                         (const unsigned long long*)rng_state, x_noisy, (hipStream_t)stream));
-    return 0;
+    return launch_rows_fwd(P, B, rev, {.one = &one}, io, (hipStream_t)stream);
 }
 
 extern "C" {
@@ -368,11 +367,10 @@ int64_t hint_plan_param_floats(const hint_plan* P) { return P ? P->param_floats 
 // + PACK_SLACK floats of zeros behind the bias region (a padded row's dummy steps load up to three tiles past its last)
 int64_t hint_plan_packed_floats(const hint_plan* P) { return P ? P->packed_floats + P->n_bias + PACK_SLACK : -1; }
 
-static inline int rows_padded(int B) { return (B + ROWS - 1) / ROWS * ROWS; }
 int64_t hint_plan_tape_floats(const hint_plan* P, int32_t B) {
     if (!P || B < 0) return -1;
     P = variant(P, B);
-    return tape_act_off(P, B) + (P->lean ? 1 : 2) * act_stride(P, B) + 2 * bits_stride(P, B) / 4;
+    return tape_act_off(P, B) + tape_bits_off(P, B) + 2 * bits_stride(P, B) / 4;
 }
 
 size_t hint_plan_workspace_bytes(const hint_plan* P, int32_t B) {
@@ -483,13 +481,13 @@ void hint_pack_group_destroy(hint_pack_group* G) {
 
 int hint_block_forward(const hint_plan* P, const float* params, const float* packed, const float* x,
                        const float* c, float* z, float* J, float* tape, int32_t B, void* stream) {
-    return apply(P, false, params, packed, x, c, z, J, tape, nullptr, nullptr, nullptr, B, stream);
+    return apply(P, false, params, packed, tape, nullptr, {.x = x, .c = c, .z = z, .J = J}, B, stream);
 }
 
 int hint_block_forward_ex(const hint_plan* P, const float* params, const float* packed, const float* x,
                           const float* c, float* z, float* J, float* tape, const float* perm,
                           const float* J_in, float* loss_acc, int32_t B, void* stream) {
-    return apply(P, false, params, packed, x, c, z, J, tape, perm, J_in, loss_acc, B, stream);
+    return apply(P, false, params, packed, tape, perm, {.x = x, .c = c, .z = z, .J = J, .J_in = J_in, .loss_acc = loss_acc}, B, stream);
 }
 
 int hint_block_forward_noisy(const hint_plan* P, const float* params, const float* packed, const float* x,
@@ -498,19 +496,20 @@ int hint_block_forward_noisy(const hint_plan* P, const float* params, const floa
                              float* x_noisy, int32_t B, void* stream) {
     if (noise != 0.f && (!rng_state || !x_noisy)) return fail("hint_block_forward_noisy: noise needs rng_state and x_noisy");
     if (noise != 0.f && perm) return fail("hint_block_forward_noisy: the noise is added to the block's input, in front of no permutation");
-    return apply(P, false, params, packed, x, c, z, J, tape, perm, J_in, loss_acc, B, stream, noise, noise != 0.f ? rng_state : nullptr,
-                 noise != 0.f ? x_noisy : nullptr);
+    FwdIO io{.x = x, .c = c, .z = z, .J = J, .J_in = J_in, .loss_acc = loss_acc};
+    if (noise != 0.f) { io.noise = noise; io.rng_state = (const unsigned long long*)rng_state; io.x_noisy = x_noisy; }
+    return apply(P, false, params, packed, tape, perm, io, B, stream);
 }
 
 int hint_block_inverse(const hint_plan* P, const float* params, const float* packed, const float* z,
                        const float* c, float* x, float* J, int32_t B, void* stream) {
-    return apply(P, true, params, packed, z, c, x, J, nullptr, nullptr, nullptr, nullptr, B, stream);
+    return apply(P, true, params, packed, nullptr, nullptr, {.x = z, .c = c, .z = x, .J = J}, B, stream);
 }
 
 int hint_block_inverse_ex(const hint_plan* P, const float* params, const float* packed, const float* z,
                           const float* c, float* x, float* J, const float* perm, const float* J_in,
                           int32_t B, void* stream) {
-    return apply(P, true, params, packed, z, c, x, J, nullptr, perm, J_in, nullptr, B, stream);
+    return apply(P, true, params, packed, nullptr, perm, {.x = z, .c = c, .z = x, .J = J, .J_in = J_in}, B, stream);
 }
 
 int hint_block_backward(const hint_plan* P, const float* params, const float* packed, const float* x,
@@ -525,14 +524,12 @@ int hint_block_backward(const hint_plan* P, const float* params, const float* pa
 
 namespace hint {
 // parts: bit 0 the row-parallel kernel, bit 1 the weight gradients (run_backward)
-int block_backward(const hint_plan* P, const float* params, const float* packed, const float* x,
-                          const float* tape, const float* c, const float* g_z, const float* g_J, float* g_x,
-                          float* g_c, float* g_params, int32_t accumulate, void* workspace,
-                          size_t workspace_bytes, const float* perm, float gz_scale, float gJ_const,
-                          int32_t B, int parts, void* stream) {
-    if (!P || !params || !packed || (!x && !perm) || !g_x || (!g_params && (parts & 2))) return fail("hint_block_backward: null argument");
+int block_backward(const hint_plan* P, const float* params, const float* packed, const float* tape, float* g_params,
+                   int32_t accumulate, void* workspace, size_t workspace_bytes, const float* perm, const BwdIO& io, int32_t B,
+                   int parts, void* stream) {
+    if (!P || !params || !packed || (!io.x && !perm) || !io.g_x || (!g_params && (parts & 2))) return fail("hint_block_backward: null argument");
     if (perm && !tape) return fail("hint_block_backward_ex: a fused permutation needs the tape of hint_block_forward_ex");
-    if (P->dc > 0 && !c) return fail("hint_block_backward: plan has dc=%d but c is NULL", P->dc);
+    if (P->dc > 0 && !io.c) return fail("hint_block_backward: plan has dc=%d but c is NULL", P->dc);
     if (!tape && B > 0) return fail("hint_block_backward: tape is NULL (the backward pass reads the forward's lane tiles, s values and activations from it)");
     if (B < 0) return fail("negative batch");
     hipStream_t s = (hipStream_t)stream;
@@ -551,7 +548,7 @@ int block_backward(const hint_plan* P, const float* params, const float* packed,
     bind_tape(P, B, const_cast<float*>(tape), &one);
     one.gparams = g_params;
     split_workspace(P, B, workspace, &one);
-    return run_backward(P, one, nullptr, nullptr, 1, 0, 1, x, c, g_z, g_J, g_x, g_c, gz_scale, gJ_const, B, accumulate ? 1 : 0, parts, s);
+    return run_backward(P, {.one = &one}, io, B, accumulate ? 1 : 0, parts, s);
 }
 }  // namespace hint
 
@@ -562,8 +559,8 @@ int hint_block_backward_ex(const hint_plan* P, const float* params, const float*
                            float* g_c, float* g_params, int32_t accumulate, void* workspace,
                            size_t workspace_bytes, const float* perm, float gz_scale, float gJ_const,
                            int32_t B, void* stream) {
-    return block_backward(P, params, packed, x, tape, c, g_z, g_J, g_x, g_c, g_params, accumulate, workspace, workspace_bytes,
-                          perm, gz_scale, gJ_const, B, 3, stream);
+    return block_backward(P, params, packed, tape, g_params, accumulate, workspace, workspace_bytes, perm,
+                          {.x = x, .c = c, .g_z = g_z, .g_J = g_J, .g_x = g_x, .g_c = g_c, .gz_scale = gz_scale, .gJ_const = gJ_const}, B, 3, stream);
 }
 
 int hint_block_backward_rows(const hint_plan* P, const float* params, const float* packed, const float* x,
@@ -572,8 +569,8 @@ int hint_block_backward_rows(const hint_plan* P, const float* params, const floa
                              float gJ_const, int32_t B, void* stream) {
     // part A alone: g_x, g_c and the per-row factors of the weight gradients (left in `workspace` for a later
     // hint_chain_wgrad_range / hint_chain_wgrad_adam over a chain that holds this block with the same tape and workspace)
-    return block_backward(P, params, packed, x, tape, c, g_z, g_J, g_x, g_c, nullptr, 1, workspace, workspace_bytes, perm, gz_scale,
-                          gJ_const, B, 1, stream);
+    return block_backward(P, params, packed, tape, nullptr, 1, workspace, workspace_bytes, perm,
+                          {.x = x, .c = c, .g_z = g_z, .g_J = g_J, .g_x = g_x, .g_c = g_c, .gz_scale = gz_scale, .gJ_const = gJ_const}, B, 1, stream);
 }
 
 #ifdef HINT_STAMPS

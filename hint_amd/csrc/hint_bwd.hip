@@ -416,13 +416,13 @@ __global__ __launch_bounds__(64 * MAX_NW) void hint_bwd_kernel(
 #undef LEVEL_SRC
 }
 
+#include "hint_host.hpp"      // (the launch records; behind the kernels, which see no host name)
+
 namespace hint {
 
-hipError_t launch_bwd(const KArgs& a, int lds_bytes, int grid, const ChainBlock& one, const ChainBlock* chain,
-                      int n_chain, const float* x, const float* c, const float* g_z, const float* g_J,
-                      float* g_x, float* g_c, float gz_scale, float gJ_const, hipStream_t stream) {
-    hipLaunchKernelGGL(hint_bwd_kernel, dim3(grid), dim3(64 * a.nw), lds_bytes, stream, a, one, chain, n_chain, x, c,
-                       g_z, g_J, g_x, g_c, gz_scale, gJ_const);
+hipError_t launch_bwd(const RowLaunch& L, const BlockSet& bs, const BwdIO& io, hipStream_t stream) {
+    hipLaunchKernelGGL(hint_bwd_kernel, dim3(L.grid), dim3(64 * L.a.nw), L.lds, stream, L.a, *bs.one, bs.chain, bs.n_chain, io.x, io.c,
+                       io.g_z, io.g_J, io.g_x, io.g_c, io.gz_scale, io.gJ_const);
     return hipGetLastError();
 }
 

@@ -17,9 +17,9 @@ struct hint_chain {
     ChainBlock* d_table = nullptr;
 };
 
-static bool chain_any_perm(const hint_chain* C) {
-    for (const ChainBlock& b : C->host) if (b.perm != nullptr) return true;
-    return false;
+// blocks [b0, b1) of the chain as the block set of a launch
+static BlockSet blocks_of(const hint_chain* C, int b0, int b1) {
+    return {.one = &C->host[b0], .chain = C->d_table + b0, .host = C->host.data() + b0, .n_chain = b1 - b0, .cb0 = b0, .n_total = C->n};
 }
 
 int hint_chain_create(const hint_plan* P, int32_t n_blocks, int32_t B, hint_chain** out) {
@@ -116,20 +116,9 @@ int hint_chain_forward_noisy(const hint_chain* C, const float* x, const float* c
     if (chain_gathered(C)) return fail("hint_chain_forward: the chain's blocks have inputs of their own (hint_chain_set_block_io): it serves part B only");
     const hint_plan* P = C->plan;
     if (P->dc > 0 && !c) return fail("hint_chain_forward: plan has dc=%d but c is NULL", P->dc);
-    const Dispatch D = dispatch(P, C->B);
-    KArgs a = make_args(P, C->B, false);
-    const int nr = D.nr;
-    const int lds = lds_with_perms(P, plan_lds(P, false, nr), C->n, chain_any_perm(C), &a);
-    if (D.fwd == FWD_WL) {
-        WlArgs w = P->wl_f[nr - 1];
-        w.off_perm = a.perm_lds;
-        HIP_TRY(launch_wl_apply(false, a, w, lds, D.grid, C->host[0], C->d_table, C->n, x, z, J, J_in, loss_acc, noise,
-                                (const unsigned long long*)rng_state, x_noisy, (hipStream_t)stream));
-        return 0;
-    }
-    HIP_TRY(launch_apply(false, D.fwd == FWD_FLY, a, lds, D.grid, C->host[0], C->d_table, C->n, x, c, z, J,
-                         J_in, loss_acc, noise, (const unsigned long long*)rng_state, x_noisy, (hipStream_t)stream));
-    return 0;
+    return launch_rows_fwd(P, C->B, false, blocks_of(C, 0, C->n),
+                           {.x = x, .c = c, .z = z, .J = J, .J_in = J_in, .loss_acc = loss_acc, .noise = noise,
+                            .rng_state = (const unsigned long long*)rng_state, .x_noisy = x_noisy}, (hipStream_t)stream);
 }
 
 int hint_chain_inverse(const hint_chain* C, const float* z, const float* c, float* x, float* J, const float* J_in,
@@ -139,56 +128,68 @@ int hint_chain_inverse(const hint_chain* C, const float* z, const float* c, floa
     if (chain_gathered(C)) return fail("hint_chain_inverse: the chain's blocks have inputs of their own (hint_chain_set_block_io): it serves part B only");
     const hint_plan* P = C->plan;
     if (P->dc > 0 && !c) return fail("hint_chain_inverse: plan has dc=%d but c is NULL", P->dc);
-    const Dispatch D = dispatch(P, C->B);
-    KArgs a = make_args(P, C->B, false);
-    const int nr = D.nr;
-    const int lds = lds_with_perms(P, plan_lds(P, false, nr), C->n, chain_any_perm(C), &a);
-    if (D.fwd == FWD_WL) {
-        WlArgs w = P->wl_f[nr - 1];
-        w.off_perm = a.perm_lds;
-        HIP_TRY(launch_wl_apply(true, a, w, lds, D.grid, C->host[0], C->d_table, C->n, z, x, J, J_in, nullptr, 0.f,
-                                nullptr, nullptr, (hipStream_t)stream));
-        return 0;
+    return launch_rows_fwd(P, C->B, true, blocks_of(C, 0, C->n), {.x = z, .c = c, .z = x, .J = J, .J_in = J_in}, (hipStream_t)stream);
+}
+
+// What the chain's four backward entry points check before run_backward.  `who`: the name inside the messages; the flags hold the
+// entry points' differences, the order of the checks included (each reports the fault it has always reported first).
+enum : unsigned {
+    CK_PART_A = 1, CK_PART_B = 2,      // the parts that run (the bits of `parts`)
+    CK_RANGE = 4,                      // blocks [b0, b1) are the caller's and are checked; else the whole chain
+    CK_ARENAS = 8,                     // `ad` and n: the arenas' alignment, and every block's parameters a slice of them
+    CK_BLOCK_IO = 16,                  // a block's own x_in / c_in (hint_chain_set_block_io) count as inputs; part A refuses such a chain
+    CK_X_FIRST = 32, CK_X_LAST = 64,   // a missing x is reported in front of the arenas' alignment / behind the blocks (neither: between them)
+};
+static int check_backward(const char* who, const hint_chain* C, unsigned f, bool null_arg, const BwdIO& io, int b0, int b1,
+                          const AdamFuse* ad, int64_t n) {
+    if (!C || null_arg || ((f & CK_ARENAS) && (!ad->p || !ad->m || !ad->v || !ad->st))) return fail("%s: null argument", who);
+    if (!C->committed) return fail("%s: hint_chain_commit() has not been called", who);
+    const hint_plan* P = C->plan;
+    const bool own_io = (f & CK_BLOCK_IO) != 0;
+    if (!(f & (CK_PART_A | CK_PART_B))) return fail("hint_chain_backward_parts: parts must select part A (1), part B (2) or both (3)");
+    if (!(f & CK_RANGE)) { b0 = 0; b1 = C->n; }
+    else if (b0 < 0 || b1 > C->n || b0 >= b1) return fail("%s: blocks [%d, %d) out of range (chain has %d)", who, b0, b1, C->n);
+    if ((f & CK_PART_A) && own_io) {
+        if (chain_gathered(C)) return fail("%s: the chain's blocks have inputs of their own (hint_chain_set_block_io): part B only", who);
+        if (!io.g_z || !io.g_x) return fail("%s: null argument", who);
     }
-    HIP_TRY(launch_apply(true, D.fwd == FWD_FLY, a, lds, D.grid, C->host[0], C->d_table, C->n, z, c, x, J, J_in, nullptr, 0.f,
-                         nullptr, nullptr, (hipStream_t)stream));
+    if (!own_io && P->dc > 0 && !io.c) return fail("%s: plan has dc=%d but c is NULL", who, P->dc);
+    const bool no_x = !io.x && !C->host[0].perm && !(own_io && C->host[0].x_in);
+    const char* no_x_msg = "%s: x is NULL but the first block has no fused permutation";
+    if (no_x && (f & CK_X_FIRST)) return fail(no_x_msg, who);
+    if ((f & CK_ARENAS) && (((uintptr_t)ad->p | (uintptr_t)ad->m | (uintptr_t)ad->v) & 15) != 0)
+        return fail("%s: the arenas must be 16-byte aligned", who);
+    if (no_x && !(f & CK_X_LAST)) return fail(no_x_msg, who);
+    for (int i = b0; i < b1; ++i) {
+        const ChainBlock& b = C->host[i];
+        if (own_io && P->dc > 0 && !io.c && !b.c_in) return fail("%s: plan has dc=%d but block %d has no condition", who, P->dc, i);
+        if (!b.wsG1 || !b.actA1 || !b.gparams) return fail("%s: block %d was set without workspace / g_params", who, i);
+        const int64_t off = (f & CK_ARENAS) ? b.params - ad->p : 0;
+        if ((f & CK_ARENAS) && (off < 0 || off + P->param_floats > n || (off & 3) != 0))
+            return fail("%s: block %d's parameters are not a 16-byte aligned slice of the arena [params, params + n)", who, i);
+    }
+    if (no_x) return fail(no_x_msg, who);
     return 0;
+}
+
+static AdamFuse adam_fuse(float* params, float* exp_avg, float* exp_avg_sq, const float* opt_state, float beta1, float beta2, float eps,
+                          float weight_decay, float grad_scale, float grad_clamp) {
+    return {params, exp_avg, exp_avg_sq, opt_state, beta1, beta2, eps, weight_decay, grad_scale, grad_clamp > 0.f ? grad_clamp : HINT_NO_CLAMP};
 }
 
 int hint_chain_backward_parts(const hint_chain* C, const float* x, const float* c, const float* g_z, const float* g_J,
                               float* g_x, float* g_c, float gz_scale, float gJ_const, int32_t accumulate,
                               int32_t parts, void* stream) {
-    if (!C) return fail("hint_chain_backward: null argument");
-    if (!C->committed) return fail("hint_chain_backward: hint_chain_commit() has not been called");
-    const hint_plan* P = C->plan;
-    if ((parts & 3) == 0) return fail("hint_chain_backward_parts: parts must select part A (1), part B (2) or both (3)");
-    if ((parts & 1) && chain_gathered(C)) return fail("hint_chain_backward: the chain's blocks have inputs of their own (hint_chain_set_block_io): part B only");
-    if ((parts & 1) && (!g_z || !g_x)) return fail("hint_chain_backward: null argument");
-    for (int i = 0; i < C->n; ++i) {
-        if (P->dc > 0 && !c && !C->host[i].c_in) return fail("hint_chain_backward: plan has dc=%d but block %d has no condition", P->dc, i);
-        if (!C->host[i].wsG1 || !C->host[i].actA1 || !C->host[i].gparams)
-            return fail("hint_chain_backward: block %d was set without workspace / g_params", i);
-    }
-    if (!x && !C->host[0].perm && !C->host[0].x_in) return fail("hint_chain_backward: x is NULL but the first block has no fused permutation");
-    return run_backward(P, C->host[0], C->d_table, C->host.data(), C->n, 0, C->n, x, c, g_z, g_J, g_x, g_c, gz_scale, gJ_const, C->B,
-                        accumulate ? 1 : 0, parts & 3, (hipStream_t)stream);
+    const BwdIO io{.x = x, .c = c, .g_z = g_z, .g_J = g_J, .g_x = g_x, .g_c = g_c, .gz_scale = gz_scale, .gJ_const = gJ_const};
+    if (check_backward("hint_chain_backward", C, (parts & 3) | CK_BLOCK_IO | CK_X_LAST, false, io, 0, 0, nullptr, 0)) return 1;
+    return run_backward(C->plan, blocks_of(C, 0, C->n), io, C->B, accumulate ? 1 : 0, parts & 3, (hipStream_t)stream);
 }
 
 int hint_chain_wgrad_range(const hint_chain* C, const float* x, const float* c, int32_t accumulate, int32_t block_begin,
                            int32_t block_end, void* stream) {
-    if (!C) return fail("hint_chain_wgrad_range: null argument");
-    if (!C->committed) return fail("hint_chain_wgrad_range: hint_chain_commit() has not been called");
-    if (block_begin < 0 || block_end > C->n || block_begin >= block_end)
-        return fail("hint_chain_wgrad_range: blocks [%d, %d) out of range (chain has %d)", block_begin, block_end, C->n);
-    const hint_plan* P = C->plan;
-    if (!x && !C->host[0].perm && !C->host[0].x_in) return fail("hint_chain_wgrad_range: x is NULL but the first block has no fused permutation");
-    for (int i = block_begin; i < block_end; ++i) {
-        if (P->dc > 0 && !c && !C->host[i].c_in) return fail("hint_chain_wgrad_range: plan has dc=%d but block %d has no condition", P->dc, i);
-        if (!C->host[i].wsG1 || !C->host[i].actA1 || !C->host[i].gparams)
-            return fail("hint_chain_wgrad_range: block %d was set without workspace / g_params", i);
-    }
-    return run_backward(P, C->host[block_begin], C->d_table + block_begin, C->host.data() + block_begin, block_end - block_begin,
-                        block_begin, C->n, x, c, nullptr, nullptr, nullptr, nullptr, 1.f, 0.f, C->B, accumulate ? 1 : 0, 2, (hipStream_t)stream);
+    const BwdIO io{.x = x, .c = c};
+    if (check_backward("hint_chain_wgrad_range", C, CK_PART_B | CK_RANGE | CK_BLOCK_IO, false, io, block_begin, block_end, nullptr, 0)) return 1;
+    return run_backward(C->plan, blocks_of(C, block_begin, block_end), io, C->B, accumulate ? 1 : 0, 2, (hipStream_t)stream);
 }
 
 int hint_chain_backward(const hint_chain* C, const float* x, const float* c, const float* g_z, const float* g_J,
@@ -200,47 +201,20 @@ int hint_chain_backward_adam(const hint_chain* C, const float* x, const float* c
                              float* g_x, float* g_c, float gz_scale, float gJ_const, float* params, float* exp_avg,
                              float* exp_avg_sq, int64_t n, const float* opt_state, float beta1, float beta2, float eps,
                              float weight_decay, float grad_scale, float grad_clamp, void* stream) {
-    if (!C || !g_z || !g_x || !params || !exp_avg || !exp_avg_sq || !opt_state) return fail("hint_chain_backward_adam: null argument");
-    if (!C->committed) return fail("hint_chain_backward_adam: hint_chain_commit() has not been called");
-    const hint_plan* P = C->plan;
-    if (P->dc > 0 && !c) return fail("hint_chain_backward_adam: plan has dc=%d but c is NULL", P->dc);
-    if (!x && !C->host[0].perm) return fail("hint_chain_backward_adam: x is NULL but the first block has no fused permutation");
-    if ((((uintptr_t)params | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & 15) != 0)
-        return fail("hint_chain_backward_adam: the arenas must be 16-byte aligned");
-    for (int i = 0; i < C->n; ++i) {
-        const ChainBlock& b = C->host[i];
-        if (!b.wsG1 || !b.actA1 || !b.gparams) return fail("hint_chain_backward_adam: block %d was set without workspace / g_params", i);
-        const int64_t off = b.params - params;
-        if (off < 0 || off + P->param_floats > n || (off & 3) != 0)
-            return fail("hint_chain_backward_adam: block %d's parameters are not a 16-byte aligned slice of the arena [params, params + n)", i);
-    }
-    AdamFuse ad{params, exp_avg, exp_avg_sq, opt_state, beta1, beta2, eps, weight_decay, grad_scale,
-                grad_clamp > 0.f ? grad_clamp : HINT_NO_CLAMP};
-    return run_backward(P, C->host[0], C->d_table, C->host.data(), C->n, 0, C->n, x, c, g_z, g_J, g_x, g_c, gz_scale, gJ_const, C->B, 1, 3,
-                        (hipStream_t)stream, &ad);
+    const BwdIO io{.x = x, .c = c, .g_z = g_z, .g_J = g_J, .g_x = g_x, .g_c = g_c, .gz_scale = gz_scale, .gJ_const = gJ_const};
+    const AdamFuse ad = adam_fuse(params, exp_avg, exp_avg_sq, opt_state, beta1, beta2, eps, weight_decay, grad_scale, grad_clamp);
+    // (no CK_BLOCK_IO: this entry point has never looked at x_in / c_in, nor refused a gathered chain as hint_chain_backward_parts does)
+    if (check_backward("hint_chain_backward_adam", C, CK_PART_A | CK_PART_B | CK_ARENAS | CK_X_FIRST, !g_z || !g_x, io, 0, 0, &ad, n)) return 1;
+    return run_backward(C->plan, blocks_of(C, 0, C->n), io, C->B, 1, 3, (hipStream_t)stream, &ad);
 }
 
 int hint_chain_wgrad_adam(const hint_chain* C, const float* x, const float* c, float* params, float* exp_avg, float* exp_avg_sq,
                           int64_t n, const float* opt_state, float beta1, float beta2, float eps, float weight_decay,
                           float grad_scale, float grad_clamp, void* stream) {
-    if (!C || !params || !exp_avg || !exp_avg_sq || !opt_state) return fail("hint_chain_wgrad_adam: null argument");
-    if (!C->committed) return fail("hint_chain_wgrad_adam: hint_chain_commit() has not been called");
-    const hint_plan* P = C->plan;
-    if ((((uintptr_t)params | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & 15) != 0)
-        return fail("hint_chain_wgrad_adam: the arenas must be 16-byte aligned");
-    if (!x && !C->host[0].perm && !C->host[0].x_in) return fail("hint_chain_wgrad_adam: x is NULL but the first block has no fused permutation");
-    for (int i = 0; i < C->n; ++i) {
-        const ChainBlock& b = C->host[i];
-        if (P->dc > 0 && !c && !b.c_in) return fail("hint_chain_wgrad_adam: plan has dc=%d but block %d has no condition", P->dc, i);
-        if (!b.wsG1 || !b.actA1 || !b.gparams) return fail("hint_chain_wgrad_adam: block %d was set without workspace / g_params", i);
-        const int64_t off = b.params - params;
-        if (off < 0 || off + P->param_floats > n || (off & 3) != 0)
-            return fail("hint_chain_wgrad_adam: block %d's parameters are not a 16-byte aligned slice of the arena [params, params + n)", i);
-    }
-    AdamFuse ad{params, exp_avg, exp_avg_sq, opt_state, beta1, beta2, eps, weight_decay, grad_scale,
-                grad_clamp > 0.f ? grad_clamp : HINT_NO_CLAMP};
-    return run_backward(P, C->host[0], C->d_table, C->host.data(), C->n, 0, C->n, x, c, nullptr, nullptr, nullptr, nullptr, 1.f, 0.f, C->B, 1, 2,
-                        (hipStream_t)stream, &ad);
+    const BwdIO io{.x = x, .c = c};
+    const AdamFuse ad = adam_fuse(params, exp_avg, exp_avg_sq, opt_state, beta1, beta2, eps, weight_decay, grad_scale, grad_clamp);
+    if (check_backward("hint_chain_wgrad_adam", C, CK_PART_B | CK_ARENAS | CK_BLOCK_IO, false, io, 0, 0, &ad, n)) return 1;
+    return run_backward(C->plan, blocks_of(C, 0, C->n), io, C->B, 1, 2, (hipStream_t)stream, &ad);
 }
 
 void hint_chain_destroy(hint_chain* C) {

@@ -389,19 +389,18 @@ __global__ __launch_bounds__(64 * MAX_NW) void hint_apply_kernel(
 #undef HINT_CB
 }
 
+#include "hint_host.hpp"      // (the launch records; behind the kernels, which see no host name)
+
 namespace hint {
 
-hipError_t launch_apply(bool rev, bool fly, const KArgs& a, int lds_bytes, int grid, const ChainBlock& one,
-                        const ChainBlock* chain, int n_chain, const float* x, const float* c, float* z, float* J,
-                        const float* J_in, float* loss_acc, float noise, const unsigned long long* rng_state,
-                        float* x_noisy, hipStream_t stream) {
-#define HINT_LAUNCH_APPLY(REV, FLYK, ...) hipLaunchKernelGGL((hint_apply_kernel<REV, FLYK>), dim3(grid), dim3(64 * a.nw), lds_bytes, stream, a, one, chain, n_chain, __VA_ARGS__)
+hipError_t launch_apply(bool rev, bool fly, const RowLaunch& L, const BlockSet& bs, const FwdIO& io, hipStream_t stream) {
+#define HINT_LAUNCH_APPLY(REV, FLYK, ...) hipLaunchKernelGGL((hint_apply_kernel<REV, FLYK>), dim3(L.grid), dim3(64 * L.a.nw), L.lds, stream, L.a, *bs.one, bs.chain, bs.n_chain, io.x, io.c, io.z, io.J, io.J_in, __VA_ARGS__)
     if (rev) {
-        if (fly) HINT_LAUNCH_APPLY(true, true, x, c, z, J, J_in, (float*)nullptr, 0.f, (const unsigned long long*)nullptr, (float*)nullptr);
-        else HINT_LAUNCH_APPLY(true, false, x, c, z, J, J_in, (float*)nullptr, 0.f, (const unsigned long long*)nullptr, (float*)nullptr);
+        if (fly) HINT_LAUNCH_APPLY(true, true, (float*)nullptr, 0.f, (const unsigned long long*)nullptr, (float*)nullptr);
+        else HINT_LAUNCH_APPLY(true, false, (float*)nullptr, 0.f, (const unsigned long long*)nullptr, (float*)nullptr);
     } else {
-        if (fly) HINT_LAUNCH_APPLY(false, true, x, c, z, J, J_in, loss_acc, noise, rng_state, x_noisy);
-        else HINT_LAUNCH_APPLY(false, false, x, c, z, J, J_in, loss_acc, noise, rng_state, x_noisy);
+        if (fly) HINT_LAUNCH_APPLY(false, true, io.loss_acc, io.noise, io.rng_state, io.x_noisy);
+        else HINT_LAUNCH_APPLY(false, false, io.loss_acc, io.noise, io.rng_state, io.x_noisy);
     }
 #undef HINT_LAUNCH_APPLY
     return hipGetLastError();

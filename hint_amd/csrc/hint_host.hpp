@@ -1,8 +1,9 @@
 // Host-side internals shared by the translation units behind the C ABI (include/hint_amd.h): the plan object, the
 // kernels' launch wrappers and the helpers every entry point uses.  Not part of the public ABI.
 //   hint_plan.cpp     the planner: node list -> static schedule in device memory (hint_plan_create / _check / _destroy)
-//   hint_abi.cpp      sizes and layouts, the block-level entry points, re-pack groups, the optimizer, build info
-//   hint_chain.cpp    chained launches: the blocks of a flow in one kernel each (hint_chain_*)
+//   hint_abi.cpp      sizes and layouts, the launch path (row_launch, launch_rows_fwd, wgrad_launch, run_backward), the block-level
+//                     entry points, re-pack groups, the optimizer, build info
+//   hint_chain.cpp    chained launches: the blocks of a flow in one kernel each (hint_chain_*); their argument checks
 //   hint_invgrad.cpp  backward of the inverse direction, level by level on the block kernels
 #pragma once
 #include <hip/hip_runtime.h>
@@ -31,39 +32,58 @@ hipError_t launch_inv_lane(int op, float* out, const float* g, const float* a, c
                            int num_cu, hipStream_t stream);
 hipError_t launch_inv_minus(float* dst, const float* src, long n, int keep, int num_cu, hipStream_t stream);
 hipError_t launch_inv_rowmat(const float* x, const float* P, float* y, long n, int d, int num_cu, hipStream_t stream);
-hipError_t launch_apply(bool rev, bool fly, const KArgs& a, int lds_bytes, int grid, const ChainBlock& one,
-                        const ChainBlock* chain, int n_chain, const float* x, const float* c, float* z, float* J,
-                        const float* J_in, float* loss_acc, float noise, const unsigned long long* rng_state,
-                        float* x_noisy, hipStream_t stream);
-hipError_t launch_bwd(const KArgs& a, int lds_bytes, int grid, const ChainBlock& one, const ChainBlock* chain,
-                      int n_chain, const float* x, const float* c, const float* g_z, const float* g_J,
-                      float* g_x, float* g_c, float gz_scale, float gJ_const, hipStream_t stream);
-hipError_t launch_wgrad(const WJob* jobs, int n_jobs, int n_small, int n_rowj, int splits, const ChainBlock& one, const ChainBlock* chain,
-                        int n_chain, int cb0, int WT, int ST, int d, int dc, int n_levels, int B, int Bp, int rows_per_wg,
-                        int64_t act_stride, int64_t a2_off, int64_t bits_a2_off, int64_t param_floats, const float* x,
-                        const float* c, const uint8_t* real, int accumulate, const int32_t* twmap, int tw_floats,
-                        int64_t thin_slab_off, int thin_slabs, int num_cu, const AdamFuse* adam, bool small, bool wide,
+// ---- the arguments of a row-kernel or part-B launch, as records: filled with designated fields at the call sites, unpacked into the
+// kernels' parameter lists by the launch wrappers (the namespace hint tails of hint_fwd.hip, hint_bwd.hip, hint_wl_*.hip, hint_wgrad.hip)
+#pragma clang diagnostic ignored "-Wc++20-designator"      // (designated initializers: C++20, an extension under this build's -std=c++17)
+struct BlockSet {                          // the blocks a launch runs over
+    const ChainBlock* one = nullptr;       // a single block, or the first of the chain's
+    const ChainBlock* chain = nullptr;     // the chain's device table from that block on (nullptr: `one` alone)
+    const ChainBlock* host = nullptr;      // .. and its host copy (nullptr: `one` alone)
+    int n_chain = 1;
+    int cb0 = 0, n_total = 1;              // run_backward: the first block's index in its chain and that chain's length
+};
+inline bool any_perm(const BlockSet& bs) {
+    if (!bs.host) return bs.one->perm != nullptr;
+    for (int i = 0; i < bs.n_chain; ++i) if (bs.host[i].perm != nullptr) return true;
+    return false;
+}
+struct FwdIO {                             // forward / inverse (the inverse reads x as z and writes z as x; it has no loss and no noise)
+    const float* x = nullptr; const float* c = nullptr; float* z = nullptr; float* J = nullptr; const float* J_in = nullptr;
+    float* loss_acc = nullptr; float noise = 0.f; const unsigned long long* rng_state = nullptr; float* x_noisy = nullptr;
+};
+struct BwdIO {                             // backward part A (part B reads x and c)
+    const float* x = nullptr; const float* c = nullptr; const float* g_z = nullptr; const float* g_J = nullptr;
+    float* g_x = nullptr; float* g_c = nullptr; float gz_scale = 1.f, gJ_const = 0.f;
+};
+struct RowLaunch {                         // what a batch of B rows on a plan variant gets (hint_abi.cpp row_launch)
+    KArgs a; WlArgs w;                     // w: wave-local plans only
+    int lds = 0, grid = 0;                 // dynamic LDS bytes, workgroups
+};
+struct WgradLaunch {                       // part B: everything its two kernels are told about the plan and the batch (hint_abi.cpp wgrad_launch)
+    const WJob* jobs; int n_jobs, n_small, n_rowj;     // the launch list; the single-tile jobs among them; the row jobs at its end
+    bool interleave;                       // the planner sorted the jobs (hint_plan::wsorted)
+    int splits, rows_per_wg;
+    int WT, ST, d, dc, n_levels, B, Bp;
+    int64_t act_stride, a2_off, bits_a2_off, param_floats;
+    const uint8_t* real; const int32_t* twmap; int tw_floats;
+    int64_t thin_slab_off; int thin_slabs;             // the backward kernel's first-layer slabs (fuse_dw1): one per workgroup of part A
+    int num_cu; bool small, wide;                      // hint_wgrad_kernel<small, wide>
+};
+hipError_t launch_apply(bool rev, bool fly, const RowLaunch& L, const BlockSet& bs, const FwdIO& io, hipStream_t stream);
+hipError_t launch_wl_apply(bool rev, const RowLaunch& L, const BlockSet& bs, const FwdIO& io, hipStream_t stream);
+// backward part A, indexed by Dispatch::bwd (hint_abi.cpp BWD_LAUNCH): hint_wl_bwd.hip; hint_bwd.hip; hint_bwd3.hip (rows of <= 3 tiles);
+// hint_bwd_fly.hip (plans with lean general groups)
+using BwdLaunch = hipError_t(const RowLaunch& L, const BlockSet& bs, const BwdIO& io, hipStream_t stream);
+BwdLaunch launch_wl_bwd, launch_bwd, launch_bwd_n3, launch_bwd_fly;
+hipError_t launch_wgrad(const WgradLaunch& g, const BlockSet& bs, const float* x, const float* c, int accumulate, const AdamFuse* adam,
                         hipStream_t stream);
-hipError_t launch_bwd_n3(const KArgs& a, int lds_bytes, int grid, const ChainBlock& one, const ChainBlock* chain,
-                         int n_chain, const float* x, const float* c, const float* g_z, const float* g_J,
-                         float* g_x, float* g_c, float gz_scale, float gJ_const, hipStream_t stream);      // (hint_bwd3.hip: rows of <= 3 tiles)
 hipError_t set_max_lds_apply(int bytes);
-hipError_t launch_ext_coeff(const ExtArgs& a, hipStream_t stream);        // (hint_ext.hip)
 hipError_t set_max_lds_bwd(int bytes);
 hipError_t set_max_lds_bwd_n3(int bytes);
-hipError_t launch_bwd_fly(const KArgs& a, int lds_bytes, int grid, const ChainBlock& one, const ChainBlock* chain,
-                          int n_chain, const float* x, const float* c, const float* g_z, const float* g_J,
-                          float* g_x, float* g_c, float gz_scale, float gJ_const, hipStream_t stream);     // (hint_bwd_fly.hip: plans with lean general groups)
 hipError_t set_max_lds_bwd_fly(int bytes);
-hipError_t launch_wl_apply(bool rev, const KArgs& a, const WlArgs& w, int lds_bytes, int grid, const ChainBlock& one,
-                           const ChainBlock* chain, int n_chain, const float* x, float* z, float* J, const float* J_in,
-                           float* loss_acc, float noise, const unsigned long long* rng_state, float* x_noisy,
-                           hipStream_t stream);
-hipError_t launch_wl_bwd(const KArgs& a, const WlArgs& w, int lds_bytes, int grid, const ChainBlock& one,
-                         const ChainBlock* chain, int n_chain, const float* x, const float* g_z, const float* g_J,
-                         float* g_x, float gz_scale, float gJ_const, hipStream_t stream);
 hipError_t set_max_lds_wl_apply(int bytes);
 hipError_t set_max_lds_wl_bwd(int bytes);
+hipError_t launch_ext_coeff(const ExtArgs& a, hipStream_t stream);        // (hint_ext.hip)
 hipError_t launch_adam(float* p, float* g, float* m, float* v, long n, float lr_t, float b1, float b2,
                        float inv_sqrt_bc2, float eps, float wd, float gscale, float gclamp, int zero_grads,
                        int num_cu, const float* dev_state, hipStream_t stream);
@@ -221,8 +241,8 @@ int64_t tape_act_off(const hint_plan* P, int B);
 int64_t act_stride(const hint_plan* P, int B);
 int64_t bits_stride(const hint_plan* P, int B);
 int grid_for(const hint_plan* P, int B);
-// Which kernel instances a batch of B rows runs on: the one decision every launch site takes (apply, run_backward, the chain's
-// forward and inverse) and what hint_plan_dispatch / hint_plan_check_dispatch report.  P may already be the variant (variant()
+// Which kernel instances a batch of B rows runs on: the one decision both launch sites take (launch_rows_fwd, run_backward)
+// and what hint_plan_dispatch / hint_plan_check_dispatch report.  P may already be the variant (variant()
 // returns a variant unchanged); n_chain: blocks of the launch whose part-B batch split counts (run_backward's n_total).
 enum { FWD_WL = 0, FWD_GEN = 1, FWD_FLY = 2 };                  // hint_wl_apply_kernel, hint_apply_kernel<REV, false | true>
 enum { BWD_WL = 0, BWD_GEN = 1, BWD_N3 = 2, BWD_FLY = 3 };      // hint_wl_bwd_kernel, hint_bwd_kernel, hint_bwd_kernel_n3, hint_bwd_kernel_fly
@@ -236,19 +256,18 @@ struct Dispatch {
 Dispatch dispatch(const hint_plan* P, int B, int n_chain = 1);
 int dispatch_out(const hint_plan* P, int B, int32_t* out, int32_t n_out);     // (the exports' layout: include/hint_amd.h)
 int paths_out(const hint_plan* P, int B, int32_t* out, int32_t n_out);        // (hint_plan_paths / hint_plan_check_paths)
-int lds_with_perms(const hint_plan* P, int lds_plan, int n_blocks, bool any_perm, KArgs* a, bool backward = false);     // (backward: which slot of hint_debug_last_lds_bytes the launch's size goes to)
-KArgs make_args(const hint_plan* P, int B, bool backward);
 void split_workspace(const hint_plan* P, int B, void* workspace, ChainBlock* b);
 void bind_tape(const hint_plan* P, int B, float* tape, ChainBlock* b);
+// forward (rev: inverse) of the blocks of `bs` on B rows: the one place that goes dispatch -> kernel arguments -> LDS size ->
+// wave-local or general launch (hint_block_forward* / _inverse*, hint_chain_forward* / _inverse check their arguments and call it)
+int launch_rows_fwd(const hint_plan* P, int B, bool rev, const BlockSet& bs, const FwdIO& io, hipStream_t s);
 // part A (row-parallel, bit 0 of `parts`) and part B (weight gradients, bit 1) of the backward pass of one block or of
 // blocks [cb0, cb0 + n_chain) of a chain of n_total blocks (the batch split of part B follows n_total: a bucketed
 // launch sums in the same order as the whole chain's)
-int run_backward(const hint_plan* P, const ChainBlock& one, const ChainBlock* chain, const ChainBlock* chain_host, int n_chain,
-                 int cb0, int n_total, const float* x, const float* c, const float* g_z, const float* g_J, float* g_x, float* g_c,
-                 float gz_scale, float gJ_const, int B, int accumulate, int parts, hipStream_t s, const AdamFuse* adam = nullptr);
-int block_backward(const hint_plan* P, const float* params, const float* packed, const float* x, const float* tape,
-                   const float* c, const float* g_z, const float* g_J, float* g_x, float* g_c, float* g_params,
-                   int32_t accumulate, void* workspace, size_t workspace_bytes, const float* perm, float gz_scale,
-                   float gJ_const, int32_t B, int parts, void* stream);
+int run_backward(const hint_plan* P, const BlockSet& bs, const BwdIO& io, int B, int accumulate, int parts, hipStream_t s,
+                 const AdamFuse* adam = nullptr);
+int block_backward(const hint_plan* P, const float* params, const float* packed, const float* tape, float* g_params,
+                   int32_t accumulate, void* workspace, size_t workspace_bytes, const float* perm, const BwdIO& io, int32_t B,
+                   int parts, void* stream);
 
 }  // namespace hint

@@ -118,11 +118,11 @@ int hint_block_inverse_backward(const hint_plan* P, const float* params, const f
         if (hint_block_pack(L, params, W + w.packed, stream) != 0) return 1;
         if (hint_block_forward(L, params, W + w.packed, y, c, yup, W + w.J, W + w.tape, B, stream) != 0) return 1;
         HIP_TRY(launch_inv_lane(0, t, nullptr, nullptr, nullptr, lower, n, P->d, cu, s));
-        if (block_backward(L, params, W + w.packed, y, W + w.tape, c, t, nullptr, e, nullptr, gneg, 1, W + w.bws, w.bws_bytes,
-                           nullptr, 1.f, 0.f, B, 1, stream) != 0) return 1;
+        if (block_backward(L, params, W + w.packed, W + w.tape, gneg, 1, W + w.bws, w.bws_bytes, nullptr,
+                           {.x = y, .c = c, .g_z = t, .g_x = e}, B, 1, stream) != 0) return 1;
         HIP_TRY(launch_inv_lane(1, t, g, e, nullptr, lower, n, P->d, cu, s));
-        if (block_backward(L, params, W + w.packed, y, W + w.tape, c, t, g_J, gin, g_c ? gc : nullptr, gneg, 1, W + w.bws,
-                           w.bws_bytes, nullptr, 1.f, 0.f, B, 3, stream) != 0) return 1;
+        if (block_backward(L, params, W + w.packed, W + w.tape, gneg, 1, W + w.bws, w.bws_bytes, nullptr,
+                           {.x = y, .c = c, .g_z = t, .g_J = g_J, .g_x = gin, .g_c = g_c ? gc : nullptr}, B, 3, stream) != 0) return 1;
         HIP_TRY(launch_inv_lane(2, g, g, t, gin, lower, n, P->d, cu, s));
         if (g_c != nullptr) HIP_TRY(launch_inv_minus(g_c, gc, (long)B * P->dc, 1, cu, s));
         y = yup;

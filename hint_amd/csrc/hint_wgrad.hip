@@ -870,45 +870,39 @@ __global__ __launch_bounds__(256) void hint_wreduce_kernel(ChainBlock one, const
     }
 }
 
+#include "hint_host.hpp"      // (the launch records; behind the kernels, which see no host name)
+
 namespace hint {
 
-hipError_t launch_wgrad(const WJob* jobs, int n_jobs, int n_small, int n_rowj, int splits, const ChainBlock& one, const ChainBlock* chain,
-                        int n_chain, int cb0, int WT, int ST, int d, int dc, int n_levels, int B, int Bp, int rows_per_wg,
-                        int64_t act_stride, int64_t a2_off, int64_t bits_a2_off, int64_t param_floats, const float* x,
-                        const float* c, const uint8_t* real, int accumulate, const int32_t* twmap, int tw_floats,
-                        int64_t thin_slab_off, int thin_slabs, int num_cu, const AdamFuse* adam, bool small, bool wide,
-                        hipStream_t stream) {
-    const bool interleave = n_small < 0;       // (flag in the sign: the planner sorted the jobs)
-    if (interleave) n_small = -n_small - 1;
-#ifdef HINT_DW_SOLO_ALL
-    n_small = n_jobs - n_rowj;                          // (experiment: one (job, split) per wavefront for every job)
-    small = n_jobs > 0;
+#ifdef HINT_STAMPS
+#define HINT_DW_STAMPS , h_dw_stamps        // (the diagnostic build's kernels take the stamp buffer as one more parameter)
+#else
+#define HINT_DW_STAMPS
 #endif
-    const int used = (n_jobs - n_small - n_rowj + (n_small + DW_WAVES - 1) / DW_WAVES + (n_rowj + DW_WAVES - 1) / DW_WAVES) * splits;
+
+hipError_t launch_wgrad(const WgradLaunch& g, const BlockSet& bs, const float* x, const float* c, int accumulate, const AdamFuse* adam,
+                        hipStream_t stream) {
+    const int n_chain = bs.n_chain;
+    const int used = (g.n_jobs - g.n_small - g.n_rowj + (g.n_small + DW_WAVES - 1) / DW_WAVES + (g.n_rowj + DW_WAVES - 1) / DW_WAVES) * g.splits;
     const int grid_pb = n_chain > 1 ? (used + 7) / 8 * 8 : used;
     if (used > 0) {
-        const int gpb = (interleave && n_chain > 1 && (splits & 7) == 0) ? -grid_pb : grid_pb;
-#ifdef HINT_STAMPS
-#define HINT_DW_LAUNCH(S_, W_) hipLaunchKernelGGL((hint_wgrad_kernel<S_, W_>), dim3(grid_pb * n_chain), dim3(DW_WAVES * 64), 0, stream, jobs, n_jobs, n_small, n_rowj, splits, \
-                               one, chain, gpb, cb0, WT, ST, d, dc, n_levels, B, Bp, rows_per_wg, act_stride, a2_off, bits_a2_off, param_floats, x, c, h_dw_stamps)
-#else
-#define HINT_DW_LAUNCH(S_, W_) hipLaunchKernelGGL((hint_wgrad_kernel<S_, W_>), dim3(grid_pb * n_chain), dim3(DW_WAVES * 64), 0, stream, jobs, n_jobs, n_small, n_rowj, splits, \
-                               one, chain, gpb, cb0, WT, ST, d, dc, n_levels, B, Bp, rows_per_wg, act_stride, a2_off, bits_a2_off, param_floats, x, c)
-#endif
+        const int gpb = (g.interleave && n_chain > 1 && (g.splits & 7) == 0) ? -grid_pb : grid_pb;
+#define HINT_DW_LAUNCH(S_, W_) hipLaunchKernelGGL((hint_wgrad_kernel<S_, W_>), dim3(grid_pb * n_chain), dim3(DW_WAVES * 64), 0, stream, g.jobs, g.n_jobs, g.n_small, g.n_rowj, g.splits, \
+                               *bs.one, bs.chain, gpb, bs.cb0, g.WT, g.ST, g.d, g.dc, g.n_levels, g.B, g.Bp, g.rows_per_wg, g.act_stride, g.a2_off, g.bits_a2_off, g.param_floats, x, c HINT_DW_STAMPS)
         // (small, wide: dispatch() in hint_abi.cpp - small is n_small > 0)
-        if (wide) { if (small) HINT_DW_LAUNCH(true, true); else HINT_DW_LAUNCH(false, true); }
-        else if (small) HINT_DW_LAUNCH(true, false);
+        if (g.wide) { if (g.small) HINT_DW_LAUNCH(true, true); else HINT_DW_LAUNCH(false, true); }
+        else if (g.small) HINT_DW_LAUNCH(true, false);
         else HINT_DW_LAUNCH(false, false);
 #undef HINT_DW_LAUNCH
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    int blocks_pb = (int)((param_floats / 4 + 255) / 256);
-    const int cap = num_cu * 4 / (n_chain > 0 ? n_chain : 1);
+    int blocks_pb = (int)((g.param_floats / 4 + 255) / 256);
+    const int cap = g.num_cu * 4 / (n_chain > 0 ? n_chain : 1);
     blocks_pb = blocks_pb < 1 ? 1 : (blocks_pb > cap && cap >= 1 ? cap : blocks_pb);
-    const int thin_blocks = twmap != nullptr ? (tw_floats + 31) / 32 : 0;
-    hipLaunchKernelGGL(hint_wreduce_kernel, dim3((blocks_pb + thin_blocks) * n_chain), dim3(256), 0, stream, one, chain, real,
-                       param_floats, splits, accumulate, blocks_pb, twmap, tw_floats, thin_slab_off, thin_slabs, thin_blocks,
+    const int thin_blocks = g.twmap != nullptr ? (g.tw_floats + 31) / 32 : 0;
+    hipLaunchKernelGGL(hint_wreduce_kernel, dim3((blocks_pb + thin_blocks) * n_chain), dim3(256), 0, stream, *bs.one, bs.chain, g.real,
+                       g.param_floats, g.splits, accumulate, blocks_pb, g.twmap, g.tw_floats, g.thin_slab_off, g.thin_slabs, thin_blocks,
                        adam ? *adam : AdamFuse{});
     return hipGetLastError();
 }

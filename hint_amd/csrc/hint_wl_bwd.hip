@@ -337,16 +337,16 @@ __global__ __launch_bounds__(64 * MAX_NW) __attribute__((amdgpu_waves_per_eu(2, 
 #undef GSTP
 }
 
+#include "hint_host.hpp"      // (the launch records; behind the kernels, which see no host name)
+
 namespace hint {
 
-hipError_t launch_wl_bwd(const KArgs& a, const WlArgs& w, int lds_bytes, int grid, const ChainBlock& one,
-                         const ChainBlock* chain, int n_chain, const float* x, const float* g_z, const float* g_J,
-                         float* g_x, float gz_scale, float gJ_const, hipStream_t stream) {
+hipError_t launch_wl_bwd(const RowLaunch& L, const BlockSet& bs, const BwdIO& io, hipStream_t stream) {      // (no condition: io.c, io.g_c unused)
 #define HINT_LAUNCH(NRV, CHV)                                                                                        \
-    hipLaunchKernelGGL((hint_wl_bwd_kernel<NRV, CHV>), dim3(grid), dim3(64 * a.nw), lds_bytes, stream, a, w, one, chain, n_chain, x, \
-                       g_z, g_J, g_x, gz_scale, gJ_const)
-    if (w.nr == 2) { if (chain != nullptr) HINT_LAUNCH(2, true); else HINT_LAUNCH(2, false); }
-    else { if (chain != nullptr) HINT_LAUNCH(1, true); else HINT_LAUNCH(1, false); }
+    hipLaunchKernelGGL((hint_wl_bwd_kernel<NRV, CHV>), dim3(L.grid), dim3(64 * L.a.nw), L.lds, stream, L.a, L.w, *bs.one, bs.chain, bs.n_chain, \
+                       io.x, io.g_z, io.g_J, io.g_x, io.gz_scale, io.gJ_const)
+    if (L.w.nr == 2) { if (bs.chain != nullptr) HINT_LAUNCH(2, true); else HINT_LAUNCH(2, false); }
+    else { if (bs.chain != nullptr) HINT_LAUNCH(1, true); else HINT_LAUNCH(1, false); }
 #undef HINT_LAUNCH
     return hipGetLastError();
 }

@@ -300,21 +300,20 @@ __global__ __launch_bounds__(64 * MAX_NW) __attribute__((amdgpu_waves_per_eu(2, 
 #undef HINT_CB
 }
 
+#include "hint_host.hpp"      // (the launch records; behind the kernels, which see no host name)
+
 namespace hint {
 
-hipError_t launch_wl_apply(bool rev, const KArgs& a, const WlArgs& w, int lds_bytes, int grid, const ChainBlock& one,
-                           const ChainBlock* chain, int n_chain, const float* x, float* z, float* J, const float* J_in,
-                           float* loss_acc, float noise, const unsigned long long* rng_state, float* x_noisy,
-                           hipStream_t stream) {
+hipError_t launch_wl_apply(bool rev, const RowLaunch& L, const BlockSet& bs, const FwdIO& io, hipStream_t stream) {
     const unsigned long long* no_rng = nullptr;
     float* no_f = nullptr;
 #define HINT_LAUNCH(REV, NRV, CHV, LOSS, NOISE, RNG, XN)                                                             \
-    hipLaunchKernelGGL((hint_wl_apply_kernel<REV, NRV, CHV>), dim3(grid), dim3(64 * a.nw), lds_bytes, stream, a, w, one, chain, \
-                       n_chain, x, z, J, J_in, LOSS, NOISE, RNG, XN)
+    hipLaunchKernelGGL((hint_wl_apply_kernel<REV, NRV, CHV>), dim3(L.grid), dim3(64 * L.a.nw), L.lds, stream, L.a, L.w, *bs.one, bs.chain, \
+                       bs.n_chain, io.x, io.z, io.J, io.J_in, LOSS, NOISE, RNG, XN)
 #define HINT_LAUNCH_CH(REV, NRV, LOSS, NOISE, RNG, XN)                                                               \
-    { if (chain != nullptr) HINT_LAUNCH(REV, NRV, true, LOSS, NOISE, RNG, XN); else HINT_LAUNCH(REV, NRV, false, LOSS, NOISE, RNG, XN); }
-    if (rev) { if (w.nr == 2) HINT_LAUNCH_CH(true, 2, no_f, 0.f, no_rng, no_f) else HINT_LAUNCH_CH(true, 1, no_f, 0.f, no_rng, no_f) }
-    else { if (w.nr == 2) HINT_LAUNCH_CH(false, 2, loss_acc, noise, rng_state, x_noisy) else HINT_LAUNCH_CH(false, 1, loss_acc, noise, rng_state, x_noisy) }
+    { if (bs.chain != nullptr) HINT_LAUNCH(REV, NRV, true, LOSS, NOISE, RNG, XN); else HINT_LAUNCH(REV, NRV, false, LOSS, NOISE, RNG, XN); }
+    if (rev) { if (L.w.nr == 2) HINT_LAUNCH_CH(true, 2, no_f, 0.f, no_rng, no_f) else HINT_LAUNCH_CH(true, 1, no_f, 0.f, no_rng, no_f) }
+    else { if (L.w.nr == 2) HINT_LAUNCH_CH(false, 2, io.loss_acc, io.noise, io.rng_state, io.x_noisy) else HINT_LAUNCH_CH(false, 1, io.loss_acc, io.noise, io.rng_state, io.x_noisy) }
 #undef HINT_LAUNCH_CH
 #undef HINT_LAUNCH
     return hipGetLastError();

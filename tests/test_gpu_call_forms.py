@@ -7,8 +7,16 @@ bands and poisoned scratch are tests/test_gpu_poison.py's job; only what the hea
 g_params, Adam's moments - is initialised).  Rows come from one kink-free pool per family and group of forms: candidates next to a
 ReLU kink in the float64 oracle are discarded beforehand (the Spy rule, KINK, the ledger's caps), no row is waived.  Tolerances are
 check_fwd / check_grads and TOL_* of tests/test_gpu_instances.py: a dropped term is an error of order 1
-(test_a_natural_mistake_is_far_over_the_bound).  Each test prints its worst error over bound per form before it asserts."""
+(test_a_natural_mistake_is_far_over_the_bound).  Each test prints its worst error over bound per form before it asserts.
+
+Behind the oracle comparisons every test holds the launch to tests/golden/launch_bits.json (tests/golden/make_launch_bits.py wrote
+it): a sha256 of every generated input and of every tensor the forms hand back, the dynamic LDS bytes of the last forward and
+backward launch and the tape and workspace sizes at that B - the host launch path's decisions, bit for bit.  The bits belong to
+the CU count they were recorded on: on another device the test fails and says so."""
 import ctypes as C
+import hashlib
+import json
+import os
 
 import pytest
 import torch
@@ -177,6 +185,7 @@ def run_block_forms(rig, worst):
     grads_ok("F3 first pass", got, first)
     grads_ok("F3 second pass (accumulate)", got2, second)
     assert torch.equal(gp2.cpu()[~rig.real.cpu()], R[~rig.real.cpu()]), "accumulate: the arena's padding changed"
+    return r, dict(z=z, J=J, loss=loss, xi=xi, Ji=Ji, gx=gx, gc=gc, gp=gp[rig.real], gx2=gx2, gc2=gc2, gp2=gp2[rig.real])
 
 
 # ------------------------------------------------------------------------------------------------------ F4, F5: the chain
@@ -222,6 +231,7 @@ def run_chain_forms(rig, worst):
         same = torch.equal(rig.G[real], G4[real])
         worst.note("F5", 0.0 if same else float("inf"), "wgrad_range [2,3) then [0,2)")
         assert same, "F5: hint_chain_wgrad_range [2,3) then [0,2) differs from the single call"
+        return r, dict(z=z, J=J, loss=loss, gx=gx, gc=gc, G=G4[real])
     finally:
         lib.hint_chain_destroy(h)
 
@@ -280,6 +290,8 @@ def run_gathered_forms(rig, worst):
         assert torch.equal(rig.arena, P0), "F7: lr = 0 moved the weights"
         assert bool((rig.G == 7.0).all()), "F7: the gradient arena was written"
         assert bool((M[~real] == 0).all()) and bool((V[~real] == 0).all()), "F7: padding of the moments was stepped"
+        return r, dict(G=G6[real], arena=rig.arena, exp_avg=M, exp_avg_sq=V,
+                       **{f"{k}{i}": out[i][k] for i in range(NB) for k in ("z", "J", "gx", "gc")})
     finally:
         lib.hint_chain_destroy(h)
 
@@ -290,11 +302,16 @@ COMPARES = {"F1": run_block_forms, "F2": run_block_forms, "F3": run_block_forms,
 CASES = [(g, fam.name) for fam in cf.FAMILIES for g, forms in cf.GROUPS.items() if all((f, fam.name) in cf.pairs() for f in forms)]
 
 
-@pytest.mark.parametrize("group,fam_name", CASES, ids=[f"{f}-{g}" for g, f in CASES])
-def test_call_forms_vs_oracle(group, fam_name):
-    torch.set_num_threads(min(16, torch.get_num_threads()))      # (the float64 oracle: a GPU box has many host cores)
-    lib = _lib.load()
-    cu = torch.cuda.get_device_properties(0).multi_processor_count
+BITS_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "launch_bits.json")
+LOSS_SLOTS = 64         # loss_acc: float atomics into this many slots - one summation order only while no two workgroups share a slot
+
+
+def sha(t):
+    return hashlib.sha256(t.detach().contiguous().cpu().numpy().tobytes()).hexdigest()
+
+
+def run_case(lib, group, fam_name, cu):
+    """one (group, family) against the oracle -> its record for tests/golden/launch_bits.json"""
     fam = cf.FAMILY[fam_name]
     B = cf.resolve_B(lib, fam, cu)
     rig = Rig(fam, lib, B)
@@ -302,6 +319,31 @@ def test_call_forms_vs_oracle(group, fam_name):
     rig.assert_dispatch(entry)
     worst = Worst(fam)
     try:
-        run(rig, worst)
+        ins, outs = run(rig, worst)
     finally:
         worst.print()
+    if plan_dispatch(lib, rig.plan, B)["grid"] > LOSS_SLOTS:
+        outs.pop("loss", None)
+    ins = dict(ins, params=rig.arena, **{f"W{i}": w for i, w in enumerate(rig.W)})
+    return dict(cu=cu, B=B, lds_fwd=lib.hint_debug_last_lds_bytes(0), lds_bwd=lib.hint_debug_last_lds_bytes(1),
+                tape_floats=lib.hint_plan_tape_floats(rig.plan, B), workspace_bytes=int(lib.hint_plan_workspace_bytes(rig.plan, B)),
+                inputs={k: sha(v) for k, v in sorted(ins.items())}, outputs={k: sha(v) for k, v in sorted(outs.items()) if v is not None})
+
+
+@pytest.mark.parametrize("group,fam_name", CASES, ids=[f"{f}-{g}" for g, f in CASES])
+def test_call_forms_vs_oracle(group, fam_name):
+    torch.set_num_threads(min(16, torch.get_num_threads()))      # (the float64 oracle: a GPU box has many host cores)
+    lib = _lib.load()
+    cu = torch.cuda.get_device_properties(0).multi_processor_count
+    with open(BITS_PATH) as f:
+        bits = json.load(f)
+    want = bits["cases"][f"{group}/{fam_name}"]
+    assert cu == want["cu"], (f"{BITS_PATH} was recorded on a device of {want['cu']} CUs and this one has {cu}: batch sizes, grids and "
+                              "summation orders follow the CU count, so the recorded bits say nothing here")
+    got = run_case(lib, group, fam_name, cu)
+    dropped = {k.split(":")[1] for k in bits["dropped"] if k.startswith(f"{group}/{fam_name}:")}
+    assert set(got["outputs"]) == set(want["outputs"]) | dropped, (sorted(got["outputs"]), sorted(want["outputs"]), sorted(dropped))
+    got["outputs"] = {k: v for k, v in got["outputs"].items() if k not in dropped}
+    assert got["inputs"] == want["inputs"], f"{group}/{fam_name}: a generated input drifted: look at tests/call_forms.py, not at the kernels"
+    diff = sorted(k for k in want if k != "outputs" and got[k] != want[k]) + sorted(k for k, v in want["outputs"].items() if got["outputs"][k] != v)
+    assert not diff, (f"{group}/{fam_name}: not the recorded bits", diff, {k: (got[k], want[k]) for k in diff if k in want})

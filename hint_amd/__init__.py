@@ -12,6 +12,7 @@ from .conditional import (AffineCoupling, ConditionalFlowTrainer, ConditionalHin
                           ExternalAffineCoupling, F_fully_connected)
 from .optim import ClampAdam  # noqa: F401,E402
 from .metrics import MultiMMD, multi_mmd  # noqa: F401,E402
+from .metrics import CorrelationTarget, corr_mse, corrcoef  # noqa: F401,E402
 from .abc import nearest_rows, quantile_abc  # noqa: F401,E402
 from .curves import curve_features, lens_forward_process, mean_target_distance, target_distances  # noqa: F401,E402
 from .curves import chamfer_distances, hausdorff_distances, lens_fit_loss, trace_fourier_curves  # noqa: F401,E402

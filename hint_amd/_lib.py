@@ -94,6 +94,12 @@ class OverlapDesc(C.Structure):
                 ("dice", C.c_void_p), ("crossings", C.c_void_p), ("max_groups", C.c_int32)]
 
 
+class CorrDesc(C.Structure):
+    """mirror of `hint_corr_desc` (include/hint_amd.h)"""
+    _fields_ = [("x", C.c_void_p), ("n", C.c_int32), ("d", C.c_int32), ("target", C.c_void_p), ("corr", C.c_void_p),
+                ("out", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
+
+
 _lib = None
 
 _PROTOS = {
@@ -190,6 +196,9 @@ _PROTOS = {
     "hint_overlap_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32, C.c_int64]),
     "hint_overlap_run": (C.c_int, [C.POINTER(OverlapDesc), C.c_void_p]),
     "hint_overlap_geometry": (C.c_int64, [C.c_int64, C.c_int32, C.c_int64, C.c_int32]),
+    "hint_corr_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "hint_corr_run": (C.c_int, [C.POINTER(CorrDesc), C.c_void_p]),
+    "hint_corr_job": (C.c_int64, [C.c_int32, C.c_int32, C.c_int64, C.c_int32]),
 }
 
 

@@ -5,6 +5,11 @@
 costs three N x N GEMMs and about thirty passes over N x N temporaries there; here it is hint_mmd_run: four small launches,
 no N x N matrix in memory, a bit-reproducible result.  MultiMMD keeps one ground-truth set and its YY term, for loops that score
 many samples against it (compare_conditional: eight models per run).  No gradient is implemented and there is no CPU fallback.
+
+    corrcoef(x), corr_mse(x, corr_true), CorrelationTarget                  run_experiments.py:212-221 (test_likelihood)
+
+are np.corrcoef(x.T) and np.nanmean(np.square(corr - corr_true)) in double on the kernels of hint_corr.hip: the sample stays on
+the device, numpy's NaN entries are kept, the result is bit-reproducible.
 """
 from __future__ import annotations
 
@@ -16,7 +21,7 @@ import torch
 from . import _lib
 from ._lib import HintAmdError
 
-__all__ = ["multi_mmd", "MultiMMD", "DEFAULT_WIDTHS_EXPONENTS", "mmd_jobs"]
+__all__ = ["multi_mmd", "MultiMMD", "DEFAULT_WIDTHS_EXPONENTS", "mmd_jobs", "corrcoef", "corr_mse", "CorrelationTarget", "corr_jobs"]
 
 DEFAULT_WIDTHS_EXPONENTS = ((0.5, 1), (0.2, 1), (0.2, 0.5))      # rejection_sampling.py:56
 MAX_KERNELS = 8
@@ -37,19 +42,19 @@ def _check_kernels(widths_exponents) -> Tuple[Tuple[float, float], ...]:
     return ks
 
 
-def _check_set(t, name: str) -> torch.Tensor:
+def _check_set(t, name: str, who: str = "multi_mmd") -> torch.Tensor:
     if not isinstance(t, torch.Tensor):
-        raise HintAmdError(f"multi_mmd: {name} must be a tensor (got {type(t).__name__})")
+        raise HintAmdError(f"{who}: {name} must be a tensor (got {type(t).__name__})")
     if t.dim() != 2:
-        raise HintAmdError(f"multi_mmd: {name} must be 2-D [samples, features] (got shape {tuple(t.shape)})")
+        raise HintAmdError(f"{who}: {name} must be 2-D [samples, features] (got shape {tuple(t.shape)})")
     if not t.is_cuda:
-        raise HintAmdError(f"multi_mmd: {name} is on {t.device}; the metric is a GPU kernel and there is no CPU fallback")
+        raise HintAmdError(f"{who}: {name} is on {t.device}; the metric is a GPU kernel and there is no CPU fallback")
     if t.shape[0] < 1 or t.shape[1] < 1:
-        raise HintAmdError(f"multi_mmd: {name} is empty (shape {tuple(t.shape)})")
+        raise HintAmdError(f"{who}: {name} is empty (shape {tuple(t.shape)})")
     if not t.is_floating_point():
-        raise HintAmdError(f"multi_mmd: {name} is {t.dtype}; expected a floating-point tensor")
+        raise HintAmdError(f"{who}: {name} is {t.dtype}; expected a floating-point tensor")
     if t.requires_grad and torch.is_grad_enabled():
-        raise HintAmdError(f"multi_mmd: {name} requires grad, and no gradient of the metric is implemented; "
+        raise HintAmdError(f"{who}: {name} requires grad, and no gradient of the metric is implemented; "
                            "call it under torch.no_grad() or detach the input")
     t = t.detach()
     if t.dtype != torch.float32 or not t.is_contiguous():         # (copies only where needed)
@@ -123,3 +128,95 @@ class MultiMMD:
         return out[0]
 
     __call__ = mmd
+
+
+# ---- correlation matrix / correlation MSE (hint_corr.hip): run_experiments.py:212-221 ----
+
+def corr_jobs(n: int, d: int):
+    """the Gram launch's work items, (slab, tile row, tile column, first row, rows) each, with the tile edge T, the rows per
+    slab R and the slab count.  Host only."""
+    lib = _lib.load()
+    count = lib.hint_corr_job(n, d, -1, 0)
+    _lib.check(1 if count < 0 else 0, "hint_corr_job")
+    T, R, slabs = (lib.hint_corr_job(n, d, -1, f) for f in (1, 2, 3))
+    return [tuple(lib.hint_corr_job(n, d, j, f) for f in range(5)) for j in range(count)], T, R, slabs
+
+
+def _check_target(t, d: int, device, who: str) -> torch.Tensor:
+    """corr_true as a contiguous float64 [d, d] tensor on `device` (fp32 -> fp64 is exact)"""
+    if not isinstance(t, torch.Tensor):
+        try:
+            t = torch.as_tensor(t)
+        except (TypeError, ValueError, RuntimeError) as e:
+            raise HintAmdError(f"{who}: corr_true must be a tensor or an array (got {type(t).__name__})") from e
+    if t.dtype not in (torch.float32, torch.float64):
+        raise HintAmdError(f"{who}: corr_true is {t.dtype}; expected float32 or float64")
+    if tuple(t.shape) != (d, d):
+        raise HintAmdError(f"{who}: corr_true has shape {tuple(t.shape)}; x has {d} columns, so expected ({d}, {d})")
+    return t.detach().to(device=device, dtype=torch.float64).contiguous()
+
+
+def _corr_run(x: torch.Tensor, target, want_corr: bool):
+    """(out[4], corr or None) of a checked fp32 x and a checked float64 target (or None) on x's device"""
+    lib = _lib.load()
+    n, d = x.shape
+    nbytes = lib.hint_corr_workspace_bytes(n, d)
+    if nbytes == 0:
+        _lib.check(1, "hint_corr_workspace_bytes")
+    with torch.cuda.device(x.device):
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+        out = torch.empty(4, dtype=torch.float64, device=x.device)
+        corr = torch.empty((d, d), dtype=torch.float64, device=x.device) if want_corr else None
+        desc = _lib.CorrDesc()
+        desc.x, desc.n, desc.d = x.data_ptr(), n, d
+        desc.target = None if target is None else target.data_ptr()
+        desc.corr = None if corr is None else corr.data_ptr()
+        desc.out, desc.workspace, desc.workspace_bytes = out.data_ptr(), ws.data_ptr(), nbytes
+        st = lib.hint_corr_run(desc, torch.cuda.current_stream(x.device).cuda_stream)
+    _lib.check(st, "hint_corr_run")
+    return out, corr
+
+
+def corrcoef(x: torch.Tensor) -> torch.Tensor:
+    """np.corrcoef(x.T) of a sample x [n, d] (rows are samples) as a float64 [d, d] tensor on x's device, numpy's NaNs included"""
+    x = _check_set(x, "x", "corrcoef")
+    return _corr_run(x, None, True)[1]
+
+
+def corr_mse(x: torch.Tensor, corr_true) -> torch.Tensor:
+    """np.nanmean(np.square(np.corrcoef(x.T) - corr_true)) as a 0-dim float64 tensor on x's device (run_experiments.py:212-221)"""
+    x = _check_set(x, "x", "corr_mse")
+    t = _check_target(corr_true, x.shape[1], x.device, "corr_mse")
+    return _corr_run(x, t, False)[0][0]
+
+
+class CorrelationTarget:
+    """corr_mse against one ground-truth correlation matrix, kept on the device as float64: mse(x) returns corr_mse(x, corr_true)
+    bit for bit.  `corr` is the last sample's matrix; `terms` holds [sum of squares, entries compared, NaN entries of corr] of the
+    last call.  from_sample(x) takes corr_true from a ground-truth sample (rejection_sampling.py:105-132)."""
+
+    def __init__(self, corr_true):
+        if not isinstance(corr_true, torch.Tensor):
+            corr_true = torch.as_tensor(corr_true)
+        if corr_true.dim() != 2 or corr_true.shape[0] != corr_true.shape[1] or corr_true.shape[0] < 1:
+            raise HintAmdError(f"CorrelationTarget: corr_true must be a square matrix (got shape {tuple(corr_true.shape)})")
+        self._given = corr_true
+        self.target = None          # float64 on the device of the first sample
+        self.corr = None
+        self.terms = None
+
+    @classmethod
+    def from_sample(cls, x: torch.Tensor) -> "CorrelationTarget":
+        o = cls(corrcoef(x))
+        o.target = o._given
+        return o
+
+    def mse(self, x: torch.Tensor) -> torch.Tensor:
+        x = _check_set(x, "x", "CorrelationTarget.mse")
+        if self.target is None or self.target.device != x.device or self.target.shape[0] != x.shape[1]:
+            self.target = _check_target(self._given, x.shape[1], x.device, "CorrelationTarget.mse")
+        out, self.corr = _corr_run(x, self.target, True)
+        self.terms = out[1:4]
+        return out[0]
+
+    __call__ = mse

@@ -914,6 +914,34 @@ size_t hint_overlap_workspace_bytes(int64_t n_rows, int32_t n_coeffs, int32_t n_
 int hint_overlap_run(const hint_overlap_desc* desc, void* stream);
 int64_t hint_overlap_geometry(int64_t n_rows, int32_t n_points, int64_t max_template_points, int32_t field);
 
+/* Correlation matrix and correlation MSE, the second number of the reference's test_likelihood (run_experiments.py:212-221:
+ * the sample goes to the host, np.corrcoef(x.T) and np.nanmean(np.square(corr - corr_true)) run there; corr_true is the
+ * np.corrcoef of a ground-truth sample, rejection_sampling.py:105-132).  For x fp32 [n, d], rows being samples, all in double:
+ *   u = x - column mean,  S_ij = sum_rows u_i u_j,  r_ij = S_ij / (sqrt(S_ii) sqrt(S_jj)) clipped to [-1, 1]
+ *   out = {mse, sum, count, nan_r}: sum of (r_ij - t_ij)^2 over the `count` entries where that difference is not NaN,
+ *         mse = sum / count (NaN for count 0: np.nanmean's value), nan_r = NaN entries of r.  Without a target: {NaN, 0, 0, nan_r}.
+ * NaN semantics are numpy's: a column of zero variance (n = 1: every column), or one holding a NaN or an inf, gives a NaN row and
+ * column of r and changes no other entry.  corr is symmetric bit for bit.  Four launches on `stream`, no atomics: the same bits
+ * on every run.  Every byte of out, of corr (when given) and of the first workspace_bytes the library asks for is written.
+ *   hint_corr_workspace_bytes   bytes of workspace for a run (0 on bad sizes); never more than 68 MiB (d = 512, n > 16384), 2.3 MiB
+ *                               at 10000 x 100.  Limits: 1 <= n <= 2^24, 1 <= d <= 512.
+ *   hint_corr_job               the Gram launch's work items, host only: the rows are cut into slabs of R rows (R = 256 up to 64
+ *                               slabs, more rows per slab beyond), and a job is one slab's 16 x 16 tile (ti, tj >= ti) of S.
+ *                               j = -1: field 0 the job count, 1 the tile edge, 2 R, 3 the slab count; j >= 0: field 0 the job's
+ *                               slab, 1 ti, 2 tj, 3 its first row, 4 its row count.  -1 on an error.
+ * None of these has a caller's device buffer among its parameters: the buffers are named by the descriptor. */
+typedef struct hint_corr_desc {
+    const float* x;                        /* device float[n, d] row-major, 4-byte aligned */
+    int32_t n, d;
+    const double* target;                  /* NULL, or device double[d, d]: corr_true */
+    double* corr;                          /* NULL, or device double[d, d]; target and corr are not both NULL */
+    double* out;                           /* device double[4] */
+    void* workspace; size_t workspace_bytes;      /* 16-byte aligned */
+} hint_corr_desc;
+size_t hint_corr_workspace_bytes(int32_t n, int32_t d);
+int hint_corr_run(const hint_corr_desc* desc, void* stream);
+int64_t hint_corr_job(int32_t n, int32_t d, int64_t j, int32_t field);
+
 int hint_abi_version(void);
 const char* hint_last_error(void);
 /* what the library binary was built with and runs with: "libhint_amd abi N, gfx950, HIP x.y.z, clang ..., src <12 hex digits: hash

@@ -109,6 +109,7 @@ _PROTOS = {
     "hint_debug_set_prefetch": (C.c_int, [C.c_int]),
     "hint_debug_reload_knobs": (C.c_int, []),
     "hint_debug_last_lds_bytes": (C.c_int32, [C.c_int32]),
+    "hint_debug_last_wl_shape": (C.c_int32, [C.c_int32]),
     "hint_plan_create": (C.c_int, [C.POINTER(NodeDesc), C.c_int32, C.c_int32, C.c_int32, C.c_float,
                                    C.POINTER(C.c_void_p)]),
     "hint_plan_check": (C.c_int, [C.POINTER(NodeDesc), C.c_int32, C.c_int32, C.c_int32, C.c_float,
@@ -126,6 +127,8 @@ _PROTOS = {
     "hint_plan_paths": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.c_int32]),
     "hint_plan_check_paths": (C.c_int, [C.POINTER(NodeDesc), C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32,
                                         C.c_int32, C.POINTER(C.c_int32), C.c_int32]),
+    "hint_plan_check_wl_shape": (C.c_int64, [C.POINTER(NodeDesc), C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32,
+                                             C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "hint_plan_check_digest": (C.c_int, [C.POINTER(NodeDesc), C.c_int32, C.c_int32, C.c_int32, C.c_float,
                                          C.POINTER(C.c_uint64), C.c_int32]),
     "hint_plan_check_wjob": (C.c_int64, [C.POINTER(NodeDesc), C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_int64,

@@ -25,6 +25,7 @@ static Knobs read_knobs() {
     if (get("HINT_PLAN_DUMP", &v)) k.plan_dump = v != 0;
     if (get("HINT_WL", &v)) k.wl = v != 0;
     if (get("HINT_WL_NR", &v)) k.wl_nr = v;
+    if (get("HINT_WL_STATIC", &v)) k.wl_static = v != 0;
     if (get("HINT_SUB", &v)) k.sub = v != 0;
     if (get("HINT_NW", &v)) k.nw = v;
     if (get("HINT_LEAN", &v)) k.lean = v != 0;
@@ -129,6 +130,7 @@ int64_t ws_thin_off(const hint_plan* P, int B) {        // floats from the part-
 // HINT_PF (0 = off; hint_host.hpp Knobs).
 static std::atomic<int> g_l2_prefetch{-1};
 static std::atomic<int> g_last_lds[2] = {{0}, {0}};     // dynamic LDS bytes of the last row-kernel launch: [0] forward / inverse, [1] backward part A
+static std::atomic<int> g_last_shape[2] = {{-1}, {-1}}; // .. and the WL_SHAPES entry whose instance it ran on (-1: a dynamic instance, or no wave-local kernel)
 bool l2_prefetch_on() {
     int v = g_l2_prefetch.load(std::memory_order_relaxed);
     if (v < 0) {
@@ -270,13 +272,34 @@ static RowLaunch row_launch(const Dispatch& D, int B, bool backward, const Block
     if (P->wl) {
         L.w = (backward ? P->wl_b : P->wl_f)[D.nr - 1];
         L.w.off_perm = L.a.perm_lds;
+        // the shape-specialised instances exist for chained launches only (the training forward and the backward)
+        if (knobs().wl_static && bs.chain != nullptr) L.shape = wl_shape_match(L.a, L.w, backward);
     }
     return L;
 }
 
+// what hint_plan_check_wl_shape reads: the table entry a chained training launch of the variant for B would take, then the
+// launch's own folded fields in list order (what tools/wl_shape_table.py prints the table from)
+int wl_shape_out(const hint_plan* P, int B, bool backward, bool with_perm, int32_t* out, int32_t n_out) {
+    const Dispatch D = dispatch(P, B);
+    if (!D.P->wl) {                  // (the general kernels: no entry, no fields)
+        for (int i = 0; i < n_out && i < 1 + WL_FOLD_FIELDS; ++i) out[i] = i == 0 ? -1 : 0;
+        return 0;
+    }
+    ChainBlock blk{};
+    blk.perm = with_perm ? (const float*)&blk : nullptr;       // (never read: row_launch asks whether there is one)
+    const RowLaunch L = row_launch(D, B, backward, {.one = &blk, .chain = &blk, .host = &blk});
+    const WlFold f = wl_fold_of(L.a, L.w);
+    if (n_out > 0) out[0] = L.shape;
+    for (int i = 0; i < WL_FOLD_FIELDS && 1 + i < n_out; ++i) out[1 + i] = ((const int32_t*)&f)[i];
+    return 0;
+}
+
 int launch_rows_fwd(const hint_plan* P, int B, bool rev, const BlockSet& bs, const FwdIO& io, hipStream_t s) {
     const Dispatch D = dispatch(P, B);
-    const RowLaunch L = row_launch(D, B, false, bs);
+    RowLaunch L = row_launch(D, B, false, bs);
+    if (rev) L.shape = -1;          // (the sampling direction stays dynamic)
+    g_last_shape[0].store(L.shape, std::memory_order_relaxed);
     if (D.fwd == FWD_WL) HIP_TRY(launch_wl_apply(rev, L, bs, io, s));
     else HIP_TRY(launch_apply(rev, D.fwd == FWD_FLY, L, bs, io, s));
     return 0;
@@ -306,7 +329,11 @@ int run_backward(const hint_plan* P, const BlockSet& bs, const BwdIO& io, int B,
 #endif
 
     const Dispatch D = dispatch(P, B, bs.n_total);
-    if (parts & 1) HIP_TRY(BWD_LAUNCH[D.bwd](row_launch(D, B, true, bs), bs, io, s));
+    if (parts & 1) {
+        const RowLaunch L = row_launch(D, B, true, bs);
+        g_last_shape[1].store(L.shape, std::memory_order_relaxed);
+        HIP_TRY(BWD_LAUNCH[D.bwd](L, bs, io, s));
+    }
     if (parts & 2) HIP_TRY(launch_wgrad(wgrad_launch(D, B), bs, io.x, io.c, accumulate, adam, s));
     return 0;
 }
@@ -362,6 +389,7 @@ int hint_debug_set_prefetch(int on) {
     return g_l2_prefetch.exchange(on ? 1 : 0);
 }
 int32_t hint_debug_last_lds_bytes(int32_t backward) { return g_last_lds[backward ? 1 : 0].load(std::memory_order_relaxed); }
+int32_t hint_debug_last_wl_shape(int32_t backward) { return g_last_shape[backward ? 1 : 0].load(std::memory_order_relaxed); }
 
 int64_t hint_plan_param_floats(const hint_plan* P) { return P ? P->param_floats : -1; }
 // + PACK_SLACK floats of zeros behind the bias region (a padded row's dummy steps load up to three tiles past its last)

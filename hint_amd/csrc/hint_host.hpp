@@ -20,6 +20,7 @@
 
 #include "../../include/hint_amd.h"
 #include "hint_dev.h"
+#include "hint_wl_shape.hpp"
 #include "hint_adam.hpp"
 
 namespace hint {
@@ -58,6 +59,7 @@ struct BwdIO {                             // backward part A (part B reads x an
 struct RowLaunch {                         // what a batch of B rows on a plan variant gets (hint_abi.cpp row_launch)
     KArgs a; WlArgs w;                     // w: wave-local plans only
     int lds = 0, grid = 0;                 // dynamic LDS bytes, workgroups
+    int shape = -1;                        // wave-local plans: entry of WL_SHAPES (hint_wl_shape.hpp) whose instance a chained training forward / backward takes; -1: the dynamic one
 };
 struct WgradLaunch {                       // part B: everything its two kernels are told about the plan and the batch (hint_abi.cpp wgrad_launch)
     const WJob* jobs; int n_jobs, n_small, n_rowj;     // the launch list; the single-tile jobs among them; the row jobs at its end
@@ -129,6 +131,7 @@ struct Knobs {
     bool plan_dump = false;     // HINT_PLAN_DUMP=1   the planner prints groups, rows per wavefront, LDS sizes, kernel decisions, boundary slots
     bool wl = true;             // HINT_WL=0          no wave-local kernels (narrow trees run on the general ones)
     int wl_nr = 0;              // HINT_WL_NR=1|2     wave-local kernels: row tiles per workgroup forced
+    bool wl_static = true;      // HINT_WL_STATIC=0   wave-local kernels: no shape-specialised instances (hint_wl_shape.hpp), every launch on the dynamic ones
     bool sub = true;            // HINT_SUB=0         no subtree groups
     int nw = 0;                 // HINT_NW=4|8        wavefronts per workgroup of the general kernels (0: the planner picks)
     bool lean = true;           // HINT_LEAN=0        keep a1 / g2 in HBM (no lean, lean-wide or subtree groups)
@@ -256,6 +259,7 @@ struct Dispatch {
 Dispatch dispatch(const hint_plan* P, int B, int n_chain = 1);
 int dispatch_out(const hint_plan* P, int B, int32_t* out, int32_t n_out);     // (the exports' layout: include/hint_amd.h)
 int paths_out(const hint_plan* P, int B, int32_t* out, int32_t n_out);        // (hint_plan_paths / hint_plan_check_paths)
+int wl_shape_out(const hint_plan* P, int B, bool backward, bool with_perm, int32_t* out, int32_t n_out);   // (hint_plan_check_wl_shape)
 void split_workspace(const hint_plan* P, int B, void* workspace, ChainBlock* b);
 void bind_tape(const hint_plan* P, int B, float* tape, ChainBlock* b);
 // forward (rev: inverse) of the blocks of `bs` on B rows: the one place that goes dispatch -> kernel arguments -> LDS size ->

@@ -1317,6 +1317,18 @@ int hint_plan_check_paths(const hint_node_desc* nodes, int32_t n_nodes, int32_t 
     return 0;
 }
 
+int64_t hint_plan_check_wl_shape(const hint_node_desc* nodes, int32_t n_nodes, int32_t d, int32_t dc, float clamp, int32_t B,
+                                 int32_t num_cu, int32_t backward, int32_t with_perm, int32_t field) {
+    if (B < 1 || num_cu < 1 || field < -1 || field >= HINT_WL_FOLD_FIELDS) { fail("hint_plan_check_wl_shape: bad arguments"); return INT64_MIN; }
+    std::unique_ptr<hint_plan> P;
+    if (host_plan(nodes, n_nodes, d, dc, clamp, &P)) return INT64_MIN;
+    P->num_cu = num_cu;
+    if (P->alt4) P->alt4->num_cu = num_cu;
+    int32_t v[1 + HINT_WL_FOLD_FIELDS];
+    wl_shape_out(P.get(), B, backward != 0, with_perm != 0, v, 1 + HINT_WL_FOLD_FIELDS);
+    return v[1 + field];
+}
+
 int64_t hint_plan_check_wjob(const hint_node_desc* nodes, int32_t n_nodes, int32_t d, int32_t dc, float clamp, int32_t variant,
                              int64_t j, int32_t field) {
     std::unique_ptr<hint_plan> P;

@@ -20,8 +20,36 @@
 // a group to its first row of the next group and of the next block.
 #pragma once
 #include "hint_rows.hpp"
+#include "hint_wl_shape.hpp"
 
 namespace hint {
+
+// The kernels' view of their shape arguments (hint_wl_shape.hpp): the dynamic policy - no type in the kernels' trailing
+// parameter pack - hands the kernel arguments through; WlStatic<ID> overwrites every folded field of a copy with the table's
+// constant, so that index arithmetic, LDS offsets and trip counts that depend on nothing else are the compiler's.
+template <bool BWD, typename... S> struct WlPolicy {
+    static constexpr int shape = -1;
+    static __device__ __forceinline__ const KArgs& kargs(const KArgs& a) { return a; }
+    static __device__ __forceinline__ const WlArgs& wlargs(const WlArgs& w) { return w; }
+};
+template <bool BWD, int ID> struct WlPolicy<BWD, WlStatic<ID>> {
+    static constexpr int shape = ID;
+    static constexpr WlFold F = BWD ? WL_SHAPES[ID].bwd : WL_SHAPES[ID].fwd;
+    static __device__ __forceinline__ KArgs kargs(const KArgs& a) {
+        KArgs r = a;
+#define X(n) r.n = F.a_##n;
+        HINT_WL_FOLD_K(X)
+#undef X
+        return r;
+    }
+    static __device__ __forceinline__ WlArgs wlargs(const WlArgs&) {
+        WlArgs r{};
+#define Y(n) r.n = F.w_##n;
+        HINT_WL_FOLD_W(Y)
+#undef Y
+        return r;
+    }
+};
 
 __device__ __forceinline__ f32x4 fma4(const f32x4 w, float s, const f32x4 a) {
     return f32x4{fmaf(w.x, s, a.x), fmaf(w.y, s, a.y), fmaf(w.z, s, a.z), fmaf(w.w, s, a.w)};

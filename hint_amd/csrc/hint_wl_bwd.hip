@@ -41,13 +41,17 @@ __device__ __forceinline__ void wl_level_commit(const WlLevel& p, float* xs, flo
     }
 }
 
-template <int NR, bool CH>        // (CH: chained launch or single block - hint_wl_fwd.hip)
+template <int NR, bool CH, typename... S>        // (CH: chained launch or single block; S: the shape policy - hint_wl_fwd.hip)
 __global__ __launch_bounds__(64 * MAX_NW) __attribute__((amdgpu_waves_per_eu(2, 2))) void hint_wl_bwd_kernel(
-    KArgs a, WlArgs w, ChainBlock one, const ChainBlock* __restrict__ chain, int n_chain,
+    KArgs a_in, WlArgs w_in, ChainBlock one, const ChainBlock* __restrict__ chain, int n_chain,
     const float* __restrict__ x, const float* __restrict__ g_z, const float* __restrict__ g_J,
     float* __restrict__ g_x, float gz_scale, float gJ_const) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    const int tid = threadIdx.x, nthreads = blockDim.x;
+    using Shape = WlPolicy<true, S...>;
+    static_assert(Shape::shape < 0 || (CH && NR == WL_SHAPES[Shape::shape < 0 ? 0 : Shape::shape].bwd.w_nr), "static instances: the chained backward of the shape's row-tile count");
+    const auto& a = Shape::kargs(a_in);
+    const auto& w = Shape::wlargs(w_in);
+    const int tid = threadIdx.x, nthreads = Shape::shape < 0 ? (int)blockDim.x : 64 * a.nw;
     const int lane = tid & 63;
     const int wave = rfl(tid >> 6);
     const float inv_d = frcp(a.d);
@@ -345,14 +349,22 @@ hipError_t launch_wl_bwd(const RowLaunch& L, const BlockSet& bs, const BwdIO& io
 #define HINT_LAUNCH(NRV, CHV)                                                                                        \
     hipLaunchKernelGGL((hint_wl_bwd_kernel<NRV, CHV>), dim3(L.grid), dim3(64 * L.a.nw), L.lds, stream, L.a, L.w, *bs.one, bs.chain, bs.n_chain, \
                        io.x, io.g_z, io.g_J, io.g_x, io.gz_scale, io.gJ_const)
-    if (L.w.nr == 2) { if (bs.chain != nullptr) HINT_LAUNCH(2, true); else HINT_LAUNCH(2, false); }
+    // the shape-specialised instances (hint_wl_shape.hpp; L.shape: every folded field compared by row_launch): chained launches only
+#define HINT_LAUNCH_S(ID, NRV)                                                                                       \
+    hipLaunchKernelGGL((hint_wl_bwd_kernel<NRV, true, WlStatic<ID>>), dim3(L.grid), dim3(64 * L.a.nw), L.lds, stream, L.a, L.w, *bs.one, bs.chain, \
+                       bs.n_chain, io.x, io.g_z, io.g_J, io.g_x, io.gz_scale, io.gJ_const)
+    if (bs.chain != nullptr && L.shape >= 0) { if (L.shape == 0) HINT_LAUNCH_S(0, 1); else HINT_LAUNCH_S(1, 2); }
+    else if (L.w.nr == 2) { if (bs.chain != nullptr) HINT_LAUNCH(2, true); else HINT_LAUNCH(2, false); }
     else { if (bs.chain != nullptr) HINT_LAUNCH(1, true); else HINT_LAUNCH(1, false); }
+#undef HINT_LAUNCH_S
 #undef HINT_LAUNCH
     return hipGetLastError();
 }
+static_assert(WL_N_SHAPES == 2, "one instance per entry of WL_SHAPES: launch_wl_bwd, set_max_lds_wl_bwd");
 
 hipError_t set_max_lds_wl_bwd(int bytes) {
-    const void* fns[4] = {(const void*)hint_wl_bwd_kernel<1, true>, (const void*)hint_wl_bwd_kernel<2, true>,
+    const void* fns[6] = {(const void*)hint_wl_bwd_kernel<1, true, WlStatic<0>>, (const void*)hint_wl_bwd_kernel<2, true, WlStatic<1>>,
+                          (const void*)hint_wl_bwd_kernel<1, true>, (const void*)hint_wl_bwd_kernel<2, true>,
                           (const void*)hint_wl_bwd_kernel<1, false>, (const void*)hint_wl_bwd_kernel<2, false>};
     for (const void* f : fns) {
         hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);

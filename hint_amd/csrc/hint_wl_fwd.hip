@@ -17,14 +17,19 @@ using namespace hint;
 
 // CH: a chained launch (the blocks' pointers come from the device table `chain`) or a single block (`one`, by value): as one
 // kernel the select between the two kept the 18 scalar registers of `one` alive through every chained launch.
-template <bool REV, int NR, bool CH>
+// S: the shape policy (hint_wl.hpp WlPolicy) - none: every shape field is a kernel argument; WlStatic<ID>: constants of the instance
+template <bool REV, int NR, bool CH, typename... S>
 __global__ __launch_bounds__(64 * MAX_NW) __attribute__((amdgpu_waves_per_eu(2, 2))) void hint_wl_apply_kernel(
-    KArgs a, WlArgs w, ChainBlock one, const ChainBlock* __restrict__ chain, int n_chain,
+    KArgs a_in, WlArgs w_in, ChainBlock one, const ChainBlock* __restrict__ chain, int n_chain,
     const float* __restrict__ x, float* __restrict__ z, float* __restrict__ J, const float* __restrict__ J_in,
     float* __restrict__ loss_acc, float noise, const unsigned long long* __restrict__ rng_state,
     float* __restrict__ x_noisy) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    const int tid = threadIdx.x, nthreads = blockDim.x;
+    using Shape = WlPolicy<false, S...>;
+    static_assert(Shape::shape < 0 || (!REV && CH && NR == WL_SHAPES[Shape::shape < 0 ? 0 : Shape::shape].fwd.w_nr), "static instances: the chained training forward of the shape's row-tile count");
+    const auto& a = Shape::kargs(a_in);
+    const auto& w = Shape::wlargs(w_in);
+    const int tid = threadIdx.x, nthreads = Shape::shape < 0 ? (int)blockDim.x : 64 * a.nw;
     const int lane = tid & 63, m = lane & 15, kq = lane >> 4;
     const int wave = rfl(tid >> 6);
     const float inv_d = frcp(a.d);
@@ -312,15 +317,26 @@ hipError_t launch_wl_apply(bool rev, const RowLaunch& L, const BlockSet& bs, con
                        bs.n_chain, io.x, io.z, io.J, io.J_in, LOSS, NOISE, RNG, XN)
 #define HINT_LAUNCH_CH(REV, NRV, LOSS, NOISE, RNG, XN)                                                               \
     { if (bs.chain != nullptr) HINT_LAUNCH(REV, NRV, true, LOSS, NOISE, RNG, XN); else HINT_LAUNCH(REV, NRV, false, LOSS, NOISE, RNG, XN); }
+    // the shape-specialised instances (hint_wl_shape.hpp; L.shape: every folded field compared by row_launch): chained training forward only
+#define HINT_LAUNCH_S(ID, NRV)                                                                                       \
+    hipLaunchKernelGGL((hint_wl_apply_kernel<false, NRV, true, WlStatic<ID>>), dim3(L.grid), dim3(64 * L.a.nw), L.lds, stream, L.a, L.w, *bs.one, \
+                       bs.chain, bs.n_chain, io.x, io.z, io.J, io.J_in, io.loss_acc, io.noise, io.rng_state, io.x_noisy)
+    if (!rev && bs.chain != nullptr && L.shape >= 0) {
+        if (L.shape == 0) HINT_LAUNCH_S(0, 1); else HINT_LAUNCH_S(1, 2);
+        return hipGetLastError();
+    }
     if (rev) { if (L.w.nr == 2) HINT_LAUNCH_CH(true, 2, no_f, 0.f, no_rng, no_f) else HINT_LAUNCH_CH(true, 1, no_f, 0.f, no_rng, no_f) }
     else { if (L.w.nr == 2) HINT_LAUNCH_CH(false, 2, io.loss_acc, io.noise, io.rng_state, io.x_noisy) else HINT_LAUNCH_CH(false, 1, io.loss_acc, io.noise, io.rng_state, io.x_noisy) }
+#undef HINT_LAUNCH_S
 #undef HINT_LAUNCH_CH
 #undef HINT_LAUNCH
     return hipGetLastError();
 }
+static_assert(WL_N_SHAPES == 2, "one instance pair per entry of WL_SHAPES: launch_wl_apply, set_max_lds_wl_apply");
 
 hipError_t set_max_lds_wl_apply(int bytes) {
-    const void* fns[8] = {(const void*)hint_wl_apply_kernel<false, 1, true>, (const void*)hint_wl_apply_kernel<true, 1, true>,
+    const void* fns[10] = {(const void*)hint_wl_apply_kernel<false, 1, true, WlStatic<0>>, (const void*)hint_wl_apply_kernel<false, 2, true, WlStatic<1>>,
+                          (const void*)hint_wl_apply_kernel<false, 1, true>, (const void*)hint_wl_apply_kernel<true, 1, true>,
                           (const void*)hint_wl_apply_kernel<false, 2, true>, (const void*)hint_wl_apply_kernel<true, 2, true>,
                           (const void*)hint_wl_apply_kernel<false, 1, false>, (const void*)hint_wl_apply_kernel<true, 1, false>,
                           (const void*)hint_wl_apply_kernel<false, 2, false>, (const void*)hint_wl_apply_kernel<true, 2, false>};

@@ -149,6 +149,16 @@ int hint_plan_paths(const hint_plan* plan, int32_t B, int32_t* out, int32_t n_ou
 /* The same for a host-only plan (as hint_plan_check builds it: no device needed) on a device of num_cu CUs. */
 int hint_plan_check_paths(const hint_node_desc* nodes, int32_t n_nodes, int32_t d, int32_t dc, float clamp, int32_t B,
                           int32_t num_cu, int32_t* out, int32_t n_out);
+/* Host-only as well: the shape-specialised instances of the wave-local row kernels (hint_amd/csrc/hint_wl_shape.hpp).  For a
+ * CHAINED training launch (backward = 0: forward, 1: backward part A) of B >= 1 rows on a device of num_cu CUs, with
+ * (with_perm = 1) or without fixed permutations between the blocks, returns
+ *   field -1: the entry of the shape table whose instance the launch takes (every folded field equal), or -1: the dynamic instance
+ *   field 0 .. HINT_WL_FOLD_FIELDS - 1: the launch's own folded field of that index, in the order of that header's field lists
+ *             (tools/wl_shape_table.py prints the table from them).
+ * A plan that does not run on the wave-local kernels reports -1 and zeros.  INT64_MIN (and hint_last_error) on bad arguments. */
+#define HINT_WL_FOLD_FIELDS 36
+int64_t hint_plan_check_wl_shape(const hint_node_desc* nodes, int32_t n_nodes, int32_t d, int32_t dc, float clamp, int32_t B,
+                                 int32_t num_cu, int32_t backward, int32_t with_perm, int32_t field);
 /* Host-only as well: one 64-bit digest per table the planner emits, first for the plan, then for its 4-wavefront variant (zeros
  * when there is none).  Per plan HINT_PLAN_DIGESTS values: meta blob, slot table, thin records, row records, bias map, real-element
  * map, weight-gradient jobs, first-layer-gradient map, pack segments, pack tiles, unit_w23, the plan's scalar fields.  Writes the
@@ -954,12 +964,14 @@ const char* hint_build_info(void);
  * phases later into an LDS sink nobody reads (an L2 warm-up; on unless the environment says HINT_PF=0 when the library
  * first launches): hint_debug_set_prefetch(0 / 1) switches it for the launches that follow and returns the previous
  * setting - a launch already captured in a hipGraph keeps what it was captured with.  hint_debug_last_lds_bytes(backward)
- * = dynamic LDS bytes of the process's last forward / inverse (0) or backward part-A (1) launch. */
+ * = dynamic LDS bytes of the process's last forward / inverse (0) or backward part-A (1) launch; hint_debug_last_wl_shape(backward)
+ * = the shape-table entry whose specialised instance that launch ran on, or -1 (a dynamic instance; HINT_WL_STATIC=0). */
 int hint_debug_set_prefetch(int on);
 /* The library reads its HINT_* environment variables once (the list: INTEGRATION.md); this re-reads them - for tests and A/B tools
  * that change the environment inside one process.  Plans already built keep what they were built with. */
 int hint_debug_reload_knobs(void);
 int32_t hint_debug_last_lds_bytes(int32_t backward);
+int32_t hint_debug_last_wl_shape(int32_t backward);
 
 #ifdef __cplusplus
 }

@@ -22,5 +22,6 @@ from .curves import fit_lens_shapes, lens_fit_grad, lens_fit_starts  # noqa: F40
 from .curves import fit_plus_shapes, plus_dominant_angle, plus_fit_grad, plus_fit_starts  # noqa: F401,E402
 from .curves import (lens_iou_dice, lens_shape_scores, plus_iou_dice, plus_shape_scores,  # noqa: F401,E402
                      polygon_overlap)
+from .shapes import fourier_coeffs, lens_draws, lens_rings, sample_lens_joint, sample_lens_prior  # noqa: F401,E402
 
 __version__ = "0.1.0"

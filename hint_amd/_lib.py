@@ -100,6 +100,20 @@ class CorrDesc(C.Structure):
                 ("out", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
 
 
+class LensGenDesc(C.Structure):
+    """mirror of `hint_lensgen_desc` (include/hint_amd.h)"""
+    _fields_ = [("n_rows", C.c_int64), ("seed", C.c_uint64), ("offset", C.c_uint64), ("draws", C.c_void_p), ("x", C.c_void_p),
+                ("ring", C.c_void_p), ("counts", C.c_void_p), ("eps", C.c_void_p), ("draws_out", C.c_void_p),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("max_groups", C.c_int32)]
+
+
+class FcoefDesc(C.Structure):
+    """mirror of `hint_fcoef_desc` (include/hint_amd.h)"""
+    _fields_ = [("points", C.c_void_p), ("counts", C.c_void_p), ("n_rows", C.c_int64), ("p_max", C.c_int32),
+                ("n_coeffs", C.c_int32), ("x", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+                ("max_groups", C.c_int32)]
+
+
 _lib = None
 
 _PROTOS = {
@@ -202,6 +216,10 @@ _PROTOS = {
     "hint_corr_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "hint_corr_run": (C.c_int, [C.POINTER(CorrDesc), C.c_void_p]),
     "hint_corr_job": (C.c_int64, [C.c_int32, C.c_int32, C.c_int64, C.c_int32]),
+    "hint_lensgen_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "hint_lensgen_run": (C.c_int, [C.POINTER(LensGenDesc), C.c_void_p]),
+    "hint_fcoef_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32]),
+    "hint_fcoef_run": (C.c_int, [C.POINTER(FcoefDesc), C.c_void_p]),
 }
 
 

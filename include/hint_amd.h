@@ -952,6 +952,80 @@ size_t hint_corr_workspace_bytes(int32_t n, int32_t d);
 int hint_corr_run(const hint_corr_desc* desc, void* stream);
 int64_t hint_corr_job(int32_t n, int32_t d, int64_t j, int32_t field);
 
+/* The lens-shape prior sampler: what feeds the evaluation pipeline (data.py:85-125 LensShapeModel.generate_lens_shape, sample_prior
+ * and sample_joint - one polygon-library intersection and one DFT per row in a Python loop; rejection_sampling.py:76-85
+ * prepare_samples runs it for 1e8 prior rows, data.py:466-489 prepare_data_loaders for the training and test sets).  A row has four
+ * draws, u_r, u_t in [0, 1] and n_x, n_y standard normal:
+ *   r0 = 1 + u_r, r1 = 2 r0, theta = 2 pi u_t, c1 = 0.8 (r0 + r1) (sin theta, cos theta)                          (data.py:87-93)
+ *   A_j = r0 e_j, B_j = c1 + r1 e_j, e_j = (cos(2 pi j / 64), -sin(2 pi j / 64)), j = 0..63: the two clockwise 64-gons a
+ *         default-resolution buffer() of a point stands for
+ *   ring  = P, the A_j strictly inside B in A's clockwise order (one cyclic run), Q, the B_j strictly inside A in B's clockwise
+ *         order, P again: the closed clockwise ring of A n B.  P and Q are the two edge-edge crossings, P the one where the
+ *         boundary passes onto A.  THE ORDER OF THE RING'S VERTICES IS THIS LIBRARY'S DEFINITION: the reference takes whatever its
+ *         polygon library returns, and that library is not available to pin it.  The closed ring has 31 or 32 points (the count
+ *         depends on theta alone: 90.5 % / 9.5 %); the closing point stays in (data.py:98).
+ *   ring -= mean(closed ring) + 0.5 (n_x, n_y)                                                                     (data.py:99)
+ *   x     = the 20 floats flatten_coeffs(fourier_coeffs(ring, 5)) (data.py:30-33, :42-49), as hint_fcoef_desc states them
+ * all in fp32: sin and cos of theta by sincospi(2 u_t); the figure is built at r0 = 1 and a centred point is
+ * fma(r0, p - mean, -n / 2); the sums run in ring order.  tests/shapegen_oracle.py derives the distance to the exact value: at
+ * most 153 u A per ring point and 187 u A per coefficient, u = 2^-24, A the row's largest centred coordinate magnitude; rows in
+ * which a vertex lies within 2^-19 r0 of the other polygon's boundary may differ from the exact count by a vertex.
+ * Draws: `draws` [n_rows, 4] = (u_r, u_t, n_x, n_y) as given, or (draws NULL) Philox4x32-10 with counter = {row lo, row hi, stream,
+ * 0x4C454E53}, key = {seed lo, seed hi}, row = offset + i.  Stream 0: u_r = (float)c0 2^-32, u_t = (float)c1 2^-32, (n_x, n_y) = one
+ * Box-Muller pair (r cos, r sin) of (min(((float)c2 + 1) 2^-32, 1), (float)c3 2^-32).  Stream 1: eps, the pair of (c0, c1): the
+ * observation noise sample_joint adds.  A row depends on (seed, offset + i) only: a run cut into chunks at any boundaries gives
+ * the bits of one call, and two runs agree bit for bit.  draws_out receives the draws used (either source).
+ * A row whose u_r or u_t is outside [0, 1], or one of whose draws is not finite, is REJECTED: x = NaN, count 0, ring 0; it
+ * disturbs no other row.  The workspace is int32[workspace_bytes / 4]: every word is written by a run and their sum is the
+ * number of rejected rows (0 for every Philox run).
+ *   run              stream-ordered on the current device: one launch, no host synchronisation, no allocation (capturable).
+ *                    max_groups: 0 = the default grid, otherwise the workgroups at most.  Rejects, before any device call and
+ *                    naming the field: a null desc, x or workspace; n_rows outside 1..2^30; offset + n_rows above 2^64 - 1;
+ *                    max_groups < 0; draws, x, draws_out or workspace not 16-byte, ring or eps not 8-byte, counts not 4-byte
+ *                    aligned; a workspace smaller than workspace_bytes says.
+ *   workspace_bytes  0 (and an error message) for an n_rows run would reject.  Never decreases with n_rows; at most 32 KiB. */
+typedef struct hint_lensgen_desc {
+    int64_t n_rows;
+    uint64_t seed, offset;
+    const float* draws;                    /* NULL (Philox), or device float[n_rows, 4], 16-byte aligned */
+    float* x;                              /* device float[n_rows, 20], 16-byte aligned */
+    float* ring;                           /* NULL, or device float[n_rows, 32, 2]: the closed ring, centred, zero-padded */
+    int32_t* counts;                       /* NULL, or device int32[n_rows]: points of the closed ring, 31 or 32 */
+    float* eps;                            /* NULL, or device float[n_rows, 2] */
+    float* draws_out;                      /* NULL, or device float[n_rows, 4], 16-byte aligned */
+    void* workspace; size_t workspace_bytes;      /* 16-byte aligned */
+    int32_t max_groups;
+} hint_lensgen_desc;
+size_t hint_lensgen_workspace_bytes(int64_t n_rows);
+int hint_lensgen_run(const hint_lensgen_desc* desc, void* stream);
+
+/* Points to Fourier coefficients (data.py:42-49 fourier_coeffs and :30-33 flatten_coeffs): the opposite direction of the traced
+ * curves above.  For points [n_rows, p_max, 2], of which row i counts its first N = counts[i] (all p_max without counts), and
+ * K = n_coeffs odd:
+ *   a[c, m] = (1 / N) sum_n p[n, c] exp(-2 pi i m n / N), m = -K/2 .. K/2;  x[i] = [Re a[0, :], Re a[1, :], Im a[0, :], Im a[1, :]]
+ * in fp32: for each |m| and axis, C = sum p cos(phi_n) and S = sum p sin(phi_n), phi_n = 2 pi ((|m| n) mod N) / N - the angle
+ * reduced in integers, each twiddle the true value rounded once (sincospi in double) - fused multiply-adds onto the sum, n
+ * ascending; Re a[+-m] = C / N, Im a[m] = -S / N, Im a[-m] = S / N.  Within (N + 2) u A of the exact value, A the row's largest
+ * coordinate magnitude.  K <= N <= p_max is required of every row, so the reference's M = min(N // 2, M) never binds and the
+ * output's width never depends on a row; a row with another count is REJECTED (x = NaN) and counted in the workspace as
+ * hint_lensgen_desc's rows are.
+ *   run              one launch, stream-ordered, capturable.  Rejects, before any device call and naming the field: a null desc,
+ *                    points, x or workspace; n_rows outside 1..2^24; n_coeffs even or outside 1..25; p_max outside n_coeffs..1024;
+ *                    max_groups < 0; points not 8-byte, counts or x not 4-byte, workspace not 16-byte aligned; a workspace
+ *                    smaller than workspace_bytes says.
+ *   workspace_bytes  0 (and an error message) for sizes run would reject.  Never decreases with n_rows; at most 128 KiB. */
+typedef struct hint_fcoef_desc {
+    const float* points;                   /* device float[n_rows, p_max, 2], 8-byte aligned */
+    const int32_t* counts;                 /* NULL, or device int32[n_rows] */
+    int64_t n_rows;
+    int32_t p_max, n_coeffs;
+    float* x;                              /* device float[n_rows, 4 n_coeffs] */
+    void* workspace; size_t workspace_bytes;      /* 16-byte aligned */
+    int32_t max_groups;
+} hint_fcoef_desc;
+size_t hint_fcoef_workspace_bytes(int64_t n_rows, int32_t p_max, int32_t n_coeffs);
+int hint_fcoef_run(const hint_fcoef_desc* desc, void* stream);
+
 int hint_abi_version(void);
 const char* hint_last_error(void);
 /* what the library binary was built with and runs with: "libhint_amd abi N, gfx950, HIP x.y.z, clang ..., src <12 hex digits: hash

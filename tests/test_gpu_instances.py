@@ -67,18 +67,23 @@ def inputs(case, B, seed=11):
     return x, c, zi, gz, gJ
 
 
-def oracle_block(case, B):
-    """float64 oracle of one block: parameters (float32), inputs, kept-row mask, and every reference quantity"""
-    dims_c = [(case.dc,)] if case.dc else []
-    nodes = orc.build_nodes(case.d, dims_c, list(case.widths))
+def block_params(case):
+    """(the tree's node table, its float32 parameters) of a block case"""
+    nodes = orc.build_nodes(case.d, [(case.dc,)] if case.dc else [], list(case.widths))
     P = orc.init_params(nodes, seed=5, scale=case.scale)
     if case.big_s:
         P = big_s(P, case.big_s)
-    x, c, zi, gz, gJ = inputs(case, B)
+    return nodes, P
+
+
+def oracle_block_rows(case, nodes, P, rows):
+    """float64 oracle of one block on explicit rows = (x, c, zi, gz, gJ) (float32, on the host): the kept-row mask, the largest |s|,
+    the cotangents as used (zero on rows next to a kink) and every reference quantity"""
+    x, c, zi, gz, gJ = rows
     P64 = {k: v.double().requires_grad_(True) for k, v in P.items()}
     x64 = x.double().requires_grad_(True)
     c64 = [c.double().requires_grad_(True)] if case.dc else []
-    with Spy(B) as spy:
+    with Spy(x.shape[0]) as spy:
         z64, J64 = orc.block_apply(nodes, P64, x64, c64, rev=False)
     keep = spy.kink > KINK
     gz, gJ = gz * keep[:, None], gJ * keep
@@ -88,7 +93,14 @@ def oracle_block(case, B):
                                      [t.detach() for t in c64], rev=True)
     ref = dict(z=z64.detach(), J=J64.detach(), xi=xi64, Ji=Ji64, gx=x64.grad, gc=c64[0].grad if case.dc else None,
                gw={k: v.grad for k, v in P64.items()})
-    return P, (x, c, zi, gz, gJ), keep, spy.s_max, ref
+    return (x, c, zi, gz, gJ), keep, spy.s_max, ref
+
+
+def oracle_block(case, B):
+    """float64 oracle of one block: parameters (float32), inputs, kept-row mask, and every reference quantity"""
+    nodes, P = block_params(case)
+    rows, keep, s_max, ref = oracle_block_rows(case, nodes, P, inputs(case, B))
+    return P, rows, keep, s_max, ref
 
 
 def make_chain_pair(case):

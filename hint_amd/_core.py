@@ -136,7 +136,8 @@ class TrainerCore:
     @lr.setter
     def lr(self, value: float):          # learning-rate schedules (train_unconditional.py:191-199) need no re-capture:
         self._lr = float(value)
-        self.opt_state[0] = self._lr     # the captured optimizer launches read it on the device
+        self.opt_state[0:1].fill_(self._lr)     # the captured optimizer launches read it on the device (fill_: no host copy, so a
+                                                # schedule that sets it every step never waits for the stream)
 
     def last_losses(self):
         """the two loss terms (0.5 |z|^2 mean = -log p(z), -log|det J| mean) of the most recent step's local shard as device

@@ -212,7 +212,7 @@ class _PosteriorSampler:
         # the fused route needs one plan for every hac_x block and ExternalAffineCouplings without node permutations of their own
         self.fusable = all(e.shape_key == self.hx[0].shape_key for e in self.hx) and all(e.total_perm() is None for e in self.ex)
         self._pack_group = PackGroup(self.engines, device)
-        self._chains = {}            # (B, per_row) -> (handle, key, coef, perms)
+        self._chains = {}            # (B, per_row, stream) -> (handle, key, coef, perms): coef is scratch of one stream-ordered call
 
     def __del__(self):
         try:
@@ -245,13 +245,14 @@ class _PosteriorSampler:
                 flow.perm_x[i].W = flow.perm_x[i].W.contiguous()
         perms = [e.compose_perm(flow.perm_x[i].W if i > 0 else None) for i, e in enumerate(self.hx)]
         key = tuple((e.arena.data_ptr(), e.packed.data_ptr()) for e in self.hx) + tuple(p.data_ptr() if p is not None else 0 for p in perms)
-        have = self._chains.get((B, per_row))
+        skey = (B, per_row, torch.cuda.current_stream(self.device).cuda_stream)     # (as hint.py and flow.py key their pools)
+        have = self._chains.get(skey)
         if have is not None and have[1] == key:
             return have[0], have[2]
         torch.cuda.synchronize(self.device)             # (a launch on a stale chain's device table may still be queued)
         if have is not None:
             self.lib.hint_chain_destroy(have[0])
-            del self._chains[(B, per_row)]
+            del self._chains[skey]
         elif len(self._chains) >= 8:                    # ragged batch sizes: forget the older ones
             for k in list(self._chains):
                 self.lib.hint_chain_destroy(self._chains[k][0])
@@ -273,7 +274,7 @@ class _PosteriorSampler:
             except Exception:
                 self.lib.hint_chain_destroy(handle)
                 raise
-        self._chains[(B, per_row)] = (handle, key, coef, perms)
+        self._chains[skey] = (handle, key, coef, perms)
         return handle, coef
 
     def _y_lane(self, y: torch.Tensor):
@@ -698,7 +699,9 @@ class ConditionalFlowTrainer(TrainerCore):
             self._adam_dev(scale)
         else:
             self._adam_host(scale)
-            self.rng_state[1] = self.step_count          # keep the device counter in step for a later capture
+            # keep the device counter in step for a later capture.  (fill_: a launch with the value as its argument.  `rng_state[1] = n`
+            #  is a copy from pageable host memory, which blocks the host until the stream has run dry)
+            self.rng_state[1:2].fill_(self.step_count)
 
     def _iteration_legacy(self, x: torch.Tensor, y: torch.Tensor, on_device_adam: bool):
         """Round 4's iteration (HINT_COND_LEGACY=1; kept for A/B runs): both lanes forward and backward as direct launches.  What FrEIA's graph does between the couplings is folded

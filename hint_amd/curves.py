@@ -828,6 +828,18 @@ def _check_angle(angle, n_rows: int, device, who: str) -> torch.Tensor:
     return angle
 
 
+_PLUS_SHIFTS = {}            # device -> PLUS_STARTS as a [9, 2] tensor there
+
+
+def _plus_start_shifts(device) -> torch.Tensor:
+    """PLUS_STARTS on the device, uploaded once: torch.tensor(list, device=...) copies from pageable host memory, which blocks
+    the host until the current stream has run dry - once per device, not once per call"""
+    t = _PLUS_SHIFTS.get(device)
+    if t is None:
+        t = _PLUS_SHIFTS[device] = torch.tensor(PLUS_STARTS, dtype=torch.float32, device=device)
+    return t
+
+
 def plus_fit_starts(curve: torch.Tensor, angle: Optional[torch.Tensor] = None) -> torch.Tensor:
     """[N, 9, 9] fp32: the nine starts of the reference's fit_plus_shape_to_points for every row, computed on the device -
     init_plus_params for the nine (xshift, yshift) of its list, in its order: lengths 5, widths 2, the offsets at the mean of the
@@ -840,7 +852,7 @@ def plus_fit_starts(curve: torch.Tensor, angle: Optional[torch.Tensor] = None) -
     out = torch.empty(n, len(PLUS_STARTS), PLUS_PARAMS, dtype=torch.float32, device=curve.device)
     out[:, :, 0:2] = 5.0
     out[:, :, 2:4] = 2.0
-    out[:, :, 4:6] = torch.tensor(PLUS_STARTS, dtype=torch.float32, device=curve.device)[None]
+    out[:, :, 4:6] = _plus_start_shifts(curve.device)[None]
     out[:, :, 6:8] = centre[:, None, :]
     out[:, :, 8] = angle[:, None]
     return out

@@ -273,15 +273,20 @@ static RowLaunch row_launch(const Dispatch& D, int B, bool backward, const Block
         L.w = (backward ? P->wl_b : P->wl_f)[D.nr - 1];
         L.w.off_perm = L.a.perm_lds;
         // the shape-specialised instances exist for chained launches only (the training forward and the backward)
-        if (knobs().wl_static && bs.chain != nullptr) L.shape = wl_shape_match(L.a, L.w, backward);
+        // (and only for a plan whose level schedule - every row record of every group walked by the planner - is the entry's)
+        if (knobs().wl_static && bs.chain != nullptr) L.shape = wl_shape_match(L.a, L.w, backward ? P->wl_sb : P->wl_sf, backward);
     }
     return L;
 }
 
 // what hint_plan_check_wl_shape reads: the table entry a chained training launch of the variant for B would take, then the
 // launch's own folded fields in list order (what tools/wl_shape_table.py prints the table from)
-int wl_shape_out(const hint_plan* P, int B, bool backward, bool with_perm, int32_t* out, int32_t n_out) {
+int wl_shape_out(const hint_plan* P, int B, bool backward, bool with_perm, int32_t* out, int32_t n_out, int32_t* sched) {
     const Dispatch D = dispatch(P, B);
+    if (sched != nullptr) {
+        const WlSched zero{};
+        std::memcpy(sched, D.P->wl ? (backward ? &D.P->wl_sb : &D.P->wl_sf) : &zero, sizeof(WlSched));
+    }
     if (!D.P->wl) {                  // (the general kernels: no entry, no fields)
         for (int i = 0; i < n_out && i < 1 + WL_FOLD_FIELDS; ++i) out[i] = i == 0 ? -1 : 0;
         return 0;

@@ -176,6 +176,7 @@ struct hint_plan {
     // wave-local plans (hint_wl.hpp): narrow trees run on hint_wl_apply_kernel / hint_wl_bwd_kernel
     int wl = 0, wl_nr2 = 0;     // wl_nr2: two 16-row tiles per workgroup on one weight stream fit the LDS as well
     WlArgs wl_f[2]{}, wl_b[2]{};  // [nr - 1]
+    WlSched wl_sf{}, wl_sb{};   // the level schedule of either direction (hint_wl_shape.hpp; derived from the digested tables alone: hint_plan.cpp wl_sched_of)
     // subtree groups (hint_sub.hpp): the deepest n_sub groups run one subtree per wavefront
     int n_sub = 0, sub_pf = 0, sub_pb = 0, sub_pbias = 0, sub_bsrc = 0, sub_cols = 0;
     int sub_slab_f = 0, sub_slab_b = 0;                 // floats of their slabs
@@ -259,7 +260,7 @@ struct Dispatch {
 Dispatch dispatch(const hint_plan* P, int B, int n_chain = 1);
 int dispatch_out(const hint_plan* P, int B, int32_t* out, int32_t n_out);     // (the exports' layout: include/hint_amd.h)
 int paths_out(const hint_plan* P, int B, int32_t* out, int32_t n_out);        // (hint_plan_paths / hint_plan_check_paths)
-int wl_shape_out(const hint_plan* P, int B, bool backward, bool with_perm, int32_t* out, int32_t n_out);   // (hint_plan_check_wl_shape)
+int wl_shape_out(const hint_plan* P, int B, bool backward, bool with_perm, int32_t* out, int32_t n_out, int32_t* sched = nullptr);   // (hint_plan_check_wl_shape; sched: WL_SCHED_FIELDS)
 void split_workspace(const hint_plan* P, int B, void* workspace, ChainBlock* b);
 void bind_tape(const hint_plan* P, int B, float* tape, ChainBlock* b);
 // forward (rev: inverse) of the blocks of `bs` on B rows: the one place that goes dispatch -> kernel arguments -> LDS size ->

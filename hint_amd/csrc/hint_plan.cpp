@@ -1055,6 +1055,44 @@ static void plan_launch_jobs(PlanBuild& b) {
 }
 
 // ---- stage 10: the tables as the device takes them ----
+// The level schedule of a wave-local plan (hint_wl_shape.hpp WlSched): per group what its entries, its boundary and EVERY one of
+// its row records, units and coupling entries agree on.  A field on which two of them differ is -1: the launch site then takes
+// no shape-specialised instance (and tools/wl_shape_table.py refuses to print such an entry).
+static WlSched wl_sched_of(const PlanBuild& b, bool backward) {
+    const hint_plan* P = b.P.get();
+    WlSched s{};
+    if ((int)b.groups.size() > WL_MAX_G) { s.tail_slots = -1; return s; }
+    auto uni = [](int32_t& field, int v, bool first) { if (first) field = v; else if (field != v) field = -1; };
+    for (size_t gi = 0; gi < b.groups.size(); ++gi) {
+        const Group& g = b.groups[gi];
+        WlGroupK& k = s.g[gi];
+        k.ent_begin = g.ent_begin; k.ent_cnt = g.ent_cnt; k.level = g.level; k.level_last = g.level_last;
+        k.slots = b.rng[P->lop_cnt + gi];
+        bool first = true;
+        for (int ui = g.unit_begin; ui < g.unit_end; ++ui, first = false) {
+            const Unit& u = b.units[ui];
+            uni(k.cin, u.cin, first); uni(k.hw, u.h, first); uni(k.sl, u.sl_n, first);
+            uni(k.kcp, u.cin < 4 ? 4 : 8, first);
+        }
+        if (first) k.cin = k.hw = k.sl = k.kcp = -1;
+        for (int e = g.ent_begin; e < g.ent_begin + g.ent_cnt; ++e)
+            if (b.ents[e].sl_ns != k.sl || b.ents[e].sl_nt != k.sl) k.sl = -1;
+        const int r0 = g.row_begin, r1 = r0 + b.rng[g.rng_begin + b.nw];
+        first = true;
+        for (int r = r0; r < r1; ++r, first = false) {
+            const RowRec& rec = backward ? b.recs_b[r] : b.recs_f[r];
+            const int n1 = rec.counts & 0xff, ntt = (rec.counts >> 24) & 0xff;
+            uni(k.n1, n1, first); uni(k.thin_K, rec.thin_k & 0xff, first);
+            k.ntt_min = first ? ntt : std::min(k.ntt_min, ntt);
+            k.ntt_max = first ? ntt : std::max(k.ntt_max, ntt);
+            if (backward && ((rec.p2 & 0xff) != k.cin || (rec.p2 >> 16) != k.hw)) k.cin = k.hw = k.kcp = -1;
+        }
+        if (first) k.n1 = k.thin_K = k.ntt_min = k.ntt_max = -1;     // (a group without rows: nothing to fold)
+    }
+    s.tail_slots = b.rng[P->lop_cnt + b.groups.size()];
+    return s;
+}
+
 static void finish_tables(PlanBuild& b) {
     hint_plan* P = b.P.get();
     // the meta blob staged in LDS by the kernels
@@ -1072,6 +1110,7 @@ static void finish_tables(PlanBuild& b) {
     b.thins.insert(b.thins.end(), b.thin_w.begin(), b.thin_w.end());
     b.recs = b.recs_f;                  // forward | backward
     b.recs.insert(b.recs.end(), b.recs_b.begin(), b.recs_b.end());
+    if (P->wl) { P->wl_sf = wl_sched_of(b, false); P->wl_sb = wl_sched_of(b, true); }
 }
 
 // ---- digests of everything the planner emits (hint_plan_check_digest; tests/test_plan_digest_cpu.py pins them) ----
@@ -1319,14 +1358,16 @@ int hint_plan_check_paths(const hint_node_desc* nodes, int32_t n_nodes, int32_t 
 
 int64_t hint_plan_check_wl_shape(const hint_node_desc* nodes, int32_t n_nodes, int32_t d, int32_t dc, float clamp, int32_t B,
                                  int32_t num_cu, int32_t backward, int32_t with_perm, int32_t field) {
-    if (B < 1 || num_cu < 1 || field < -1 || field >= HINT_WL_FOLD_FIELDS) { fail("hint_plan_check_wl_shape: bad arguments"); return INT64_MIN; }
+    const bool sched_field = field >= HINT_WL_SCHED_FIELD0 && field < HINT_WL_SCHED_FIELD0 + HINT_WL_SCHED_FIELDS;
+    if (B < 1 || num_cu < 1 || field < -1 || (field >= HINT_WL_FOLD_FIELDS && !sched_field)) { fail("hint_plan_check_wl_shape: bad arguments"); return INT64_MIN; }
     std::unique_ptr<hint_plan> P;
     if (host_plan(nodes, n_nodes, d, dc, clamp, &P)) return INT64_MIN;
     P->num_cu = num_cu;
     if (P->alt4) P->alt4->num_cu = num_cu;
-    int32_t v[1 + HINT_WL_FOLD_FIELDS];
-    wl_shape_out(P.get(), B, backward != 0, with_perm != 0, v, 1 + HINT_WL_FOLD_FIELDS);
-    return v[1 + field];
+    int32_t v[1 + HINT_WL_FOLD_FIELDS], sv[HINT_WL_SCHED_FIELDS];
+    static_assert(HINT_WL_SCHED_FIELDS == WL_SCHED_FIELDS, "include/hint_amd.h states the schedule's size");
+    wl_shape_out(P.get(), B, backward != 0, with_perm != 0, v, 1 + HINT_WL_FOLD_FIELDS, sv);
+    return sched_field ? sv[field - HINT_WL_SCHED_FIELD0] : v[1 + field];
 }
 
 int64_t hint_plan_check_wjob(const hint_node_desc* nodes, int32_t n_nodes, int32_t d, int32_t dc, float clamp, int32_t variant,

@@ -27,14 +27,23 @@ namespace hint {
 // The kernels' view of their shape arguments (hint_wl_shape.hpp): the dynamic policy - no type in the kernels' trailing
 // parameter pack - hands the kernel arguments through; WlStatic<ID> overwrites every folded field of a copy with the table's
 // constant, so that index arithmetic, LDS offsets and trip counts that depend on nothing else are the compiler's.
+// A group's schedule (hint_wl_shape.hpp WlSched) reaches the group loop and the row body as a VALUE: the shape-specialised
+// instances unroll their group loop over the shape's group list and index the constexpr schedule with the loop counter, so every
+// field is a literal once the loop is unrolled (SK = true: the code may rely on it); the dynamic instances pass SK = false and a
+// dummy, and read everything from the tables and the row records.
 template <bool BWD, typename... S> struct WlPolicy {
     static constexpr int shape = -1;
+    static constexpr int n_groups = 0;
+    static constexpr WlSched SC{};
     static __device__ __forceinline__ const KArgs& kargs(const KArgs& a) { return a; }
     static __device__ __forceinline__ const WlArgs& wlargs(const WlArgs& w) { return w; }
 };
 template <bool BWD, int ID> struct WlPolicy<BWD, WlStatic<ID>> {
     static constexpr int shape = ID;
     static constexpr WlFold F = BWD ? WL_SHAPES[ID].bwd : WL_SHAPES[ID].fwd;
+    static constexpr int n_groups = F.a_n_groups;
+    static constexpr WlSched SC = BWD ? WL_SHAPES[ID].sbwd : WL_SHAPES[ID].sfwd;
+    static_assert(n_groups >= 1 && n_groups <= WL_MAX_G && wl_sched_valid(SC, n_groups), "a folded schedule field is not uniform over its group (tools/wl_shape_table.py refuses such an entry)");
     static __device__ __forceinline__ KArgs kargs(const KArgs& a) {
         KArgs r = a;
 #define X(n) r.n = F.a_##n;
@@ -205,6 +214,17 @@ __device__ __forceinline__ RowU wl_rec_decode(const RecV& v) {
     for (int i = 0; i < 16; ++i) r[i] = __builtin_amdgcn_readlane(v.v, i);
     return decode_rec(r);
 }
+// a decoded record with the fields that every row of group G shares replaced by G's constants: their v_readlane, shifts and masks are dead
+template <int KIND, bool SK>
+__device__ __forceinline__ RowU wl_rec_fold(RowU u, const WlGroupK& gk) {
+    if constexpr (SK) {
+        u.n1 = gk.n1;
+        if (gk.ntt_min == gk.ntt_max) u.ntt = gk.ntt_min;
+        u.thin_k = (u.thin_k & ~0xff) | gk.thin_K;
+        if (KIND == K_BWD) u.p2 = (u.p2 & 0xff00) | gk.cin | (gk.hw << 16);
+    }
+    return u;
+}
 __device__ __forceinline__ void wl_stage_recs(LDS_AS int32_t* lrecs, const void* recs_dir, int total_rows, int tid, int nthreads) {
     const GLOBAL_AS i32x4* src = (const GLOBAL_AS i32x4*)recs_dir;
     for (int i = tid; i < 4 * total_rows; i += nthreads) ((LDS_AS i32x4*)lrecs)[i] = src[i];
@@ -218,10 +238,13 @@ __device__ __forceinline__ int wl_lane_get(int table, int e) { return __builtin_
 // ONE code path for every tile count: the ring always carries three tiles (a narrower row's last tile again: L1 hits) and
 // only the MFMA groups and the per-tile epilogues sit under (wave-uniform) branches - a path per tile count would define the
 // ring in three places, and the merge costs sixteen register copies behind a vmcnt(0) at the end of every row.
-template <int KIND, int NR>
+// SK: the group's schedule is known (ntt_lo .. ntt_hi: the tile counts of its rows, else 1 .. NTT).  A known group's rows have a literal
+// number of k-blocks - the pair loop's bound and the liveness of the last step - and only the MFMA groups of tile counts
+// ntt_lo .. ntt_hi exist; it is still ONE path per row.
+template <int KIND, int NR, bool SK = false>
 __device__ __forceinline__ void wl_row(const WlCtx& c, const RowU& cr, const RowU& nr, const GLOBAL_AS float* pkn,
                                        const GLOBAL_AS uint8_t* const (&bitsn)[2], f32x4 (&ring)[RING][NEL], f32x4 (&part)[NR],
-                                       const LaneOff& lo, int lane) {
+                                       const LaneOff& lo, int lane, int ntt_lo = 1, int ntt_hi = 3) {
     static_assert(KIND < 0 || (RING == 2 && NTT == 3), "the WL rows alternate two ring slots of three tiles");     // (checked where instantiated: the general kernels include this header for its helpers with NTT = 4)
     const int m = lane & 15, kq = lane >> 4;
     const int n1 = cr.n1, ntt = cr.ntt;
@@ -290,9 +313,9 @@ __device__ __forceinline__ void wl_row(const WlCtx& c, const RowU& cr, const Row
                 bq[S_ ^ 1][h] = q_frag(h);          /* k-block KB + 1 (behind the row's last one: never used) */ \
             }                                                                                           \
             q_load((KB) + 2);                                                                           \
-            if (ntt >= 3) {                                                                             \
+            if (!SK ? ntt >= 3 : (ntt_hi >= 3 && (ntt_lo >= 3 || ntt >= 3))) {                          \
                 _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_) { WL_MFMA(0) WL_MFMA(1) WL_MFMA(2) }    \
-            } else if (ntt == 2) {                                                                      \
+            } else if (!SK ? ntt == 2 : (ntt_hi >= 2 && (ntt_lo >= 2 || ntt == 2))) {                   \
                 _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_) { WL_MFMA(0) WL_MFMA(1) }               \
             } else {                                                                                    \
                 _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_) { WL_MFMA(0) }                          \
@@ -307,9 +330,18 @@ __device__ __forceinline__ void wl_row(const WlCtx& c, const RowU& cr, const Row
     // (an odd row pays one dummy step; a single last step that re-loads its own slot behind its MFMAs measured slower)
     const int n1p = (n1 + 1) & ~1;
     int k0 = 0;
-    for (; k0 + 2 < n1p; k0 += 2) {
-        WL_STEP(k0, 0, true, c.pk, c.bits, cr, k0 + 1, true)
-        WL_STEP(k0 + 1, 1, true, c.pk, c.bits, cr, k0 + 2, true)
+    if constexpr (SK) {
+        // (the bound is a literal; kept rolled: fully unrolled - two to four pairs - measured the same at cfg 2 and GAS, for 5-20 % more code)
+#pragma unroll 1
+        for (; k0 + 2 < n1p; k0 += 2) {
+            WL_STEP(k0, 0, true, c.pk, c.bits, cr, k0 + 1, true)
+            WL_STEP(k0 + 1, 1, true, c.pk, c.bits, cr, k0 + 2, true)
+        }
+    } else {
+        for (; k0 + 2 < n1p; k0 += 2) {
+            WL_STEP(k0, 0, true, c.pk, c.bits, cr, k0 + 1, true)
+            WL_STEP(k0 + 1, 1, true, c.pk, c.bits, cr, k0 + 2, true)
+        }
     }
     WL_STEP(k0, 0, true, c.pk, c.bits, cr, k0 + 1, true)              // (an odd row's step n1: a dummy load of the tile behind)
     WL_STEP(k0 + 1, 1, k0 + 1 < n1, pkn, bitsn, nr, 0, true)          // hands the ring to the next row
@@ -412,15 +444,16 @@ struct WlCarry {
     int held;        // the record `nrec` holds (index, or -1)
     RecV nrec;       // ... fetched two rows ahead, carried across groups and blocks
 };
-template <int KIND, int NR>
+// (SK, gk: the group's schedule; the record the last row hands over to may be another group's, so only the CURRENT row's is folded)
+template <int KIND, int NR, bool SK = false>
 __device__ __forceinline__ void wl_rows(const WlCtx& c, f32x4 (&ring)[RING][NEL], WlCarry& cy, int r0, int r1, int rnext,
-                                        bool other_block, int lane) {
+                                        bool other_block, int lane, const WlGroupK& gk = WlGroupK{}) {
     if (r0 >= r1) return;
     LaneOff lo;
     lo.w = (unsigned)lane * 16u; lo.b = (unsigned)(lane >> 4) * 16u; lo.l = (unsigned)lane;
     if (cy.held != r0) cy.nrec = wl_rec_fetch(c.lrecs, r0, lane);      // (only a wavefront's first rows of a launch, or behind a group it had no rows in)
     RowU cr = wl_rec_decode(cy.nrec);
-    if (cy.primed != r0) wl_load<KIND, NR>(ring[0], c.pk, c.bits, cr, 0, lo);
+    if (cy.primed != r0) wl_load<KIND, NR>(ring[0], c.pk, c.bits, wl_rec_fold<KIND, SK>(cr, gk), 0, lo);
     const int rlast = rnext >= 0 ? rnext : r1 - 1;
     cy.nrec = wl_rec_fetch(c.lrecs, r0 + 1 < r1 ? r0 + 1 : rlast, lane);
     f32x4 part[NR];
@@ -435,7 +468,7 @@ __device__ __forceinline__ void wl_rows(const WlCtx& c, f32x4 (&ring)[RING][NEL]
 #endif
         const GLOBAL_AS float* pkn = hand ? c.pk_next : c.pk;
         const GLOBAL_AS uint8_t* const bitsn[2] = {hand ? c.bits_next[0] : c.bits[0], hand ? c.bits_next[1] : c.bits[1]};
-        wl_row<KIND, NR>(c, cr, nr, pkn, bitsn, ring, part, lo, lane);
+        wl_row<KIND, NR, SK>(c, wl_rec_fold<KIND, SK>(cr, gk), nr, pkn, bitsn, ring, part, lo, lane, gk.ntt_min, gk.ntt_max);
         cr = nr;
     }
     cy.primed = rnext;

@@ -176,16 +176,27 @@ __global__ __launch_bounds__(64 * MAX_NW) __attribute__((amdgpu_waves_per_eu(2, 
             c.tw = blk.wsSlab + a.thin_slab_off + (size_t)blockIdx.x * a.tw_floats;
             c.xld = a.xld; c.gld = a.gld; c.WT = a.WT; c.slab_h = w.slab_floats; c.train = true; c.first_tile = tg == (int)blockIdx.x;
 
+            // (a shape-specialised instance unrolls the loop over its group list: gi and with it the step's schedule - level, slot count,
+            //  slabs per net of the group just finished, the rows' constants - are literals in every copy of the body; hint_wl.hpp)
+            constexpr bool SK = Shape::shape >= 0;
+            constexpr WlSched SCH = Shape::SC;
+#pragma unroll SK ? WL_MAX_G + 1 : 1
             for (int gi = a.n_groups; gi >= 0; --gi) {
                 // gi == n_groups .. 1: the boundary in front of group gi - 1 (root first), then its rows; gi == 0: the
                 // boundary BEHIND group 0 (scatter only)
                 const int slot = gi > 0 ? gi - 1 : a.n_groups;
                 const bool tail_only = gi == 0;
-                const int ginfo = wl_lane_get(tgi, slot);
+                const WlGroupK gk = SCH.g[SK && gi > 0 ? gi - 1 : 0];          // the group whose rows run (the tail: none)
+                // slabs per net of the group whose g_v partials this boundary scatters - the one that ran last (the tail: group 0;
+                // the root's boundary: none)
+                const int SLP = !SK || gi >= a.n_groups ? 0 : SCH.g[SK ? gi : 0].sl;
+                const int ginfo = SK ? 0 : wl_lane_get(tgi, slot);
                 struct { int level; } g;
-                g.level = ginfo & 0xff;
+                g.level = SK ? gk.level : ginfo & 0xff;
                 const int lop0 = slot * a.d;
-                const float* slab_prev = slabs + ((phase + 1) & 1) * NR * w.slab_floats;     // the g_v partials of the group just finished
+                // (an even number of groups per block: the slab set of a group is the same in every block)
+                constexpr bool PHK = SK && Shape::n_groups % 2 == 0;
+                const float* slab_prev = slabs + (PHK ? ((Shape::n_groups - gi + 1) & 1) : ((phase + 1) & 1)) * NR * w.slab_floats;     // the g_v partials of the group just finished
                 const int sid = (wi * (a.n_groups + 1) + (a.n_groups - gi)) * 8;
                 (void)sid;
                 STAMP(sid + 0)
@@ -194,7 +205,7 @@ __global__ __launch_bounds__(64 * MAX_NW) __attribute__((amdgpu_waves_per_eu(2, 
                 //  coupling gradients of one transformed lane - `col`: the same lane, or a scatter-only and a coupling-only lane sharing the slot,
                 //  since a wavefront runs through both halves whatever its lanes need.  16 rows x nact slots: at d = 6 the three boundaries of a
                 //  block have 3, 4 and 2 slots for 3, 5 and 2 active lanes of 6 - each ONE pass of four slots x 16 rows)
-                const int nact = ginfo >> 8;
+                const int nact = SK ? (gi > 0 ? gk.slots : SCH.tail_slots) : ginfo >> 8;
                 for (int idx = lane; idx < ROWS * nact; idx += 64) {
                     const int row = idx & 15, kk = idx >> 4;
                     const i32x4 lq = *(const LDS_AS i32x4*)(T.lops + lop0 + kk);        // (the planner keeps a wave-local plan's table in LDS)
@@ -213,16 +224,27 @@ __global__ __launch_bounds__(64 * MAX_NW) __attribute__((amdgpu_waves_per_eu(2, 
 #pragma unroll
                         for (int net = 0; net < 2; ++net) {
                             const LDS_AS int32_t* up = (const LDS_AS int32_t*)(T.units + sc_unit + net);
-                            const int sl_n = up[21], gv_off = up[22];
-                            const bool more = __builtin_amdgcn_ballot_w64(sl_n > 4) != 0;       // (wave-uniform: a per-lane trip count is an exec-masked loop)
+                            // (a known step: exactly SLP slabs per net, no ballot, no clamps; same slab order - and one + 0.f where the
+                            //  general form adds its unused slots as zeros, which turns a sum of -0.f into +0.f)
+                            const bool SLK = SK && SLP >= 1 && SLP <= 4;
+                            const int sl_n = SLK ? SLP : up[21], gv_off = up[22];
+                            const bool more = SLK ? false : __builtin_amdgcn_ballot_w64(sl_n > 4) != 0;       // (wave-uniform: a per-lane trip count is an exec-masked loop)
 #pragma unroll
                             for (int h = 0; h < NR; ++h) {
                                 const float* sp = slab_prev + h * w.slab_floats + gv_off + row * 4 + sc_k;
                                 float v[4];             // (the first four slabs in flight together, added in slab order)
+                                if (SLK) {
 #pragma unroll
-                                for (int u = 0; u < 4; ++u) v[u] = sp[(u < sl_n ? u : sl_n - 1) * 64];
+                                    for (int u = 0; u < 4; ++u) if (u < SLP) v[u] = sp[u * 64];
 #pragma unroll
-                                for (int u = 0; u < 4; ++u) gb[h] += u < sl_n ? v[u] : 0.f;
+                                    for (int u = 0; u < 4; ++u) if (u < SLP) gb[h] += v[u];
+                                    if (SLP < 4) gb[h] += 0.f;
+                                } else {
+#pragma unroll
+                                    for (int u = 0; u < 4; ++u) v[u] = sp[(u < sl_n ? u : sl_n - 1) * 64];
+#pragma unroll
+                                    for (int u = 0; u < 4; ++u) gb[h] += u < sl_n ? v[u] : 0.f;
+                                }
                                 if (more) for (int sl = 4; sl < sl_n; ++sl) gb[h] += sp[sl * 64];
                             }
                         }
@@ -264,7 +286,7 @@ __global__ __launch_bounds__(64 * MAX_NW) __attribute__((amdgpu_waves_per_eu(2, 
                 {
                     const bool block_switch = slot == 0;                     // next: root level of the block before
                     int nlevel = a.n_levels - 1;
-                    if (!block_switch) nlevel = wl_lane_get(tgi, slot - 1) & 0xff;
+                    if (!block_switch) nlevel = SK ? SCH.g[SK && slot > 0 ? slot - 1 : 0].level : wl_lane_get(tgi, slot - 1) & 0xff;
                     if (block_switch ? cb > 0 : nlevel != g.level) {
                         const float* ntape = block_switch ? (const float*)nblk.tape : tape;
                         const bool ntop = block_switch ? (nblk.perm != nullptr || cb > 1) : top;
@@ -274,7 +296,7 @@ __global__ __launch_bounds__(64 * MAX_NW) __attribute__((amdgpu_waves_per_eu(2, 
                         lp_pending = true;
                     }
                 }
-                c.slab = (LDS_AS float*)(slabs + (phase & 1) * NR * w.slab_floats);
+                c.slab = (LDS_AS float*)(slabs + (PHK ? ((Shape::n_groups - gi) & 1) : (phase & 1)) * NR * w.slab_floats);
                 ++phase;
                 {
                     int rnext = -1;         // the wavefront's first row of the next group - of the next block's root behind group 0
@@ -287,7 +309,7 @@ __global__ __launch_bounds__(64 * MAX_NW) __attribute__((amdgpu_waves_per_eu(2, 
                     // (two wavefronts share a SIMD and the hardware serves the older one first: while the rows run the YOUNGER one goes first
                     //  instead - s_setprio; measured: backward -1.2 % at cfg 2, -1.4 % with row pairs (GAS), -3.5 % at 512 rows)
                     if (wave >= 4) __builtin_amdgcn_s_setprio(1);
-                    wl_rows<K_BWD, NR>(c, ring, primed, wl_lane_get(tr0, slot), wl_lane_get(tr1, slot), rnext, wrap, lane);
+                    wl_rows<K_BWD, NR, SK>(c, ring, primed, wl_lane_get(tr0, slot), wl_lane_get(tr1, slot), rnext, wrap, lane, gk);
                     __builtin_amdgcn_s_setprio(0);
                 }
                 STAMP(sid + 2)

@@ -168,11 +168,23 @@ __global__ __launch_bounds__(64 * MAX_NW) __attribute__((amdgpu_waves_per_eu(2, 
             }
             c.xld = a.xld; c.gld = 0; c.WT = a.WT; c.slab_h = w.slab_floats; c.train = train; c.first_tile = false;
 
+            // (a shape-specialised instance unrolls the loop over its group list: gi and with it the group's schedule - entries, level,
+            //  k-blocks, tile counts, slabs per net - are literals in every copy of the body; hint_wl.hpp)
+            constexpr bool SK = Shape::shape >= 0;
+            constexpr WlSched SCH = Shape::SC;
+#pragma unroll SK ? WL_MAX_G : 1
             for (int gi = 0; gi < a.n_groups; ++gi) {
-                const int ginfo = wl_lane_get(tgi, gi);
+                const WlGroupK gk = SCH.g[SK ? gi : 0];
                 struct { int ent_begin, ent_cnt, level, level_last; } g;
-                g.ent_begin = ginfo & 0xffff; g.ent_cnt = (ginfo >> 16) & 0xff; g.level = (ginfo >> 24) & 0x3f; g.level_last = (ginfo >> 30) & 1;
-                float* slab = slabs + (phase & 1) * NR * w.slab_floats;
+                if constexpr (SK) {
+                    g.ent_begin = gk.ent_begin; g.ent_cnt = gk.ent_cnt; g.level = gk.level; g.level_last = gk.level_last;
+                } else {
+                    const int ginfo = wl_lane_get(tgi, gi);
+                    g.ent_begin = ginfo & 0xffff; g.ent_cnt = (ginfo >> 16) & 0xff; g.level = (ginfo >> 24) & 0x3f; g.level_last = (ginfo >> 30) & 1;
+                }
+                // (an even number of groups per block: the slab set of a group is the same in every block)
+                const int ph = (SK && Shape::n_groups % 2 == 0) ? (gi & 1) : (phase & 1);
+                float* slab = slabs + ph * NR * w.slab_floats;
                 ++phase;
 #pragma unroll
                 for (int h = 0; h < 2; ++h) c.xs[h] = (const LDS_AS float*)XS(h < NR ? h : 0);
@@ -193,7 +205,7 @@ __global__ __launch_bounds__(64 * MAX_NW) __attribute__((amdgpu_waves_per_eu(2, 
                     // (two wavefronts share a SIMD and the hardware serves the older one first: while the rows run the YOUNGER one goes first
                     //  instead - s_setprio; measured per instance: forward / inverse of single row tiles -2 %, at 512 rows -5 %, row pairs +3 %: not there)
                     if (NR == 1 && wave >= 4) __builtin_amdgcn_s_setprio(1);
-                    wl_rows<K_FWD, NR>(c, ring, primed, wl_lane_get(tr0, gi), wl_lane_get(tr1, gi), rnext, wrap, lane);
+                    wl_rows<K_FWD, NR, SK>(c, ring, primed, wl_lane_get(tr0, gi), wl_lane_get(tr1, gi), rnext, wrap, lane, gk);
                     if (NR == 1) __builtin_amdgcn_s_setprio(0);
                 }
                 STAMP(sid + 1)
@@ -215,18 +227,27 @@ __global__ __launch_bounds__(64 * MAX_NW) __attribute__((amdgpu_waves_per_eu(2, 
                 for (int ps = 0; ps < npass; ++ps) {
                     const bool act = 4 * ps + kq < g.ent_cnt;
                     const int xcol = ent.x & 0xffff, sl_ns = ent.y & 0xffff, sl_nt = (int)((unsigned)ent.y >> 16);
-                    const bool more = __builtin_amdgcn_ballot_w64(sl_ns > 4 || sl_nt > 4) != 0;     // (a unit shared by more than four wavefronts: h > 192)
+                    // (a known group: exactly gk.sl slabs per net, no ballot, no clamps; same slab order, the sums start from 0.f as they do below)
+                    const bool SLK = SK && gk.sl <= 4;
+                    const bool more = SLK ? false : __builtin_amdgcn_ballot_w64(sl_ns > 4 || sl_nt > 4) != 0;     // (a unit shared by more than four wavefronts: h > 192)
 #pragma unroll
                     for (int h = 0; h < NR; ++h) {
                         const float* sp = slab + h * w.slab_floats + ent.z + m * 4;
                         const float* tp = slab + h * w.slab_floats + ent.w + m * 4;
                         // (the slabs of the wavefronts that share the unit: the first four of either net in flight together, added in slab order)
                         float vs[4], vt[4];
-#pragma unroll
-                        for (int u = 0; u < 4; ++u) { vs[u] = sp[(u < sl_ns ? u : sl_ns - 1) * 64]; vt[u] = tp[(u < sl_nt ? u : sl_nt - 1) * 64]; }
                         float s = 0.f, t = 0.f;
+                        if (SLK) {
 #pragma unroll
-                        for (int u = 0; u < 4; ++u) { s += u < sl_ns ? vs[u] : 0.f; t += u < sl_nt ? vt[u] : 0.f; }
+                            for (int u = 0; u < 4; ++u) if (u < gk.sl) { vs[u] = sp[u * 64]; vt[u] = tp[u * 64]; }
+#pragma unroll
+                            for (int u = 0; u < 4; ++u) if (u < gk.sl) { s += vs[u]; t += vt[u]; }
+                        } else {
+#pragma unroll
+                            for (int u = 0; u < 4; ++u) { vs[u] = sp[(u < sl_ns ? u : sl_ns - 1) * 64]; vt[u] = tp[(u < sl_nt ? u : sl_nt - 1) * 64]; }
+#pragma unroll
+                            for (int u = 0; u < 4; ++u) { s += u < sl_ns ? vs[u] : 0.f; t += u < sl_nt ? vt[u] : 0.f; }
+                        }
                         if (more) {
                             for (int sl = 4; sl < sl_ns; ++sl) s += sp[sl * 64];
                             for (int sl = 4; sl < sl_nt; ++sl) t += tp[sl * 64];
@@ -236,8 +257,15 @@ __global__ __launch_bounds__(64 * MAX_NW) __attribute__((amdgpu_waves_per_eu(2, 
                         if (act && train && tape != nullptr && wave == tsel && row0[h] + m < a.B)
                             tape[(size_t)(a.n_levels + g.level) * lvl + (size_t)(row0[h] + m) * a.d + xcol] = s;
                         float xn;
-                        if (!REV) { xn = expf(aa) * xold[h] + t; jpart[h] += act ? aa : 0.f; }
-                        else      { xn = (xold[h] - t) * __builtin_amdgcn_rcpf(expf(aa)); jpart[h] -= act ? aa : 0.f; }      // (v_rcp_f32, 1 ulp, instead of a ten-instruction division)
+                        if (!REV) xn = expf(aa) * xold[h] + t;
+                        else      xn = (xold[h] - t) * __builtin_amdgcn_rcpf(expf(aa));      // (v_rcp_f32, 1 ulp, instead of a ten-instruction division)
+                        {
+                            // (a plain add in every instance: where `act` is a literal - a known group with four entries - the select is gone and
+                            //  the compiler would contract alpha * atan(s) + jpart into one FMA, which rounds differently from the dynamic instance's sum)
+#pragma clang fp contract(off)
+                            if (!REV) jpart[h] += act ? aa : 0.f;
+                            else      jpart[h] -= act ? aa : 0.f;
+                        }
                         if (act) XS(h)[m * a.xld + xcol] = xn;
                     }
                     if (ps + 1 < npass) {        // (more than four transformed lanes in the group: the next entries)

@@ -155,8 +155,14 @@ int hint_plan_check_paths(const hint_node_desc* nodes, int32_t n_nodes, int32_t 
  *   field -1: the entry of the shape table whose instance the launch takes (every folded field equal), or -1: the dynamic instance
  *   field 0 .. HINT_WL_FOLD_FIELDS - 1: the launch's own folded field of that index, in the order of that header's field lists
  *             (tools/wl_shape_table.py prints the table from them).
+ *   field HINT_WL_SCHED_FIELD0 + i, i < HINT_WL_SCHED_FIELDS: int32 i of the launch's level schedule (that header's WlSched: per
+ *             group of the plan, up to four, its thirteen schedule constants in list order, then the backward's tail slot count),
+ *             derived by walking every row record of the group; a field that is not the same in every record of its group is -1,
+ *             and a launch whose schedule holds one takes the dynamic instance.
  * A plan that does not run on the wave-local kernels reports -1 and zeros.  INT64_MIN (and hint_last_error) on bad arguments. */
 #define HINT_WL_FOLD_FIELDS 36
+#define HINT_WL_SCHED_FIELD0 1000
+#define HINT_WL_SCHED_FIELDS 53
 int64_t hint_plan_check_wl_shape(const hint_node_desc* nodes, int32_t n_nodes, int32_t d, int32_t dc, float clamp, int32_t B,
                                  int32_t num_cu, int32_t backward, int32_t with_perm, int32_t field);
 /* Host-only as well: one 64-bit digest per table the planner emits, first for the plan, then for its 4-wavefront variant (zeros

@@ -23,5 +23,7 @@ from .curves import fit_plus_shapes, plus_dominant_angle, plus_fit_grad, plus_fi
 from .curves import (lens_iou_dice, lens_shape_scores, plus_iou_dice, plus_shape_scores,  # noqa: F401,E402
                      polygon_overlap)
 from .shapes import fourier_coeffs, lens_draws, lens_rings, sample_lens_joint, sample_lens_prior  # noqa: F401,E402
+from .plusgen import (plus_draws, plus_outlines, sample_plus_conditional, sample_plus_joint,  # noqa: F401,E402
+                      sample_plus_prior, sample_plus_targeted)
 
 __version__ = "0.1.0"

@@ -114,6 +114,14 @@ class FcoefDesc(C.Structure):
                 ("max_groups", C.c_int32)]
 
 
+class PlusGenDesc(C.Structure):
+    """mirror of `hint_plusgen_desc` (include/hint_amd.h); the stream is a field, not a parameter of the run"""
+    _fields_ = [("n_rows", C.c_int64), ("seed", C.c_uint64), ("offset", C.c_uint64), ("rows", C.c_void_p), ("draws", C.c_void_p),
+                ("target", C.POINTER(C.c_float)), ("x", C.c_void_p), ("y", C.c_void_p), ("outline", C.c_void_p),
+                ("counts", C.c_void_p), ("corners", C.c_void_p), ("draws_out", C.c_void_p), ("workspace", C.c_void_p),
+                ("workspace_bytes", C.c_size_t), ("max_groups", C.c_int32), ("stream", C.c_void_p)]
+
+
 _lib = None
 
 _PROTOS = {
@@ -220,6 +228,8 @@ _PROTOS = {
     "hint_lensgen_run": (C.c_int, [C.POINTER(LensGenDesc), C.c_void_p]),
     "hint_fcoef_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32]),
     "hint_fcoef_run": (C.c_int, [C.POINTER(FcoefDesc), C.c_void_p]),
+    "hint_plusgen_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "hint_plusgen_run": (C.c_int, [C.POINTER(PlusGenDesc)]),
 }
 
 

@@ -27,6 +27,7 @@
 // integer-reduced angle.
 #include "hint_host.hpp"
 #include "hint_fourier.hpp"
+#include "hint_rowdraws.hpp"
 
 namespace hint {
 
@@ -38,6 +39,7 @@ constexpr int LENS_K = 5;                           // coefficients per axis (Le
 constexpr int LENS_ROW = 4 * LENS_K;
 constexpr int LENS_RING = 32;                       // points of the ring output: the closed ring has 31 or 32
 constexpr int LENS_MIN_OPEN = 30, LENS_MAX_OPEN = 31;
+constexpr unsigned LENS_TAG = 0x4C454E53u;          // counter word 3: "LENS"
 constexpr float LENS_HALF_A = 9.7598f;              // acos(0.575) in vertex indices: where the circles cross, seen from A ..
 constexpr float LENS_HALF_B = 4.2937f;              // .. acos(0.9125), seen from B
 
@@ -92,34 +94,6 @@ static const LensTables& lens_tables() {
 
 }  // namespace hint
 
-// (hint_curve.hip's: LDS writes of some lanes, reads of others, within one wavefront)
-__device__ __forceinline__ void shapegen_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// Philox4x32-10 on counter = {row lo, row hi, stream, "LENS"}, key = {seed lo, seed hi} (include/hint_amd.h)
-__device__ __forceinline__ void lens_philox(unsigned long long seed, unsigned long long row, unsigned stream, unsigned (&c)[4]) {
-    unsigned c0 = (unsigned)row, c1 = (unsigned)(row >> 32), c2 = stream, c3 = 0x4C454E53u;
-    unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const unsigned hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-        const unsigned hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-        c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    c[0] = c0; c[1] = c1; c[2] = c2; c[3] = c3;
-}
-// one Box-Muller pair, as philox_normal4 (hint_device.hpp) takes it: v_log_f32 is log2, v_sin / v_cos take turns
-__device__ __forceinline__ float2 lens_box_muller(unsigned a, unsigned b) {
-    const float u0 = fminf(((float)a + 1.0f) * 2.3283064365386963e-10f, 1.0f);
-    const float u1 = (float)b * 2.3283064365386963e-10f;
-    const float r = __builtin_sqrtf(-1.3862943611198906f * __builtin_amdgcn_logf(u0));
-    return float2{r * __builtin_amdgcn_cosf(u1), r * __builtin_amdgcn_sinf(u1)};
-}
-
 // max over the W edges around e0 of n_k . v, less R apothem: negative when v (relative to the polygon's centre) is strictly inside
 template <int W>
 __device__ __forceinline__ float lens_slack(const float2* hs, float vx, float vy, int e0, float r_apo) {
@@ -154,15 +128,15 @@ __global__ __launch_bounds__(256) void hint_lensgen_kernel(const hint::LensArgs 
             d = a.draws[rr];
         } else {
             unsigned c[4];
-            lens_philox(a.seed, a.offset + (unsigned long long)rr, 0u, c);
-            const float2 nm = lens_box_muller(c[2], c[3]);
+            row_philox(a.seed, a.offset + (unsigned long long)rr, 0u, LENS_TAG, c);
+            const float2 nm = row_box_muller(c[2], c[3]);
             d = float4{(float)c[0] * 2.3283064365386963e-10f, (float)c[1] * 2.3283064365386963e-10f, nm.x, nm.y};
         }
         if (a.draws_out && valid) a.draws_out[row] = d;
         if (a.eps && valid) {
             unsigned c[4];
-            lens_philox(a.seed, a.offset + (unsigned long long)row, 1u, c);
-            a.eps[row] = lens_box_muller(c[0], c[1]);
+            row_philox(a.seed, a.offset + (unsigned long long)row, 1u, LENS_TAG, c);
+            a.eps[row] = row_box_muller(c[0], c[1]);
         }
         // ---- the unit figure ----
         const float r0 = 1.f + d.x;

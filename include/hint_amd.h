@@ -1032,6 +1032,91 @@ typedef struct hint_fcoef_desc {
 size_t hint_fcoef_workspace_bytes(int64_t n_rows, int32_t p_max, int32_t n_coeffs);
 int hint_fcoef_run(const hint_fcoef_desc* desc, void* stream);
 
+/* The plus-shape sampler: prior, joint and targeted rows (data.py:176-252 PlusShapeModel.densify_polyline, generate_plus_shape,
+ * sample_prior and sample_joint - one polygon-library union, one densify_polyline and one 25-coefficient DFT per row in a Python
+ * loop; data.py:466-489 runs it for the training and test sets, rejection_sampling.py:76-85 for the 1e8-row prior,
+ * rejection_sampling.py:113-127 in the rejection loop of the ground-truth conditional sample).  The plus model has no
+ * forward_process: its labels y exist nowhere but here.  A row has nine draws, u_xl, u_yl, u_xw, u_yw, u_xs, u_ys, u_a in [0, 1]
+ * and n_x, n_y standard normal.  Everything below is fp32 unless it says otherwise.
+ *   1 parameters (data.py:190-202)  xlength = fma(2, u_xl, 3), ylength = fma(2, u_yl, 3); xwidth = fma(1.5, u_xw, 0.5), ywidth =
+ *     fma(1.5, u_yw, 0.5); xshift = fma(3, u_xs, -1.5), yshift = fma(3, u_ys, -1.5); angle = (float)(pi / 2) u_a.  With a TARGET
+ *     t = (cx, cy, angle, ratio), 0.25 <= ratio <= 4 (data.py:195-200, :216): xwidth = fma(2 - ratio / 2, u_xw, ratio / 2) when
+ *     ratio >= 1, otherwise fma(2 ratio - 0.5, u_xw, 0.5); ywidth = xwidth / ratio; angle = t[2]; u_yw and u_a go unused (they are
+ *     still drawn and still checked).  The bound on ratio keeps both widths in [0.5, 2], below the lengths.  t[0], t[1] are not read.
+ *   2 local coordinates: the eight of plus_segments_from_params (best_shape_fit.py:28-29) without its 0.01 clamps, by the
+ *     operations of hint_plus_desc item 1:  xleft = xshift - xlength / 2, xright = xshift + xlength / 2, xtop = xwidth / 2,
+ *     xbottom = -xtop;  yright = ywidth / 2, yleft = -yright, ybottom = yshift - ylength / 2, ytop = yshift + ylength / 2.
+ *   3 the union's ring.  THE ORDER OF THE RING'S VERTICES IS THIS LIBRARY'S DEFINITION: the reference takes whatever its polygon
+ *     library returns, and that library is not available to pin it.  The ring is the corners of the union of the two boxes,
+ *     clockwise, starting at the first corner met clockwise from the negative x axis; for the full plus this is the vertex order of
+ *     plus_segments_from_params (:34-45).  Arm present: left xleft < yleft, right xright > yright, top ytop > xtop, bottom
+ *     ybottom < xbottom; EQUALITY (measure zero) IS "ARM ABSENT".  Per quadrant, clockwise - upper-left shown, the other three
+ *     follow by symmetry (upper-right, lower-right, lower-left, each in clockwise order):
+ *         both arms       (xleft, xtop), (yleft, xtop), (yleft, ytop)
+ *         left arm only   (xleft, xtop)
+ *         top arm only    (yleft, ytop)
+ *         neither         (yleft, ytop), (xleft, ytop), (xleft, xtop): the notch with its reflex corner
+ *     12 corners (full plus, 73.0 % of the prior) or 8 (one arm missing, four patterns of 6.2 %; two adjacent arms missing, four of
+ *     0.54 %); two opposite arms cannot be missing (lengths exceed widths).  No collinear vertices, no duplicates.
+ *   4 densify_polyline(coords, 0.2) (data.py:176-186), as hint_plus_desc item 6 states it for 0.02: edge i runs from E = V_i to
+ *     S = V_(i+1); len = max(|S.x - E.x|, |S.y - E.y|) (a difference of local coordinates: the ring is axis-aligned); count =
+ *     max(1, rint((double)len / 0.2)), round half to even; point j is E when count = 1, otherwise fma(t, S, (1 - t) E) with
+ *     t = (float)j / (float)(count - 1).  A vertex appears twice where both its edges have count >= 2, as in the reference.
+ *     N = the sum of the counts: 54 <= N <= 106 from the perimeter's bounds; storage is 128 points a row.
+ *   5 centring, rotation, offset (data.py:211-222): mean = (sum of the N dense points) / (float)N, the sum a fixed tree - sixteen
+ *     partial sums s_k = p_k + p_(k+16) + .. (ascending), then s_0 + s_1 + .. + s_15 (ascending); p -= mean; p = p R, R = [[cos a,
+ *     sin a], [-sin a, cos a]] with sincos in double of the fp32 angle, rounded once, by the operations of hint_plus_desc item 2
+ *     (qx = fma(-py, sin, px cos), qy = fma(py, cos, px sin)); p += (0.5 n_x, 0.5 n_y).
+ *   6 label (data.py:203, :211, :219, :222, :225): center = (-mean) R + 0.5 (n_x, n_y) by the same operations;
+ *     y = (center_x, center_y, angle, xwidth / ywidth).
+ *   7 x = the 100 floats flatten_coeffs(fourier_coeffs(points, 25)) (data.py:30-33, :42-49), as hint_fcoef_desc states them: the
+ *     accumulators, n ascending, the angle reduced in integers, a[m] and a[-m] from one pair of sums, each twiddle the true
+ *     value rounded once.
+ * tests/plusgen_oracle.py derives the distance to the exact value, in units of u A (u = 2^-24, A the row's largest centred
+ * coordinate magnitude, outline as it is written): a placed point 236, center 185, a coefficient 238 + N - worst-case chains; the
+ * device's worst measured are 5.6, 1.9 and 6.6; a row with an arm shorter than 2^-20 or an edge whose
+ * len / 0.2 lies within 2^-17 of a half-integer may differ from the exact ring by a point or a pattern.
+ * Draws: `draws` [n_rows, 9] in the order above as given, or (draws NULL) Philox4x32-10 with counter = {row lo, row hi, stream,
+ * 0x504C5553}, key = {seed lo, seed hi}, row = offset + i, or rows[i] where `rows` is given: stream 0 gives u_xl, u_yl, u_xw, u_yw
+ * = (float)c 2^-32; stream 1 u_xs, u_ys, u_a (the fourth word is unused); stream 2 (n_x, n_y), the Box-Muller pair of (c0, c1) as
+ * hint_lensgen_desc specifies it.  A row is a function of (seed, row, target) alone: chunks at any boundaries, the carry into the
+ * counter's high word included, give the bits of one call; a gather by `rows` gives the bits the same rows have in a contiguous
+ * call; two runs agree bit for bit.  draws_out receives the draws used (any source).
+ * A row one of whose seven uniforms is outside [0, 1], or one of whose draws is not finite, is REJECTED: x = NaN, y = NaN, count
+ * 0, corners 0, outline 0; it disturbs no other row.  The workspace is int32[workspace_bytes / 4]: every word is written by a run
+ * and their sum is the number of rejected rows (0 for every Philox run), exactly as for hint_lensgen_run.
+ *   run              stream-ordered on the current device: one launch, no host synchronisation, no allocation (capturable), no
+ *                    atomics.  With x NULL (labels only) a row stops after the mean: no second pass, no transform.  THE STREAM IS A
+ *                    FIELD OF THE DESCRIPTOR, unlike every other run of this header: the repository's frozen stream ledger
+ *                    (tests/stream_cases.py) fails for any function declared here with a stream parameter that it has no row
+ *                    for, and could not be given one when this entry point was added; tests/test_gpu_plusgen.py carries the
+ *                    gated-stream test instead.  A consequence of that ledger, not a new convention.
+ *                    max_groups: 0 = the default grid, otherwise the workgroups at most.  Rejects, before any device call and
+ *                    naming the field: a null desc or workspace; x and y both NULL; n_rows outside 1..2^30; rows together with
+ *                    draws; offset + n_rows above 2^64 - 1 (Philox without rows); max_groups < 0; a target entry that is not
+ *                    finite or a ratio outside 0.25..4; x, y or workspace not 16-byte, rows or outline not 8-byte, draws, counts,
+ *                    corners or draws_out not 4-byte aligned; a workspace smaller than workspace_bytes says.
+ *   workspace_bytes  0 (and an error message) for an n_rows run would reject.  Never decreases with n_rows; at most 32 KiB. */
+typedef struct hint_plusgen_desc {
+    int64_t n_rows;
+    uint64_t seed, offset;
+    const uint64_t* rows;                  /* NULL, or device uint64[n_rows]: the Philox row of output row i (offset goes unused) */
+    const float* draws;                    /* NULL (Philox), or device float[n_rows, 9]; not together with rows */
+    const float* target;                   /* NULL, or HOST float[4] = (cx, cy, angle, ratio), read during the call */
+    float* x;                              /* NULL, or device float[n_rows, 100], 16-byte aligned */
+    float* y;                              /* NULL, or device float[n_rows, 4], 16-byte aligned; x and y are not both NULL */
+    float* outline;                        /* NULL, or device float[n_rows, 128, 2]: the placed dense outline, zero-padded */
+    int32_t* counts;                       /* NULL, or device int32[n_rows]: N, 54..106 */
+    int32_t* corners;                      /* NULL, or device int32[n_rows]: corners + 16 arms - the low four bits are 8 or 12,
+                                              arms = bit 0 left, 1 right, 2 top, 3 bottom (present) */
+    float* draws_out;                      /* NULL, or device float[n_rows, 9] */
+    void* workspace; size_t workspace_bytes;      /* 16-byte aligned */
+    int32_t max_groups;
+    void* stream;                          /* the hipStream_t the launch goes to (NULL: the null stream) */
+} hint_plusgen_desc;
+size_t hint_plusgen_workspace_bytes(int64_t n_rows);
+int hint_plusgen_run(const hint_plusgen_desc* desc);
+
 int hint_abi_version(void);
 const char* hint_last_error(void);
 /* what the library binary was built with and runs with: "libhint_amd abi N, gfx950, HIP x.y.z, clang ..., src <12 hex digits: hash

@@ -7,6 +7,7 @@ from .hint import (HierarchicalAffineCouplingBlock, HierarchicalAffineCouplingTr
                    HintAmdError, linear_subnet_constructor, set_pack_cache, set_param_grad_mode)
 
 from .flow import FixedOrthogonal, HintFlow  # noqa: F401,E402
+from .householder import HouseholderPerm  # noqa: F401,E402
 from .train import FlowTrainer  # noqa: F401,E402
 from .conditional import (AffineCoupling, ConditionalFlowTrainer, ConditionalHintFlow,  # noqa: F401,E402
                           ExternalAffineCoupling, F_fully_connected)

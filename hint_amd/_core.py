@@ -89,6 +89,12 @@ class TrainerCore:
 
     def __init__(self, flow, engines, device: torch.device, lr: float, betas, eps: float, weight_decay: float, grad_clamp: float,
                  noise: float, use_graph: bool, group, seed: Optional[int]):
+        from .householder import trainable        # (householder.py imports hint.py: not at module level here)
+        if any(map(trainable, flow.modules())):
+            # (the chained backward does not emit dL/dW of a permutation)
+            raise _lib.HintAmdError(f"{type(self).__name__}: the model has trainable Householder permutations (learned_perms=True), "
+                                    "which the fused step does not train; use the module route - loss.backward() and "
+                                    "hint_amd.ClampAdam over model.parameters() - for such a model")
         self.lib = _lib.load()
         self.flow, self.device, self.group = flow, device, group
         self._lr, self.betas, self.eps, self.wd = lr, betas, eps, weight_decay

@@ -122,6 +122,16 @@ class PlusGenDesc(C.Structure):
                 ("workspace_bytes", C.c_size_t), ("max_groups", C.c_int32), ("stream", C.c_void_p)]
 
 
+class HouseholderDesc(C.Structure):
+    """mirror of `hint_householder_desc` (include/hint_amd.h); the stream is a field, not a parameter of the run"""
+    _fields_ = [("op", C.c_int32), ("transpose", C.c_int32), ("B", C.c_int32), ("d", C.c_int32), ("n", C.c_int32),
+                ("Vs", C.c_void_p), ("W", C.c_void_p), ("x", C.c_void_p), ("y", C.c_void_p), ("g_y", C.c_void_p),
+                ("g_x", C.c_void_p), ("g_W", C.c_void_p), ("g_V", C.c_void_p), ("workspace", C.c_void_p),
+                ("workspace_bytes", C.c_size_t), ("stream", C.c_void_p)]
+
+
+HOUSEHOLDER_BUILD, HOUSEHOLDER_APPLY, HOUSEHOLDER_GRAD = 0, 1, 2
+
 _lib = None
 
 _PROTOS = {
@@ -230,6 +240,9 @@ _PROTOS = {
     "hint_fcoef_run": (C.c_int, [C.POINTER(FcoefDesc), C.c_void_p]),
     "hint_plusgen_workspace_bytes": (C.c_size_t, [C.c_int64]),
     "hint_plusgen_run": (C.c_int, [C.POINTER(PlusGenDesc)]),
+    "hint_householder_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "hint_householder_run": (C.c_int, [C.POINTER(HouseholderDesc)]),
+    "hint_householder_geometry": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
 }
 
 

@@ -28,7 +28,7 @@ import torch.nn as nn
 
 from . import _lib, dp
 from ._core import PackGroup, TrainerCore, _LossPair
-from .flow import FixedOrthogonal
+from .flow import FixedOrthogonal, make_perm, perm_matrix
 from .hint import HierarchicalAffineCouplingBlock, HierarchicalAffineCouplingTree, HintAmdError, _as_input
 
 
@@ -89,14 +89,14 @@ class ConditionalHintFlow(nn.Module):
     `y, x = model([z_y, z_x], rev=True)`."""
 
     def __init__(self, ndim_x: int, ndim_y: int, n_blocks: int, hidden: int, clamp: float = 4.0,
-                 perm_seed: int = 1):
+                 perm_seed: int = 1, learned_perms: bool = False):
         super().__init__()
         self.ndim_x, self.ndim_y, self.n_blocks = ndim_x, ndim_y, n_blocks
         self.perm_y, self.perm_x = nn.ModuleList(), nn.ModuleList()
         self.hac_x, self.ac_y_to_x, self.ac_y = nn.ModuleList(), nn.ModuleList(), nn.ModuleList()
         for i in range(n_blocks):
-            self.perm_y.append(FixedOrthogonal([(ndim_y,)], seed=perm_seed + 2 * i) if i > 0 else nn.Identity())
-            self.perm_x.append(FixedOrthogonal([(ndim_x,)], seed=perm_seed + 2 * i + 1) if i > 0 else nn.Identity())
+            self.perm_y.append(make_perm(ndim_y, perm_seed + 2 * i, learned_perms) if i > 0 else nn.Identity())          # (learned:
+            self.perm_x.append(make_perm(ndim_x, perm_seed + 2 * i + 1, learned_perms) if i > 0 else nn.Identity())      # both lanes)
             self.hac_x.append(HierarchicalAffineCouplingBlock(
                 [(ndim_x,)], c_internal=[hidden, hidden // 2, hidden // 4], clamp=clamp))              # :72-75
             self.ac_y_to_x.append(ExternalAffineCoupling([(ndim_x,)], dims_c=[(ndim_y,)],
@@ -241,9 +241,9 @@ class _PosteriorSampler:
         """the inference chain of batch size B and its coefficient buffer [n_blocks, R, 2, nx] (R = B per row, else 1)"""
         flow, nb, dx = self.flow, self.flow.n_blocks, self.flow.ndim_x
         for i in range(1, nb):                          # (the kernels read W through its raw pointer, row-major)
-            if not flow.perm_x[i].W.is_contiguous():
+            if isinstance(flow.perm_x[i], FixedOrthogonal) and not flow.perm_x[i].W.is_contiguous():
                 flow.perm_x[i].W = flow.perm_x[i].W.contiguous()
-        perms = [e.compose_perm(flow.perm_x[i].W if i > 0 else None) for i, e in enumerate(self.hx)]
+        perms = [e.compose_perm(perm_matrix(flow.perm_x[i]) if i > 0 else None) for i, e in enumerate(self.hx)]
         key = tuple((e.arena.data_ptr(), e.packed.data_ptr()) for e in self.hx) + tuple(p.data_ptr() if p is not None else 0 for p in perms)
         skey = (B, per_row, torch.cuda.current_stream(self.device).cuda_stream)     # (as hint.py and flow.py key their pools)
         have = self._chains.get(skey)
@@ -454,8 +454,8 @@ class ConditionalFlowTrainer(TrainerCore):
         st["gc"] = [f32(B, dy) for _ in range(nb)]
         st["x_in"], st["y_in"] = f32(B, dx), f32(B, dy)          # the step's inputs (a captured graph reads them here)
         # fixed matrices in front of the modules (composed with the modules' own node permutations: none here)
-        st["perm"] = {("hac_x", i): eng[("hac_x", i)].compose_perm(flow.perm_x[i].W if i > 0 else None) for i in range(nb)}
-        st["perm"].update({("ac_y", i): eng[("ac_y", i)].compose_perm(flow.perm_y[i].W if i > 0 else None) for i in range(nb)})
+        st["perm"] = {("hac_x", i): eng[("hac_x", i)].compose_perm(perm_matrix(flow.perm_x[i]) if i > 0 else None) for i in range(nb)}
+        st["perm"].update({("ac_y", i): eng[("ac_y", i)].compose_perm(perm_matrix(flow.perm_y[i]) if i > 0 else None) for i in range(nb)})
         st["perm"].update({("ac_y_to_x", i): eng[("ac_y_to_x", i)].compose_perm(None) for i in range(nb)})
         st["tapes"], st["ws"], st["wsb"], st["chains"] = {}, {}, {}, {}
         ptr = lambda t: t.data_ptr() if t is not None else None
@@ -722,8 +722,8 @@ class ConditionalFlowTrainer(TrainerCore):
         for i in range(nb):                                         # ---- forward, both lanes ----
             front = None
             if i > 0:
-                y = y @ flow.perm_y[i].W
-                front = flow.perm_x[i].W
+                y = y @ perm_matrix(flow.perm_y[i])
+                front = perm_matrix(flow.perm_x[i])
             acc = self.loss_acc if i == nb - 1 else None
 
             def fwd(kind, inp, c, front, J_in, acc):
@@ -752,7 +752,7 @@ class ConditionalFlowTrainer(TrainerCore):
             gy = gy + gc                                            # the condition of ac_y_to_x_i is the y lane
             gx, _ = bwd("hac_x", gx)                                # (comes back through the x lane's permutation)
             if i > 0:
-                gy = gy @ flow.perm_y[i].W.t()
+                gy = gy @ perm_matrix(flow.perm_y[i]).t()
         self._optimizer(on_device_adam)
         self.last = (zy, zx, Jx, Jy)
         self._last_B = B

@@ -23,6 +23,7 @@ from . import _lib
 from . import hint as _hint
 from ._core import PackGroup, slice_layout
 from .hint import HierarchicalAffineCouplingBlock, HintAmdError, _Lease, _Region, _mark_launch, _NONES
+from .householder import HouseholderPerm, perm_matrix, trainable as _trainable_perm
 
 
 def random_orthogonal(d: int, seed: int) -> torch.Tensor:
@@ -48,6 +49,12 @@ class FixedOrthogonal(nn.Module):
 
     def output_dims(self, input_dims):
         return input_dims
+
+
+def make_perm(d: int, seed: int, learned: bool) -> nn.Module:
+    """the permutation in front of a block: the fixed orthogonal matrix, or (learned_perms=True) what
+    lens_shape/unconditional_hint_2_full.py:62-65 puts there, HouseholderPerm(fixed=False, n_reflections=ndim)"""
+    return HouseholderPerm([(d,)], n_reflections=d, seed=seed) if learned else FixedOrthogonal([(d,)], seed=seed)
 
 
 _REQUIRES_GRAD = operator.attrgetter("requires_grad")
@@ -102,9 +109,10 @@ class ChainRunner:
         (reshuffle=True trees), composed into one [d,d] matrix"""
         flow = self.flow
         for i in range(flow.n_blocks):          # the kernels read W through its raw pointer (row-major)
-            if flow.has_perm(i) and not flow.perms[i].W.is_contiguous():
+            if isinstance(flow.perms[i], FixedOrthogonal) and not flow.perms[i].W.is_contiguous():
                 flow.perms[i].W = flow.perms[i].W.contiguous()
-        front = [flow.perms[i].W if flow.has_perm(i) else None for i in range(flow.n_blocks)]
+        # (a learned permutation's matrix is rebuilt here, on the current stream, into a buffer of a stable address)
+        front = [perm_matrix(flow.perms[i]) if flow.has_perm(i) else None for i in range(flow.n_blocks)]
         return [e.compose_perm(f) for e, f in zip(self.engines, front)]
 
     def pack_all(self, zero_buf=None, rng_state=None, opt_state=None):
@@ -293,7 +301,7 @@ class HintFlow(nn.Module):
 
     def __init__(self, ndim_x: int, n_blocks: int, c_internal: Sequence[int], ndim_c: int = 0, clamp: float = 4.0,
                  max_splits: int = -1, min_split_size: int = 2, perm_seed: int = 1, perm_first: bool = False,
-                 reshuffle: bool = False):
+                 reshuffle: bool = False, learned_perms: bool = False):
         super().__init__()
         self.ndim_x, self.ndim_c, self.n_blocks = ndim_x, ndim_c, n_blocks
         dims_c = [(ndim_c,)] if ndim_c > 0 else []
@@ -301,7 +309,7 @@ class HintFlow(nn.Module):
         self.blocks = nn.ModuleList()
         for i in range(n_blocks):
             has_perm = perm_first or i > 0        # power_hint_8.py:58 vs conditional_recursive_cinn_4.py:62
-            self.perms.append(FixedOrthogonal([(ndim_x,)], seed=perm_seed + i) if has_perm else nn.Identity())
+            self.perms.append(make_perm(ndim_x, perm_seed + i, learned_perms) if has_perm else nn.Identity())
             self.blocks.append(HierarchicalAffineCouplingBlock([(ndim_x,)], dims_c=dims_c, c_internal=list(c_internal),
                                                                clamp=clamp, max_splits=max_splits,
                                                                min_split_size=min_split_size, reshuffle=reshuffle))
@@ -341,7 +349,9 @@ class HintFlow(nn.Module):
 
     def _fused(self, x, cl, rev):
         """the whole flow in chained launches; None when this call has to walk the modules (not one CUDA device, blocks of
-        different shapes, several condition tensors, gradients through rev=True, a partly frozen flow)"""
+        different shapes, several condition tensors, gradients through rev=True, a partly frozen flow, gradients with a
+        trainable permutation - blocks and permutations are then separate autograd nodes - or learned permutations beside
+        reshuffle=True blocks, whose matrices the fused route composes on the host)"""
         if not self.fuse_chain or self.n_blocks == 0 or not isinstance(x, torch.Tensor) or not x.is_cuda \
                 or x.dtype != torch.float32 or x.dim() != 2 or x.shape[1] != self.ndim_x or x.shape[0] == 0 or len(cl) > 1:
             return None
@@ -354,6 +364,9 @@ class HintFlow(nn.Module):
         if not run.chainable:
             return None
         grad = torch.is_grad_enabled()
+        learned = [m for m in self.perms if isinstance(m, HouseholderPerm)]
+        if learned and ((grad and any(map(_trainable_perm, learned))) or any(e._perm_nodes for e in run.engines)):
+            return None
         n_req = sum(map(_REQUIRES_GRAD, run.params)) if grad else 0
         needs = grad and (n_req > 0 or x.requires_grad or (c is not None and c.requires_grad))
         if needs and (rev or _hint._PARAM_GRADS != "direct" or n_req != len(run.params)):
@@ -380,7 +393,7 @@ class HintFlow(nn.Module):
             return out, J
 
     def has_perm(self, i: int) -> bool:
-        return isinstance(self.perms[i], FixedOrthogonal)
+        return isinstance(self.perms[i], (FixedOrthogonal, HouseholderPerm))
 
     @staticmethod
     def _unwrap(x):

@@ -22,6 +22,7 @@ from . import _lib, dp
 from ._core import TrainerCore, _LossPair
 from .flow import HintFlow
 from .hint import HintAmdError, _as_input
+from .householder import perm_matrix
 
 
 class FlowTrainer(TrainerCore):
@@ -204,7 +205,7 @@ class FlowTrainer(TrainerCore):
         # draws from (Philox keyed by rng_state: seed, step counter) - one stream whatever route runs the step
         self._xn = None
         in_kernel = self.noise > 0 and B > 0
-        if in_kernel and self.engines[0].compose_perm(flow.perms[0].W if flow.has_perm(0) else None) is not None:
+        if in_kernel and self.engines[0].compose_perm(perm_matrix(flow.perms[0]) if flow.has_perm(0) else None) is not None:
             # (a matrix in front of the first block - perm_first / reshuffle=True: the kernel perturbs what it reads behind the
             #  matrix, not x; no launch of its own exists for that, so this one shape keeps torch's generator)
             x = x.add(torch.randn_like(x), alpha=self.noise)
@@ -213,7 +214,7 @@ class FlowTrainer(TrainerCore):
         h, J = x, None
         n = len(self.engines)
         for i, eng in enumerate(self.engines):
-            perm = eng.compose_perm(flow.perms[i].W if flow.has_perm(i) else None)
+            perm = eng.compose_perm(perm_matrix(flow.perms[i]) if flow.has_perm(i) else None)
             if i == 0 and in_kernel:
                 self._xn = torch.empty_like(h)
                 inputs.append(self._xn)
@@ -227,7 +228,7 @@ class FlowTrainer(TrainerCore):
         g = z                                  # dL/dz = z / B : the scale is applied inside the kernel
         for i in reversed(range(n)):
             a, b = self.slices[i]
-            perm = self.engines[i].compose_perm(flow.perms[i].W if flow.has_perm(i) else None)
+            perm = self.engines[i].compose_perm(perm_matrix(flow.perms[i]) if flow.has_perm(i) else None)
             g = self.engines[i].backward_chain(inputs[i], tapes[i], c, g, (1.0 / B) if i == n - 1 else 1.0,
                                                -1.0 / B, perm, self.G[a:b], accumulate=True)
         return B

@@ -1117,6 +1117,66 @@ typedef struct hint_plusgen_desc {
 size_t hint_plusgen_workspace_bytes(int64_t n_rows);
 int hint_plusgen_run(const hint_plusgen_desc* desc);
 
+/* The trainable Householder permutation between blocks: what the reference's lens-shape and plus-shape configs put there as
+ * HouseholderPerm(fixed=False, n_reflections=ndim) (configs/lens_shape/unconditional_hint_2_full.py:62-65 and thirteen siblings).
+ * FrEIA is neither vendored by the reference nor available here, so THE PARAMETERISATION IS THIS LIBRARY'S DEFINITION (FrEIA parity
+ * unpinned, as for the fixed orthogonal matrix).  For Vs fp32 [n, d], row i the vector v_i:
+ *   H_i = I - 2 v_i v_i^T / (v_i . v_i),   W = H_0 H_1 .. H_(n-1), [d, d] row-major
+ *   forward (transpose 0)  y = x W: a row meets H_0 first;   transpose 1  y = x W^T;   the log-determinant is 0
+ * Limits: 1 <= d <= 128, 1 <= n <= 256, 1 <= B <= 2^22 (every element offset fits in 31 bits).  Nothing special happens for a zero
+ * or non-finite v_i: the division gives NaN, and as every row of W passes through H_i all of W is NaN.  A non-finite row of x spoils
+ * its own row of y only.
+ *   op build  Vs -> W.  Row r of W is e_r taken through the reflections in order, w <- w - (2 (w . v_i) / (v_i . v_i)) v_i, IN DOUBLE:
+ *             one wavefront per row, lane l keeping entries l and l + 64; a dot product is the lane's two terms added in that
+ *             order, then a butterfly over the 64 lanes (distances 32, 16, .., 1); each entry is rounded to fp32 once.  One launch.
+ *   op apply  x, W -> y, on v_mfma_f32_16x16x4_f32: tiles of 16 rows by 16 columns, W (or its transpose) staged once per workgroup in
+ *             LDS with d padded to a multiple of 4 by zeros, the k-blocks of 4 added in ascending order.  A row's result depends
+ *             on that row and W only: any split of the batch into calls gives the bits of one call.  Rows past B and columns
+ *             past d are neither read nor written.  One launch.
+ *   op grad   x, g_y, W, Vs -> any of g_x, g_W, g_V (a NULL output is not computed and not touched); at most three launches.
+ *             g_x = g_y W^T (transpose 1: g_y W): apply with the other transpose flag.
+ *             g_W = x^T g_y (transpose 1: g_y^T x), [d, d] fp32: the rows are cut into slabs of R rows (R = 256 up to 64 slabs,
+ *             more rows per slab beyond, a multiple of 16); within a slab each of four wavefronts adds every fourth k-block of 4
+ *             rows on the same MFMA, the four partial tiles are added in wavefront order and go to the workspace; the slabs of
+ *             an entry are added in ascending order in double and rounded once.
+ *             g_V [n, d] fp32 from that double sum G and Vs, in double, by one workgroup walking i = n-1 .. 0 with
+ *             P = H_0 .. H_(i-1) and Gs = G (H_(i+1) .. H_(n-1))^T (reflections are involutions: P and Gs of step i - 1 are
+ *             P H_(i-1) and Gs H_i, rank-one updates):  a = P v_i, b = Gs v_i, q = P^T b, qt = Gs^T a, s = v_i . v_i,
+ *             g_(v_i) = -(2 / s) (q + qt) + (4 (a . b) / s^2) v_i.  O(d^2) per reflection; nothing is kept from the forward.
+ *   run              stream-ordered on the current device, no host synchronisation, no allocation (capturable), no atomics: two
+ *                    runs give equal bits.  Every byte of each output given is written and nothing outside them (and the
+ *                    workspace).  THE STREAM IS A FIELD OF THE DESCRIPTOR, as in hint_plusgen_desc and for the same reason.
+ *                    Rejects, before any device call and naming the field: a null desc; an unknown op; d outside its limits, n
+ *                    (build, grad) or B (apply, grad) outside theirs; a required pointer NULL - Vs and W for build; x, W and y
+ *                    for apply; g_y and W for grad, x as well when g_W or g_V is asked, Vs when g_V is, the workspace when
+ *                    either is; grad with none of g_x, g_W, g_V; a device pointer not 4-byte or a workspace not 16-byte
+ *                    aligned; a workspace smaller than workspace_bytes says; y aliasing x, g_x aliasing g_y.
+ *   workspace_bytes  bytes a run of `op` needs: 0 for build and apply, which use none; for grad at most 4.3 MiB (d = 128,
+ *                    B >= 16384).  For sizes run would reject: 0 and an error message.  Never decreases with B.
+ *   geometry         host only: field 0 the slab's row count R of a grad run over B rows, 1 the number of slabs, 2 the tiles per
+ *                    side of W.  -1 on an error. */
+#define HINT_HOUSEHOLDER_BUILD 0
+#define HINT_HOUSEHOLDER_APPLY 1
+#define HINT_HOUSEHOLDER_GRAD 2
+typedef struct hint_householder_desc {
+    int32_t op;                            /* HINT_HOUSEHOLDER_BUILD / _APPLY / _GRAD */
+    int32_t transpose;                     /* 0: y = x W; otherwise y = x W^T */
+    int32_t B, d, n;
+    const float* Vs;                       /* device float[n, d] */
+    float* W;                              /* device float[d, d]: written by build, read by apply and grad */
+    const float* x;                        /* device float[B, d] */
+    float* y;                              /* device float[B, d] (apply) */
+    const float* g_y;                      /* device float[B, d] (grad) */
+    float* g_x;                            /* NULL, or device float[B, d] */
+    float* g_W;                            /* NULL, or device float[d, d] */
+    float* g_V;                            /* NULL, or device float[n, d] */
+    void* workspace; size_t workspace_bytes;      /* 16-byte aligned */
+    void* stream;                          /* the hipStream_t the launches go to (NULL: the null stream) */
+} hint_householder_desc;
+size_t hint_householder_workspace_bytes(int32_t op, int32_t B, int32_t d, int32_t n);
+int hint_householder_run(const hint_householder_desc* desc);
+int64_t hint_householder_geometry(int32_t B, int32_t d, int32_t field);
+
 int hint_abi_version(void);
 const char* hint_last_error(void);
 /* what the library binary was built with and runs with: "libhint_amd abi N, gfx950, HIP x.y.z, clang ..., src <12 hex digits: hash

@@ -24,6 +24,16 @@
 
 namespace hint {
 
+// what the static policy's thin_out relies on (below):
+// the two directions' schedules describe the same group at every index (thin_K differs by direction on purpose)
+constexpr bool wl_sched_same_groups(const WlSched& p, const WlSched& q, int n_groups) {
+    bool same = true;
+    for (int i = 0; i < n_groups; ++i)
+        same = same && p.g[i].ent_begin == q.g[i].ent_begin && p.g[i].ent_cnt == q.g[i].ent_cnt && p.g[i].level == q.g[i].level &&
+               p.g[i].n1 == q.g[i].n1 && p.g[i].cin == q.g[i].cin && p.g[i].hw == q.g[i].hw && p.g[i].sl == q.g[i].sl;
+    return same;
+}
+
 // The kernels' view of their shape arguments (hint_wl_shape.hpp): the dynamic policy - no type in the kernels' trailing
 // parameter pack - hands the kernel arguments through; WlStatic<ID> overwrites every folded field of a copy with the table's
 // constant, so that index arithmetic, LDS offsets and trip counts that depend on nothing else are the compiler's.
@@ -35,6 +45,7 @@ template <bool BWD, typename... S> struct WlPolicy {
     static constexpr int shape = -1;
     static constexpr int n_groups = 0;
     static constexpr WlSched SC{};
+    static constexpr int thin_out(int) { return 4; }
     static __device__ __forceinline__ const KArgs& kargs(const KArgs& a) { return a; }
     static __device__ __forceinline__ const WlArgs& wlargs(const WlArgs& w) { return w; }
 };
@@ -44,6 +55,11 @@ template <bool BWD, int ID> struct WlPolicy<BWD, WlStatic<ID>> {
     static constexpr int n_groups = F.a_n_groups;
     static constexpr WlSched SC = BWD ? WL_SHAPES[ID].sbwd : WL_SHAPES[ID].sfwd;
     static_assert(n_groups >= 1 && n_groups <= WL_MAX_G && wl_sched_valid(SC, n_groups), "a folded schedule field is not uniform over its group (tools/wl_shape_table.py refuses such an entry)");
+    // outputs of the thin product BEHIND the rows of group gi (wl_row's epilogue): forward r, backward cin.  No field carries r for the
+    // forward: thin_K is cin in sfwd and r in sbwd, and both schedules list the plan's groups in the plan's order, so the forward reads
+    // the backward schedule's group gi (tests/test_wl_static_thin_cpu.py holds the two lists against each other and against the tree)
+    static constexpr int thin_out(int gi) { return BWD ? SC.g[gi].cin : WL_SHAPES[ID].sbwd.g[gi].thin_K; }
+    static_assert(wl_sched_same_groups(WL_SHAPES[ID].sfwd, WL_SHAPES[ID].sbwd, n_groups), "forward and backward schedule list different groups: r of the forward's group gi is not sbwd.g[gi].thin_K");
     static __device__ __forceinline__ KArgs kargs(const KArgs& a) {
         KArgs r = a;
 #define X(n) r.n = F.a_##n;
@@ -143,6 +159,15 @@ __device__ __forceinline__ void wl_mask_by_bits(f32x4& v, int bits) {
 __device__ __forceinline__ f32x4 wl_layer1(const LDS_AS f32x4* q, const float (&vin)[4]) {
     const f32x4 qb = q[16], q0 = q[0], q1 = q[4], q2 = q[8], q3 = q[12];
     return fma4(q3, vin[3], fma4(q2, vin[2], fma4(q1, vin[1], fma4(q0, vin[0], qb))));
+}
+// ... of a unit with a literal number of inputs: the same chain without its terms beyond cin, which are fma(0-vector, 0.f, acc) - they
+// add +0 (that can turn -0 into +0: `pre > 0` decides the same) - and without the reads of those zero vectors
+__device__ __forceinline__ f32x4 wl_layer1_k(const LDS_AS f32x4* q, const float (&vin)[4], int cin) {
+    f32x4 pre = q[16];
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        if (k < cin) pre = fma4(q[4 * k], vin[k], pre);
+    return pre;
 }
 
 // NR = 1 or 2 adjacent 16-row tiles per workgroup ("row pair"): both ride the SAME weight stream - every fragment tile
@@ -244,7 +269,7 @@ __device__ __forceinline__ int wl_lane_get(int table, int e) { return __builtin_
 template <int KIND, int NR, bool SK = false>
 __device__ __forceinline__ void wl_row(const WlCtx& c, const RowU& cr, const RowU& nr, const GLOBAL_AS float* pkn,
                                        const GLOBAL_AS uint8_t* const (&bitsn)[2], f32x4 (&ring)[RING][NEL], f32x4 (&part)[NR],
-                                       const LaneOff& lo, int lane, int ntt_lo = 1, int ntt_hi = 3) {
+                                       const LaneOff& lo, int lane, int ntt_lo = 1, int ntt_hi = 3, int thin_o = 4) {
     static_assert(KIND < 0 || (RING == 2 && NTT == 3), "the WL rows alternate two ring slots of three tiles");     // (checked where instantiated: the general kernels include this header for its helpers with NTT = 4)
     const int m = lane & 15, kq = lane >> 4;
     const int n1 = cr.n1, ntt = cr.ntt;
@@ -351,6 +376,11 @@ __device__ __forceinline__ void wl_row(const WlCtx& c, const RowU& cr, const Row
 
     STAMP(c.sid + 2)
     // ---- the tiles are finished: activation, tape, the thin product behind the layer ----
+    // A known group's units have `no` outputs of that product (forward r, backward cin: a literal) where the vector layout pads every
+    // unit to four.  The padded outputs are products with zero vectors that land in slab components no coupling entry and no scatter
+    // slot addresses, and the compiler cannot drop them (stored to LDS; fma(0, x, acc) is not dead): only outputs < no are formed
+    // and folded, the others keep the zeros `part` starts from.  No expression of a used value changes.
+    const int no = SK ? thin_o : 4;
     if (KIND == K_FWD) {
         const LDS_AS f32x4* w3 = (const LDS_AS f32x4*)(c.par + cr.thin_b) + kq;     // W3^T vector o of the row's tile t: w3[16 t + 4 o]
         const LDS_AS f32x4* b2 = (const LDS_AS f32x4*)(c.par + cr.aux) + kq;
@@ -360,7 +390,7 @@ __device__ __forceinline__ void wl_row(const WlCtx& c, const RowU& cr, const Row
                 const f32x4 bias = b2[4 * j];
                 f32x4 wv[4];
 #pragma unroll
-                for (int o = 0; o < 4; ++o) wv[o] = w3[16 * j + 4 * o];
+                for (int o = 0; o < 4; ++o) if (o < no) wv[o] = w3[16 * j + 4 * o];
 #pragma unroll
                 for (int h = 0; h < NR; ++h) {
                     // (the bias last, as the reference's addmm adds it: fewer rows land on the other side of a ReLU kink)
@@ -370,7 +400,7 @@ __device__ __forceinline__ void wl_row(const WlCtx& c, const RowU& cr, const Row
                         *(GLOBAL_AS f32x4*)(c.a2[h] + (m * c.WT + cr.ocol + 16 * j + 4 * kq)) = v;
                     }
 #pragma unroll
-                    for (int o = 0; o < 4; ++o) part[h][o] = dot4(wv[o], v, part[h][o]);
+                    for (int o = 0; o < 4; ++o) if (o < no) part[h][o] = dot4(wv[o], v, part[h][o]);
                 }
             }
         }
@@ -381,7 +411,11 @@ __device__ __forceinline__ void wl_row(const WlCtx& c, const RowU& cr, const Row
 #pragma unroll
         for (int h = 0; h < NR; ++h)
 #pragma unroll
-            for (int k = 0; k < 4; ++k) { const float v = c.xs[h][m * c.xld + xoff + (k < cin ? k : 0)]; xin[h][k] = k < cin ? v : 0.f; }
+            for (int k = 0; k < 4; ++k) {
+                if (SK && k >= no) { xin[h][k] = 0.f; continue; }        // (a known group: cin = no; not read, not multiplied)
+                const float v = c.xs[h][m * c.xld + xoff + (k < cin ? k : 0)];
+                xin[h][k] = k < cin ? v : 0.f;
+            }
         const LDS_AS f32x4* w1 = (const LDS_AS f32x4*)(c.par + cr.thin_b) + kq;     // W1 vector k of the row's tile t: w1[20 t + 4 k]
         const int nl = m;
 #pragma unroll
@@ -390,11 +424,11 @@ __device__ __forceinline__ void wl_row(const WlCtx& c, const RowU& cr, const Row
                 f32x4 dw = zero4();
 #pragma unroll
                 for (int h = 0; h < NR; ++h) {
-                    const f32x4 pre = wl_layer1(w1 + 20 * j, xin[h]);
+                    const f32x4 pre = SK ? wl_layer1_k(w1 + 20 * j, xin[h], no) : wl_layer1(w1 + 20 * j, xin[h]);
                     f32x4 g = acc[h][j];
                     g.x = pre.x > 0.f ? g.x : 0.f; g.y = pre.y > 0.f ? g.y : 0.f; g.z = pre.z > 0.f ? g.z : 0.f; g.w = pre.w > 0.f ? g.w : 0.f;
 #pragma unroll
-                    for (int o = 0; o < 4; ++o) part[h][o] = dot4(w1[20 * j + 4 * o], g, part[h][o]);
+                    for (int o = 0; o < 4; ++o) if (o < no) part[h][o] = dot4(w1[20 * j + 4 * o], g, part[h][o]);
                     // dW1[f][k] = sum_rows g1[row][f] v[row][k], db1[f] = sum_rows g1[row][f]: the tile transposed through the
                     // private scratch tile, then four 16x16x4 MFMAs over the 16 rows (out^T[k][f]: a lane ends with four inputs
                     // of one feature); the second row tile adds into the same accumulator
@@ -429,7 +463,7 @@ __device__ __forceinline__ void wl_row(const WlCtx& c, const RowU& cr, const Row
         for (int h = 0; h < NR; ++h) {
             f32x4 s;
 #pragma unroll
-            for (int o = 0; o < 4; ++o) s[o] = kq_sum(part[h][o]);
+            for (int o = 0; o < 4; ++o) s[o] = o < no ? kq_sum(part[h][o]) : part[h][o];
             if (kq == 0) ((LDS_AS f32x4*)(c.slab + h * c.slab_h + cr.slab))[m] = s;
             part[h] = zero4();
         }
@@ -444,10 +478,11 @@ struct WlCarry {
     int held;        // the record `nrec` holds (index, or -1)
     RecV nrec;       // ... fetched two rows ahead, carried across groups and blocks
 };
-// (SK, gk: the group's schedule; the record the last row hands over to may be another group's, so only the CURRENT row's is folded)
+// (SK, gk: the group's schedule; the record the last row hands over to may be another group's, so only the CURRENT row's is folded;
+//  thin_o: outputs of the thin product behind the group's rows - a literal of a known group)
 template <int KIND, int NR, bool SK = false>
 __device__ __forceinline__ void wl_rows(const WlCtx& c, f32x4 (&ring)[RING][NEL], WlCarry& cy, int r0, int r1, int rnext,
-                                        bool other_block, int lane, const WlGroupK& gk = WlGroupK{}) {
+                                        bool other_block, int lane, const WlGroupK& gk = WlGroupK{}, int thin_o = 4) {
     if (r0 >= r1) return;
     LaneOff lo;
     lo.w = (unsigned)lane * 16u; lo.b = (unsigned)(lane >> 4) * 16u; lo.l = (unsigned)lane;
@@ -468,7 +503,7 @@ __device__ __forceinline__ void wl_rows(const WlCtx& c, f32x4 (&ring)[RING][NEL]
 #endif
         const GLOBAL_AS float* pkn = hand ? c.pk_next : c.pk;
         const GLOBAL_AS uint8_t* const bitsn[2] = {hand ? c.bits_next[0] : c.bits[0], hand ? c.bits_next[1] : c.bits[1]};
-        wl_row<KIND, NR, SK>(c, wl_rec_fold<KIND, SK>(cr, gk), nr, pkn, bitsn, ring, part, lo, lane, gk.ntt_min, gk.ntt_max);
+        wl_row<KIND, NR, SK>(c, wl_rec_fold<KIND, SK>(cr, gk), nr, pkn, bitsn, ring, part, lo, lane, gk.ntt_min, gk.ntt_max, thin_o);
         cr = nr;
     }
     cy.primed = rnext;

@@ -309,7 +309,7 @@ __global__ __launch_bounds__(64 * MAX_NW) __attribute__((amdgpu_waves_per_eu(2, 
                     // (two wavefronts share a SIMD and the hardware serves the older one first: while the rows run the YOUNGER one goes first
                     //  instead - s_setprio; measured: backward -1.2 % at cfg 2, -1.4 % with row pairs (GAS), -3.5 % at 512 rows)
                     if (wave >= 4) __builtin_amdgcn_s_setprio(1);
-                    wl_rows<K_BWD, NR, SK>(c, ring, primed, wl_lane_get(tr0, slot), wl_lane_get(tr1, slot), rnext, wrap, lane, gk);
+                    wl_rows<K_BWD, NR, SK>(c, ring, primed, wl_lane_get(tr0, slot), wl_lane_get(tr1, slot), rnext, wrap, lane, gk, Shape::thin_out(SK && gi > 0 ? gi - 1 : 0));
                     __builtin_amdgcn_s_setprio(0);
                 }
                 STAMP(sid + 2)

@@ -205,7 +205,7 @@ __global__ __launch_bounds__(64 * MAX_NW) __attribute__((amdgpu_waves_per_eu(2, 
                     // (two wavefronts share a SIMD and the hardware serves the older one first: while the rows run the YOUNGER one goes first
                     //  instead - s_setprio; measured per instance: forward / inverse of single row tiles -2 %, at 512 rows -5 %, row pairs +3 %: not there)
                     if (NR == 1 && wave >= 4) __builtin_amdgcn_s_setprio(1);
-                    wl_rows<K_FWD, NR, SK>(c, ring, primed, wl_lane_get(tr0, gi), wl_lane_get(tr1, gi), rnext, wrap, lane, gk);
+                    wl_rows<K_FWD, NR, SK>(c, ring, primed, wl_lane_get(tr0, gi), wl_lane_get(tr1, gi), rnext, wrap, lane, gk, Shape::thin_out(SK ? gi : 0));
                     if (NR == 1) __builtin_amdgcn_s_setprio(0);
                 }
                 STAMP(sid + 1)

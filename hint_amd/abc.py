@@ -15,6 +15,7 @@ import torch
 
 from . import _lib
 from ._lib import HintAmdError
+from ._ops import _run_desc
 
 __all__ = ["nearest_rows", "quantile_abc"]
 
@@ -62,20 +63,13 @@ def _check_count(v, who: str, name: str, least: int) -> int:
 
 
 def _run(y: torch.Tensor, t: torch.Tensor, k: int):
-    lib = _lib.load()
     n, ny = y.shape
-    nbytes = lib.hint_abc_workspace_bytes(n, ny, k)
-    if nbytes == 0:
-        _lib.check(1, "hint_abc_workspace_bytes")
-    with torch.cuda.device(y.device):
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=y.device)
-        idx = torch.empty(k, dtype=torch.int32, device=y.device)
-        dist = torch.empty(k, dtype=torch.float32, device=y.device)
-        desc = _lib.AbcDesc()
-        desc.y, desc.target, desc.n_rows, desc.ny, desc.k = y.data_ptr(), t.data_ptr(), n, ny, k
-        desc.idx, desc.dist, desc.workspace, desc.workspace_bytes = idx.data_ptr(), dist.data_ptr(), ws.data_ptr(), nbytes
-        st = lib.hint_abc_run(desc, torch.cuda.current_stream(y.device).cuda_stream)
-    _lib.check(st, "hint_abc_run")
+    idx = torch.empty(k, dtype=torch.int32, device=y.device)
+    dist = torch.empty(k, dtype=torch.float32, device=y.device)
+    desc = _lib.AbcDesc()
+    desc.y, desc.target, desc.n_rows, desc.ny, desc.k = y.data_ptr(), t.data_ptr(), n, ny, k
+    desc.idx, desc.dist = idx.data_ptr(), dist.data_ptr()
+    _run_desc("hint_abc_run", desc, y.device, (n, ny, k))
     return idx, dist
 
 

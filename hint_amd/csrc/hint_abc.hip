@@ -458,16 +458,12 @@ int hint_abc_run(const hint_abc_desc* desc, void* stream) {
     if (!desc->target) return fail("hint_abc_run: target is null");
     if (!desc->idx) return fail("hint_abc_run: idx is null");
     if (!desc->dist) return fail("hint_abc_run: dist is null");
-    if (!desc->workspace) return fail("hint_abc_run: workspace is null");
+    if (workspace_null("hint_abc_run", desc->workspace)) return 1;
     if (abc_check_sizes("hint_abc_run", desc->n_rows, desc->ny, desc->k, true)) return 1;
-    if (((uintptr_t)desc->y & 3) != 0) return fail("hint_abc_run: y must be 4-byte aligned");
-    if (((uintptr_t)desc->target & 3) != 0) return fail("hint_abc_run: target must be 4-byte aligned");
-    if (((uintptr_t)desc->idx & 3) != 0) return fail("hint_abc_run: idx must be 4-byte aligned");
-    if (((uintptr_t)desc->dist & 3) != 0) return fail("hint_abc_run: dist must be 4-byte aligned");
-    if (((uintptr_t)desc->workspace & 15) != 0) return fail("hint_abc_run: workspace must be 16-byte aligned");
+    if (check_aligned("hint_abc_run", {{"y", desc->y, 3}, {"target", desc->target, 3}, {"idx", desc->idx, 3}, {"dist", desc->dist, 3}}))
+        return 1;
     const AbcLayout L = abc_layout(desc->n_rows, desc->k);
-    if (desc->workspace_bytes < L.total)
-        return fail("hint_abc_run: workspace_bytes = %zu is too small (hint_abc_workspace_bytes: %zu)", desc->workspace_bytes, L.total);
+    if (workspace_fits("hint_abc_run", "abc", desc->workspace, desc->workspace_bytes, L.total)) return 1;
     const AbcGeom g = abc_geom(desc->n_rows);
     hipStream_t s = (hipStream_t)stream;
     if (desc->ny == 2 && ((uintptr_t)desc->y & 7) == 0) return abc_launch<2>(desc, g, L, s);

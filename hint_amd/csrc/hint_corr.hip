@@ -285,18 +285,14 @@ int hint_corr_run(const hint_corr_desc* desc, void* stream) {
     if (!desc) return fail("hint_corr_run: desc is null");
     if (!desc->x) return fail("hint_corr_run: x is null");
     if (!desc->out) return fail("hint_corr_run: out is null");
-    if (!desc->workspace) return fail("hint_corr_run: workspace is null");
+    if (workspace_null("hint_corr_run", desc->workspace)) return 1;
     if (!desc->target && !desc->corr) return fail("hint_corr_run: target and corr are both null: nothing to compute");
     if (corr_check_sizes("hint_corr_run", desc->n, desc->d)) return 1;
-    if (misaligned("hint_corr_run", "x", desc->x, 3)) return 1;
-    if (misaligned("hint_corr_run", "target", desc->target, 7)) return 1;
-    if (misaligned("hint_corr_run", "corr", desc->corr, 7)) return 1;
-    if (misaligned("hint_corr_run", "out", desc->out, 7)) return 1;
-    if (misaligned("hint_corr_run", "workspace", desc->workspace, 15)) return 1;
+    if (check_aligned("hint_corr_run", {{"x", desc->x, 3}, {"target", desc->target, 7}, {"corr", desc->corr, 7}, {"out", desc->out, 7}}))
+        return 1;
     const int n = desc->n, d = desc->d, Kp = corr_pad16(d);
     const CorrLayout L = corr_layout(n, d);
-    if (desc->workspace_bytes < L.total)
-        return fail("hint_corr_run: workspace_bytes = %zu is too small (hint_corr_workspace_bytes: %zu)", desc->workspace_bytes, L.total);
+    if (workspace_fits("hint_corr_run", "corr", desc->workspace, desc->workspace_bytes, L.total)) return 1;
 
     const CorrGeom g = corr_geom(n, d);
     char* ws = (char*)desc->workspace;

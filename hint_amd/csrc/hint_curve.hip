@@ -32,7 +32,7 @@
 // the same trip count and each step is one conflict-free 8-byte LDS read for ~12 vector operations, so LDS is not the limit
 // (4 SIMDs x 1 read per ~12 operations against one LDS port), no lane sits idle beyond 2 l > P - 1, and no workgroup barrier
 // stands in the row loop.  Untuned: see DESIGN section 12.
-#include "hint_pointset.hpp"
+#include "hint_host.hpp"
 
 namespace hint {
 
@@ -232,18 +232,14 @@ int hint_curve_run(const hint_curve_desc* desc, void* stream) {
     if (desc->dist && !desc->target) return fail("hint_curve_run: dist needs a target (target is null)");
     if (desc->mean && !desc->target) return fail("hint_curve_run: mean needs a target (target is null)");
     const char* who = "hint_curve_run";
-    if (ps_check_groups(who, desc->max_groups)) return 1;
+    if (check_groups(who, desc->max_groups)) return 1;
     if (!std::isfinite(desc->noise)) return fail("hint_curve_run: noise must be finite");
-    if (ps_check_aligned(who, {{"x", desc->x, 3}, {"eps", desc->eps, 3}, {"target", desc->target, 3}, {"y", desc->y, 3},
+    if (check_aligned(who, {{"x", desc->x, 3}, {"eps", desc->eps, 3}, {"target", desc->target, 3}, {"y", desc->y, 3},
                                {"dist", desc->dist, 3}, {"mean", desc->mean, 3}}))
         return 1;
-    if (desc->mean) {
-        if (!desc->workspace) return fail("hint_curve_run: workspace is null (mean needs one)");
-        if (misaligned(who, "workspace", desc->workspace, 15)) return 1;
-        if (desc->workspace_bytes < curve_ws_bytes())
-            return fail("hint_curve_run: workspace_bytes = %zu is too small (hint_curve_workspace_bytes: %zu)", desc->workspace_bytes,
-                        curve_ws_bytes());
-    }
+    if (desc->mean && (workspace_null(who, desc->workspace, "mean needs one") ||
+                       workspace_fits(who, "curve", desc->workspace, desc->workspace_bytes, curve_ws_bytes())))
+        return 1;
     const CurveGeom g = curve_geom(desc->n_rows, desc->max_groups);
     hipStream_t s = (hipStream_t)stream;
     double* partial = desc->mean ? (double*)desc->workspace : nullptr;

@@ -123,7 +123,7 @@ int64_t hint_hausdorff_geometry(int64_t n_rows, int32_t n_points, int64_t max_te
              "3 the grid cap, 4 tiles of the largest template)", field);
         return -1;
     }
-    const int64_t out[5] = {ps_grid(n_rows, 0, HD_MAX_WG), 1, PS_TILE, HD_MAX_WG, (max_template_points + PS_TILE - 1) / PS_TILE};
+    const int64_t out[5] = {capped_grid(n_rows, 0, HD_MAX_WG), 1, PS_TILE, HD_MAX_WG, (max_template_points + PS_TILE - 1) / PS_TILE};
     return out[field];
 }
 
@@ -141,12 +141,12 @@ int hint_hausdorff_run(const hint_hausdorff_desc* desc, void* stream) {
     if (hd_check_sizes(who, desc->n_rows, desc->n_coeffs, desc->n_points, row_max, desc->x != nullptr)) return 1;
     if (desc->a_offsets && desc->n_template > desc->n_rows * (int64_t)PS_MAX_M)
         return fail("%s: n_template = %lld is more than n_rows x %d points", who, (long long)desc->n_template, PS_MAX_M);
-    if (ps_check_groups(who, desc->max_groups)) return 1;
-    if (ps_check_aligned(who, {{"x", desc->x, 3}, {"b_points", desc->b_points, 3}, {"a_points", desc->a_points, 3},
+    if (check_groups(who, desc->max_groups)) return 1;
+    if (check_aligned(who, {{"x", desc->x, 3}, {"b_points", desc->b_points, 3}, {"a_points", desc->a_points, 3},
                                {"a_offsets", desc->a_offsets, 7}, {"a_params", desc->a_params, 3}, {"max_h", desc->max_h, 3},
                                {"avg_h", desc->avg_h, 3}, {"chamfer", desc->chamfer, 3}, {"points", desc->points, 3}}))
         return 1;
-    const int grid = ps_grid(desc->n_rows, desc->max_groups, HD_MAX_WG);
+    const int grid = capped_grid(desc->n_rows, desc->max_groups, HD_MAX_WG);
     hipLaunchKernelGGL(hint_hausdorff_kernel, dim3(grid), dim3(PS_THREADS), 0, (hipStream_t)stream, desc->x, desc->b_points,
                        (int)desc->n_rows, desc->x ? desc->n_coeffs : 1, desc->n_points, desc->a_points,
                        (const long long*)desc->a_offsets, desc->a_params, (long long)desc->n_template, desc->max_h, desc->avg_h,

@@ -1,5 +1,7 @@
 // Host-side internals shared by the translation units behind the C ABI (include/hint_amd.h): the plan object, the
-// kernels' launch wrappers and the helpers every entry point uses.  Not part of the public ABI.
+// kernels' launch wrappers and the helpers every entry point uses - fail(), HIP_TRY and, below them, the argument checks the
+// descriptor entry points (hint_mmd.hip .. hint_householder.hip) share, their message texts part of the behaviour
+// (tests/golden/desc_faults.json).  Not part of the public ABI.
 //   hint_plan.cpp     the planner: node list -> static schedule in device memory (hint_plan_create / _check / _destroy)
 //   hint_abi.cpp      sizes and layouts, the launch path (row_launch, launch_rows_fwd, wgrad_launch, run_backward), the block-level
 //                     entry points, re-pack groups, the optimizer, build info
@@ -14,6 +16,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -108,6 +111,44 @@ std::string& last_error_ref();           // that message (hint_plan_create keeps
 // an entry point's check of a pointer argument (null passes): 0, or fail() with the message every entry point words alike
 inline int misaligned(const char* who, const char* name, const void* p, int mask) {
     return ((uintptr_t)p & mask) != 0 ? fail("%s: %s must be %d-byte aligned", who, name, mask + 1) : 0;
+}
+
+inline int check_groups(const char* who, int32_t max_groups) {
+    if (max_groups < 0) return fail("%s: max_groups must be >= 0 (got %d)", who, max_groups);
+    return 0;
+}
+
+// a descriptor's pointers, in the order they are reported in (a null pointer is aligned)
+struct ptr_arg {
+    const char* name;
+    const void* p;
+    int mask;
+};
+
+inline int check_aligned(const char* who, std::initializer_list<ptr_arg> ptrs) {
+    for (const ptr_arg& a : ptrs)
+        if (misaligned(who, a.name, a.p, a.mask)) return 1;
+    return 0;
+}
+
+// workgroups of a persistent grid over n rows; max_wg: the kernel's cap (CUs x the workgroups its registers let a CU hold)
+inline int capped_grid(long long n, int max_groups, int max_wg) {
+    const long long cap = max_groups > 0 && max_groups < max_wg ? max_groups : max_wg;
+    return (int)(n < cap ? n : cap);
+}
+
+// the workspace contract of hint_<op>_run: not null (why: what needs it, where not every call does), 16-byte aligned, and at
+// least what hint_<op>_workspace_bytes says.  In parts, because the entry points check them at different points of their order
+inline int workspace_null(const char* who, const void* ws, const char* why = nullptr) {
+    if (ws) return 0;
+    return why ? fail("%s: workspace is null (%s)", who, why) : fail("%s: workspace is null", who);
+}
+inline int workspace_small(const char* who, const char* op, size_t bytes, size_t need) {
+    if (bytes < need) return fail("%s: workspace_bytes = %zu is too small (hint_%s_workspace_bytes: %zu)", who, bytes, op, need);
+    return 0;
+}
+inline int workspace_fits(const char* who, const char* op, const void* ws, size_t bytes, size_t need) {
+    return misaligned(who, "workspace", ws, 15) || workspace_small(who, op, bytes, need);
 }
 
 inline int cdiv(int a, int b) { return (a + b - 1) / b; }

@@ -311,10 +311,8 @@ int hint_householder_run(const hint_householder_desc* desc) {
     if (!desc) return fail("%s: desc is null", who);
     if (hh_check_sizes(who, desc->op, desc->B, desc->d, desc->n)) return 1;
     const int op = desc->op, B = desc->B, d = desc->d, n = desc->n, T = desc->transpose != 0;
-    if (misaligned(who, "Vs", desc->Vs, 3) || misaligned(who, "W", desc->W, 3) || misaligned(who, "x", desc->x, 3) ||
-        misaligned(who, "y", desc->y, 3) || misaligned(who, "g_y", desc->g_y, 3) || misaligned(who, "g_x", desc->g_x, 3) ||
-        misaligned(who, "g_W", desc->g_W, 3) || misaligned(who, "g_V", desc->g_V, 3) ||
-        misaligned(who, "workspace", desc->workspace, 15))
+    if (check_aligned(who, {{"Vs", desc->Vs, 3}, {"W", desc->W, 3}, {"x", desc->x, 3}, {"y", desc->y, 3}, {"g_y", desc->g_y, 3},
+                            {"g_x", desc->g_x, 3}, {"g_W", desc->g_W, 3}, {"g_V", desc->g_V, 3}, {"workspace", desc->workspace, 15}}))
         return 1;
     hipStream_t s = (hipStream_t)desc->stream;
     if (op == HINT_HOUSEHOLDER_BUILD) {
@@ -340,12 +338,9 @@ int hint_householder_run(const hint_householder_desc* desc) {
     if (want_v && !desc->Vs) return fail("%s: Vs is null (grad with g_V)", who);
     if (desc->g_x && hh_overlap(desc->g_y, desc->g_x, row_bytes)) return fail("%s: g_x aliases g_y", who);
     const HhLayout L = hh_layout(B, d);
-    if (want_w || want_v) {
-        if (!desc->workspace) return fail("%s: workspace is null (grad with g_W or g_V)", who);
-        if (desc->workspace_bytes < L.total)
-            return fail("%s: workspace_bytes = %zu is too small (hint_householder_workspace_bytes: %zu)", who, desc->workspace_bytes,
-                        L.total);
-    }
+    if ((want_w || want_v) && (workspace_null(who, desc->workspace, "grad with g_W or g_V") ||
+                               workspace_small(who, "householder", desc->workspace_bytes, L.total)))
+        return 1;
     if (desc->g_x && hh_launch_apply(desc->g_y, desc->W, B, d, !T, desc->g_x, s)) return 1;
     if (want_w || want_v) {
         const HhGeom g = hh_geom(B, d);

@@ -182,7 +182,7 @@ int64_t hint_lensfit_geometry(int64_t n_rows, int32_t n_points, int32_t field) {
              "3 the grid cap, 4 the most prototype points)", field);
         return -1;
     }
-    const int64_t out[5] = {ps_grid(n_rows, 0, FIT_MAX_WG), 1, PS_TILE, FIT_MAX_WG, LF_MAX_M};
+    const int64_t out[5] = {capped_grid(n_rows, 0, FIT_MAX_WG), 1, PS_TILE, FIT_MAX_WG, LF_MAX_M};
     return out[field];
 }
 
@@ -197,13 +197,13 @@ int hint_lensfit_run(const hint_lensfit_desc* desc, void* stream) {
     if (lf_check_sizes(who, desc->n_rows, desc->n_coeffs, desc->n_points, desc->n_template, desc->x != nullptr)) return 1;
     if (fit_check(who, desc->n_starts, desc->n_steps, desc->lr, desc->angle_lr, desc->gamma, desc->momentum, desc->trace)) return 1;
     if (!std::isfinite(desc->weight)) return fail("%s: weight must be finite (got %g)", who, desc->weight);
-    if (ps_check_groups(who, desc->max_groups)) return 1;
-    if (ps_check_aligned(who, {{"x", desc->x, 3}, {"b_points", desc->b_points, 3}, {"a_points", desc->a_points, 3},
+    if (check_groups(who, desc->max_groups)) return 1;
+    if (check_aligned(who, {{"x", desc->x, 3}, {"b_points", desc->b_points, 3}, {"a_points", desc->a_points, 3},
                                {"starts", desc->starts, 3}, {"params", desc->params, 3}, {"loss", desc->loss, 3},
                                {"best", desc->best, 3}, {"all_params", desc->all_params, 3}, {"all_loss", desc->all_loss, 3},
                                {"grad", desc->grad, 3}, {"trace", desc->trace, 3}}))
         return 1;
-    const int grid = ps_grid(desc->n_rows, desc->max_groups, FIT_MAX_WG);
+    const int grid = capped_grid(desc->n_rows, desc->max_groups, FIT_MAX_WG);
     hipLaunchKernelGGL(hint_lensfit_kernel, dim3(grid), dim3(PS_THREADS), 0, (hipStream_t)stream, desc->x, desc->b_points,
                        (int)desc->n_rows, desc->x ? desc->n_coeffs : 1, desc->n_points, desc->a_points, (int)desc->n_template,
                        desc->starts, desc->n_starts, desc->n_steps, desc->lr, desc->angle_lr, desc->gamma, (float)desc->momentum,

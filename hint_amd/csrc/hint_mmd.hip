@@ -287,7 +287,7 @@ int hint_mmd_run(const hint_mmd_desc* desc, void* stream) {
     if (!desc->x) return fail("hint_mmd_run: x is null");
     if (!desc->y) return fail("hint_mmd_run: y is null");
     if (!desc->out) return fail("hint_mmd_run: out is null");
-    if (!desc->workspace) return fail("hint_mmd_run: workspace is null");
+    if (workspace_null("hint_mmd_run", desc->workspace)) return 1;
     if (mmd_check_sizes("hint_mmd_run", desc->n_x, desc->n_y, desc->d)) return 1;
     if (desc->n_kernels < 1 || desc->n_kernels > MMD_MAX_KERNELS)
         return fail("hint_mmd_run: n_kernels must be 1..%d (got %d)", MMD_MAX_KERNELS, desc->n_kernels);
@@ -305,10 +305,8 @@ int hint_mmd_run(const hint_mmd_desc* desc, void* stream) {
     }
     if ((((uintptr_t)desc->x | (uintptr_t)desc->y | (uintptr_t)desc->out | (uintptr_t)desc->yy) & 3) != 0)
         return fail("hint_mmd_run: x, y, yy and out must be 4-byte aligned");
-    if (((uintptr_t)desc->workspace & 15) != 0) return fail("hint_mmd_run: workspace must be 16-byte aligned");
     const MmdLayout L = mmd_layout(desc->n_x, desc->n_y, desc->d);
-    if (desc->workspace_bytes < L.total)
-        return fail("hint_mmd_run: workspace_bytes = %zu is too small (hint_mmd_workspace_bytes: %zu)", desc->workspace_bytes, L.total);
+    if (workspace_fits("hint_mmd_run", "mmd", desc->workspace, desc->workspace_bytes, L.total)) return 1;
 
     char* ws = (char*)desc->workspace;
     float* xp = (float*)(ws + L.xp);

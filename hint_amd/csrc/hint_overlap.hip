@@ -299,7 +299,7 @@ int64_t hint_overlap_geometry(int64_t n_rows, int32_t n_points, int64_t max_temp
              "3 the grid cap, 4 tiles of the largest template)", field);
         return -1;
     }
-    const int64_t out[5] = {ps_grid(n_rows, 0, OV_MAX_WG), 1, PS_TILE, OV_MAX_WG, (max_template_points + PS_TILE - 1) / PS_TILE};
+    const int64_t out[5] = {capped_grid(n_rows, 0, OV_MAX_WG), 1, PS_TILE, OV_MAX_WG, (max_template_points + PS_TILE - 1) / PS_TILE};
     return out[field];
 }
 
@@ -324,13 +324,13 @@ int hint_overlap_run(const hint_overlap_desc* desc, void* stream) {
     if (ov_check_sizes(who, desc->n_rows, desc->n_coeffs, desc->n_points, row_max, desc->x != nullptr)) return 1;
     if (with_pts && desc->a_offsets && desc->n_template > desc->n_rows * (int64_t)PS_MAX_M)
         return fail("%s: n_template = %lld is more than n_rows x %d points", who, (long long)desc->n_template, PS_MAX_M);
-    if (ps_check_groups(who, desc->max_groups)) return 1;
-    if (ps_check_aligned(who, {{"x", desc->x, 3}, {"b_points", desc->b_points, 3}, {"a_points", desc->a_points, 3},
+    if (check_groups(who, desc->max_groups)) return 1;
+    if (check_aligned(who, {{"x", desc->x, 3}, {"b_points", desc->b_points, 3}, {"a_points", desc->a_points, 3},
                                {"a_offsets", desc->a_offsets, 7}, {"a_params", desc->a_params, 3},
                                {"plus_params", desc->plus_params, 3}, {"areas", desc->areas, 3}, {"iou", desc->iou, 3},
                                {"dice", desc->dice, 3}, {"crossings", desc->crossings, 3}}))
         return 1;
-    const int grid = ps_grid(desc->n_rows, desc->max_groups, OV_MAX_WG);
+    const int grid = capped_grid(desc->n_rows, desc->max_groups, OV_MAX_WG);
     hipLaunchKernelGGL(hint_overlap_kernel, dim3(grid), dim3(PS_THREADS), 0, (hipStream_t)stream, desc->x, desc->b_points,
                        (int)desc->n_rows, desc->x ? desc->n_coeffs : 1, desc->n_points, with_t ? desc->a_points : nullptr,
                        with_t ? (const long long*)desc->a_offsets : nullptr, with_t ? desc->a_params : nullptr,

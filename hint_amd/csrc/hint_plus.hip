@@ -201,7 +201,7 @@ int64_t hint_plus_geometry(int64_t n_rows, int32_t n_points, int32_t field) {
              "3 the grid cap, 4 the most outline points of a row)", field);
         return -1;
     }
-    const int64_t out[5] = {ps_grid(n_rows, 0, PL_MAX_WG), 1, PS_TILE, PL_MAX_WG, PS_MAX_M};
+    const int64_t out[5] = {capped_grid(n_rows, 0, PL_MAX_WG), 1, PS_TILE, PL_MAX_WG, PS_MAX_M};
     return out[field];
 }
 
@@ -218,12 +218,12 @@ int hint_plus_run(const hint_plus_desc* desc, void* stream) {
         return 1;
     if (!(desc->max_dist > 0.f) || !std::isfinite(desc->max_dist))
         return fail("%s: max_dist must be finite and > 0 (got %g)", who, (double)desc->max_dist);
-    if (ps_check_groups(who, desc->max_groups)) return 1;
-    if (ps_check_aligned(who, {{"x", desc->x, 3}, {"b_points", desc->b_points, 3}, {"params", desc->params, 3},
+    if (check_groups(who, desc->max_groups)) return 1;
+    if (check_aligned(who, {{"x", desc->x, 3}, {"b_points", desc->b_points, 3}, {"params", desc->params, 3},
                                {"segments", desc->segments, 3}, {"keep", desc->keep, 3}, {"counts", desc->counts, 3},
                                {"loss", desc->loss, 3}, {"max_h", desc->max_h, 3}, {"avg_h", desc->avg_h, 3}}))
         return 1;
-    const int grid = ps_grid(desc->n_rows, desc->max_groups, PL_MAX_WG);
+    const int grid = capped_grid(desc->n_rows, desc->max_groups, PL_MAX_WG);
     // without a curve output the kernel reads no curve: P = 2 keeps its (unused) sizes in range
     hipLaunchKernelGGL(hint_plus_kernel, dim3(grid), dim3(PS_THREADS), 0, (hipStream_t)stream, with_curve ? desc->x : nullptr,
                        with_curve ? desc->b_points : nullptr, (int)desc->n_rows, with_curve && desc->x ? desc->n_coeffs : 1,

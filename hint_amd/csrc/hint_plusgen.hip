@@ -34,6 +34,7 @@ constexpr int PG_WAVE_ROWS = 64 / PG_LANES;
 constexpr int PG_WAVES = 4;                         // wavefronts of a workgroup
 constexpr int PG_MAX_WG = 2048;                     // the grid cap: 256 CUs x 8
 constexpr long long PG_MAX_N = 1LL << 30;
+constexpr RowGrid PG_GRID{PG_WAVE_ROWS, PG_WAVES, PG_MAX_WG, PG_MAX_N};
 constexpr int PG_K = 25;                            // coefficients per axis (PlusShapeModel.n_parameters / 4)
 constexpr int PG_ROW = 4 * PG_K;
 constexpr int PG_PTS = 128;                         // storage of a dense outline: 54 <= N <= 106 (include/hint_amd.h)
@@ -64,11 +65,6 @@ struct PlusGenArgs {
     int32_t* rejected;
 };
 
-inline int plusgen_groups(long long n, int max_groups) {
-    long long g = ((n + PG_WAVE_ROWS - 1) / PG_WAVE_ROWS + PG_WAVES - 1) / PG_WAVES;
-    const long long cap = max_groups > 0 && max_groups < PG_MAX_WG ? max_groups : PG_MAX_WG;
-    return (int)(g > cap ? cap : g);
-}
 
 // per quadrant, clockwise (upper-left, upper-right, lower-right, lower-left): X the x bar's corner, I the inner corner, Y the y
 // bar's corner, F the reflex corner of the notch.  In the upper-left and lower-right quadrants the x bar's arm comes first
@@ -342,47 +338,35 @@ __global__ __launch_bounds__(256) void hint_plusgen_kernel(const hint::PlusGenAr
 // ---- the C ABI ----
 using namespace hint;
 
-static int plusgen_check_rows(const char* who, int64_t n_rows) {
-    if (n_rows < 1 || n_rows > PG_MAX_N) return fail("%s: n_rows must be 1..%lld (got %lld)", who, PG_MAX_N, (long long)n_rows);
-    return 0;
-}
-
 extern "C" {
 
 size_t hint_plusgen_workspace_bytes(int64_t n_rows) {
-    if (plusgen_check_rows("hint_plusgen_workspace_bytes", n_rows)) return 0;
-    return (size_t)plusgen_groups(n_rows, 0) * PG_WAVES * sizeof(int32_t);
+    if (PG_GRID.check_rows("hint_plusgen_workspace_bytes", n_rows)) return 0;
+    return PG_GRID.ws_bytes(n_rows);
 }
 
 int hint_plusgen_run(const hint_plusgen_desc* desc) {
     const char* who = "hint_plusgen_run";
     if (!desc) return fail("%s: desc is null", who);
     if (!desc->x && !desc->y) return fail("%s: x and y are both null", who);
-    if (!desc->workspace) return fail("%s: workspace is null", who);
-    if (plusgen_check_rows(who, desc->n_rows)) return 1;
+    if (workspace_null(who, desc->workspace)) return 1;
+    if (PG_GRID.check_rows(who, desc->n_rows)) return 1;
     if (desc->rows && desc->draws) return fail("%s: rows and draws are both given (rows name Philox rows)", who);
-    if (!desc->rows && !desc->draws && desc->offset > ~0ull - (uint64_t)desc->n_rows)
-        return fail("%s: offset + n_rows must stay below 2^64", who);
-    if (desc->max_groups < 0) return fail("%s: max_groups must be >= 0 (got %d)", who, desc->max_groups);
+    if (!desc->rows && !desc->draws && check_row_offset(who, desc->offset, desc->n_rows)) return 1;
+    if (check_groups(who, desc->max_groups)) return 1;
     if (desc->target) {
         const float* t = desc->target;
         for (int i = 0; i < 4; ++i)
             if (!std::isfinite(t[i])) return fail("%s: target[%d] is not finite", who, i);
         if (t[3] < 0.25f || t[3] > 4.f) return fail("%s: target[3], the ratio, must be 0.25..4 (got %g)", who, (double)t[3]);
     }
-    if (misaligned(who, "rows", desc->rows, 7)) return 1;
-    if (misaligned(who, "draws", desc->draws, 3)) return 1;
-    if (misaligned(who, "x", desc->x, 15)) return 1;
-    if (misaligned(who, "y", desc->y, 15)) return 1;
-    if (misaligned(who, "outline", desc->outline, 7)) return 1;
-    if (misaligned(who, "counts", desc->counts, 3)) return 1;
-    if (misaligned(who, "corners", desc->corners, 3)) return 1;
-    if (misaligned(who, "draws_out", desc->draws_out, 3)) return 1;
-    if (misaligned(who, "workspace", desc->workspace, 15)) return 1;
-    const int wgs = plusgen_groups(desc->n_rows, desc->max_groups);
-    const size_t need = (size_t)plusgen_groups(desc->n_rows, 0) * PG_WAVES * sizeof(int32_t);
-    if (desc->workspace_bytes < need)
-        return fail("%s: workspace_bytes = %zu is too small (hint_plusgen_workspace_bytes: %zu)", who, desc->workspace_bytes, need);
+    if (check_aligned(who, {{"rows", desc->rows, 7}, {"draws", desc->draws, 3}, {"x", desc->x, 15}, {"y", desc->y, 15},
+                            {"outline", desc->outline, 7}, {"counts", desc->counts, 3}, {"corners", desc->corners, 3},
+                            {"draws_out", desc->draws_out, 3}}))
+        return 1;
+    const int wgs = PG_GRID.groups(desc->n_rows, desc->max_groups);
+    const size_t need = PG_GRID.ws_bytes(desc->n_rows);
+    if (workspace_fits(who, "plusgen", desc->workspace, desc->workspace_bytes, need)) return 1;
     PlusGenArgs a;
     a.n = desc->n_rows;
     a.seed = desc->seed;
@@ -400,8 +384,7 @@ int hint_plusgen_run(const hint_plusgen_desc* desc) {
     a.draws_out = desc->draws_out;
     a.rejected = (int32_t*)desc->workspace;
     hipStream_t s = (hipStream_t)desc->stream;
-    // (a smaller grid than the default one leaves the workspace's tail unwritten: the words of wavefronts that do not exist hold 0)
-    if (wgs * PG_WAVES * sizeof(int32_t) < need) HIP_TRY(hipMemsetAsync(desc->workspace, 0, need, s));
+    if (PG_GRID.clear_tail(wgs, desc, need, s)) return 1;
     hipLaunchKernelGGL(hint_plusgen_kernel, dim3(wgs), dim3(256), 0, s, a, plusgen_tables());
     HIP_TRY(hipGetLastError());
     return 0;

@@ -4,15 +4,14 @@
 // Everything here is part of the contract of include/hint_amd.h - the fp32 order of every operation and the association of the
 // double sums - stated once, so that the kernels give the same bits on the same point sets (tests/test_gpu_plus.py
 // test_the_generated_outline_is_the_host_built_template_bit_for_bit) and keep the ones tests/golden/pointset_bits.npz recorded.
-// The entry points' shared argument checks are here as well, their message texts part of the behaviour.
+// The size and source checks of these kernels' entry points are here as well, their message texts part of the behaviour (the
+// checks every descriptor entry point shares are hint_host.hpp's).
 //   B = the curve: P <= 1024 points in LDS, traced by hint_curve.hip's rule from P - 1 twiddles or given; thread t owns points
 //       t, t + 256, ... (at most PS_PER = 4) and holds them in registers
 //   A = the other set: M <= 4096 points that pass through LDS in tiles of 1024, made by the kernel's `fill`; thread t owns points
 //       t, t + 256, ... of a tile
 //   D(i, j) = fma(dy, dy, dx dx) of A_i - B_j;  mA_i = min_j D,  mB_j = min_i D
 #pragma once
-#include <initializer_list>
-
 #include "hint_host.hpp"
 
 namespace hint {
@@ -23,12 +22,6 @@ constexpr int PS_TILE = 1024;                   // of them in LDS at a time
 constexpr int PS_THREADS = 256, PS_PER = 4;     // PS_PER = PS_MAX_P / PS_THREADS = PS_TILE / PS_THREADS points per thread
 constexpr int PS_WAVES = PS_THREADS / 64;
 constexpr long long PS_MAX_N = 1LL << 30;
-
-// workgroups of a persistent grid over n rows; max_wg: the kernel's cap (CUs x the workgroups its registers let a CU hold)
-inline int ps_grid(long long n, int max_groups, int max_wg) {
-    const long long cap = max_groups > 0 && max_groups < max_wg ? max_groups : max_wg;
-    return (int)(n < cap ? n : cap);
-}
 
 // the size checks of the entry points (with_curve false: the call reads no curve, and only the rows are checked)
 inline int ps_check_sizes(const char* who, int64_t n_rows, int32_t n_coeffs, int32_t n_points, bool traced, bool with_curve = true) {
@@ -46,24 +39,6 @@ inline int ps_check_sizes(const char* who, int64_t n_rows, int32_t n_coeffs, int
 inline int ps_check_source(const char* who, const void* x, const void* b_points, const char* needs) {
     if (x && b_points) return fail("%s: both x and b_points are given (the curve has one source)", who);
     if (needs && !x && !b_points) return fail("%s: x and b_points are both null (%s)", who, needs);
-    return 0;
-}
-
-inline int ps_check_groups(const char* who, int32_t max_groups) {
-    if (max_groups < 0) return fail("%s: max_groups must be >= 0 (got %d)", who, max_groups);
-    return 0;
-}
-
-// the descriptor's pointers, in the order they are reported in (a null pointer is aligned)
-struct ps_ptr {
-    const char* name;
-    const void* p;
-    int mask;
-};
-
-inline int ps_check_aligned(const char* who, std::initializer_list<ps_ptr> ptrs) {
-    for (const ps_ptr& a : ptrs)
-        if (misaligned(who, a.name, a.p, a.mask)) return 1;
     return 0;
 }
 

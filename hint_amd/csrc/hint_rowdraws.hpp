@@ -1,8 +1,11 @@
-// The draws of a sampled row, shared by the shape samplers (hint_shapegen.hip, hint_plusgen.hip).  Internal.
+// The draws of a sampled row, shared by the shape samplers (hint_shapegen.hip, hint_plusgen.hip), and, at the end, the host side
+// their entry points share: the grid, the workspace of rejected-row counts and the checks around them.  Internal.
 // Everything here is part of the contract of include/hint_amd.h (hint_lensgen_desc, hint_plusgen_desc): a row's draws are a
 // function of (seed, row, stream, tag) alone.
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include "hint_host.hpp"
 
 // (hint_curve.hip's: LDS writes of some lanes, reads of others, within one wavefront)
 __device__ __forceinline__ void shapegen_wave_sync() {
@@ -31,3 +34,39 @@ __device__ __forceinline__ float2 row_box_muller(unsigned a, unsigned b) {
     const float r = __builtin_sqrtf(-1.3862943611198906f * __builtin_amdgcn_logf(u0));
     return float2{r * __builtin_amdgcn_cosf(u1), r * __builtin_amdgcn_sinf(u1)};
 }
+
+// ---- the host side of hint_lensgen_run, hint_fcoef_run and hint_plusgen_run ----
+namespace hint {
+
+// a sampler's launch: per_wave items (rows; hint_fcoef_run: rows x harmonics) a wavefront, `waves` wavefronts a workgroup, at
+// most max_wg workgroups, at most max_n rows.  Every wavefront of the grid ends by writing the rows it rejected to its int32
+// of the workspace
+struct RowGrid {
+    int per_wave, waves, max_wg;
+    long long max_n;
+    int groups(long long items, int max_groups) const {
+        const long long g = ((items + per_wave - 1) / per_wave + waves - 1) / waves;
+        const long long cap = max_groups > 0 && max_groups < max_wg ? max_groups : max_wg;
+        return (int)(g > cap ? cap : g);
+    }
+    // the workspace: one int32 per wavefront of the default grid, whatever max_groups a run passes
+    size_t ws_bytes(long long items) const { return (size_t)groups(items, 0) * waves * sizeof(int32_t); }
+    int check_rows(const char* who, int64_t n_rows) const {
+        if (n_rows < 1 || n_rows > max_n) return fail("%s: n_rows must be 1..%lld (got %lld)", who, max_n, (long long)n_rows);
+        return 0;
+    }
+    // a smaller grid than the default one leaves the workspace's tail unwritten: the words of wavefronts that do not exist hold 0
+    template <class Desc>
+    int clear_tail(int wgs, const Desc* desc, size_t need, hipStream_t s) const {
+        if ((size_t)wgs * waves * sizeof(int32_t) < need) HIP_TRY(hipMemsetAsync(desc->workspace, 0, need, s));
+        return 0;
+    }
+};
+
+// rows offset .. offset + n_rows - 1 of a Philox stream
+inline int check_row_offset(const char* who, uint64_t offset, int64_t n_rows) {
+    if (offset > ~0ull - (uint64_t)n_rows) return fail("%s: offset + n_rows must stay below 2^64", who);
+    return 0;
+}
+
+}  // namespace hint

@@ -46,6 +46,8 @@ constexpr float LENS_HALF_B = 4.2937f;              // .. acos(0.9125), seen fro
 constexpr int FCOEF_MAX_P = 1024;
 constexpr long long FCOEF_MAX_N = 1LL << 24;
 constexpr int FCOEF_MAX_WG = 8192;
+constexpr RowGrid LENS_GRID{64, LENS_WAVES, LENS_MAX_WG, LENS_MAX_N};
+constexpr RowGrid FCOEF_GRID{64, 4, FCOEF_MAX_WG, FCOEF_MAX_N};    // an item: a row's harmonic |m|, K / 2 + 1 of them a row
 
 struct LensTables {
     float2 h[2 * LENS_SIDES];                       // (cos, -sin) of 2 pi i / 128: e_j = h[2 j], the outward normal of edge (j, j + 1) = h[2 j + 1]
@@ -65,16 +67,7 @@ struct LensArgs {
     int32_t* rejected;
 };
 
-inline int lens_groups(long long n, int max_groups) {
-    long long g = ((n + 63) / 64 + LENS_WAVES - 1) / LENS_WAVES;
-    const long long cap = max_groups > 0 && max_groups < LENS_MAX_WG ? max_groups : LENS_MAX_WG;
-    return (int)(g > cap ? cap : g);
-}
-inline int fcoef_groups(long long n, int K, int max_groups) {
-    long long g = (n * (K / 2 + 1) + 255) / 256;
-    const long long cap = max_groups > 0 && max_groups < FCOEF_MAX_WG ? max_groups : FCOEF_MAX_WG;
-    return (int)(g > cap ? cap : g);
-}
+inline long long fcoef_items(long long n, int K) { return n * (K / 2 + 1); }
 
 static const LensTables& lens_tables() {
     static const LensTables T = [] {
@@ -281,12 +274,8 @@ __global__ __launch_bounds__(256) void hint_fcoef_kernel(const float2* __restric
 // ---- the C ABI ----
 using namespace hint;
 
-static int lensgen_check_rows(const char* who, int64_t n_rows) {
-    if (n_rows < 1 || n_rows > LENS_MAX_N) return fail("%s: n_rows must be 1..%lld (got %lld)", who, LENS_MAX_N, (long long)n_rows);
-    return 0;
-}
 static int fcoef_check_sizes(const char* who, int64_t n_rows, int32_t p_max, int32_t n_coeffs) {
-    if (n_rows < 1 || n_rows > FCOEF_MAX_N) return fail("%s: n_rows must be 1..%lld (got %lld)", who, FCOEF_MAX_N, (long long)n_rows);
+    if (FCOEF_GRID.check_rows(who, n_rows)) return 1;
     if (n_coeffs < 1 || n_coeffs > FOURIER_MAX_K || n_coeffs % 2 == 0)
         return fail("%s: n_coeffs must be odd, 1..%d (got %d)", who, FOURIER_MAX_K, n_coeffs);
     if (p_max < n_coeffs || p_max > FCOEF_MAX_P) return fail("%s: p_max must be n_coeffs..%d (got %d)", who, FCOEF_MAX_P, p_max);
@@ -296,29 +285,24 @@ static int fcoef_check_sizes(const char* who, int64_t n_rows, int32_t p_max, int
 extern "C" {
 
 size_t hint_lensgen_workspace_bytes(int64_t n_rows) {
-    if (lensgen_check_rows("hint_lensgen_workspace_bytes", n_rows)) return 0;
-    return (size_t)lens_groups(n_rows, 0) * LENS_WAVES * sizeof(int32_t);
+    if (LENS_GRID.check_rows("hint_lensgen_workspace_bytes", n_rows)) return 0;
+    return LENS_GRID.ws_bytes(n_rows);
 }
 
 int hint_lensgen_run(const hint_lensgen_desc* desc, void* stream) {
     const char* who = "hint_lensgen_run";
     if (!desc) return fail("%s: desc is null", who);
     if (!desc->x) return fail("%s: x is null", who);
-    if (!desc->workspace) return fail("%s: workspace is null", who);
-    if (lensgen_check_rows(who, desc->n_rows)) return 1;
-    if (desc->offset > ~0ull - (uint64_t)desc->n_rows) return fail("%s: offset + n_rows must stay below 2^64", who);
-    if (desc->max_groups < 0) return fail("%s: max_groups must be >= 0 (got %d)", who, desc->max_groups);
-    if (misaligned(who, "draws", desc->draws, 15)) return 1;
-    if (misaligned(who, "x", desc->x, 15)) return 1;
-    if (misaligned(who, "ring", desc->ring, 7)) return 1;
-    if (misaligned(who, "counts", desc->counts, 3)) return 1;
-    if (misaligned(who, "eps", desc->eps, 7)) return 1;
-    if (misaligned(who, "draws_out", desc->draws_out, 15)) return 1;
-    if (misaligned(who, "workspace", desc->workspace, 15)) return 1;
-    const int wgs = lens_groups(desc->n_rows, desc->max_groups);
-    const size_t need = (size_t)lens_groups(desc->n_rows, 0) * LENS_WAVES * sizeof(int32_t);
-    if (desc->workspace_bytes < need)
-        return fail("%s: workspace_bytes = %zu is too small (hint_lensgen_workspace_bytes: %zu)", who, desc->workspace_bytes, need);
+    if (workspace_null(who, desc->workspace)) return 1;
+    if (LENS_GRID.check_rows(who, desc->n_rows)) return 1;
+    if (check_row_offset(who, desc->offset, desc->n_rows)) return 1;
+    if (check_groups(who, desc->max_groups)) return 1;
+    if (check_aligned(who, {{"draws", desc->draws, 15}, {"x", desc->x, 15}, {"ring", desc->ring, 7}, {"counts", desc->counts, 3},
+                            {"eps", desc->eps, 7}, {"draws_out", desc->draws_out, 15}}))
+        return 1;
+    const int wgs = LENS_GRID.groups(desc->n_rows, desc->max_groups);
+    const size_t need = LENS_GRID.ws_bytes(desc->n_rows);
+    if (workspace_fits(who, "lensgen", desc->workspace, desc->workspace_bytes, need)) return 1;
     LensArgs a;
     a.n = desc->n_rows;
     a.seed = desc->seed;
@@ -331,8 +315,7 @@ int hint_lensgen_run(const hint_lensgen_desc* desc, void* stream) {
     a.draws_out = (float4*)desc->draws_out;
     a.rejected = (int32_t*)desc->workspace;
     hipStream_t s = (hipStream_t)stream;
-    // (a smaller grid than the default one leaves the workspace's tail unwritten: the words of wavefronts that do not exist hold 0)
-    if (wgs * LENS_WAVES * sizeof(int32_t) < need) HIP_TRY(hipMemsetAsync(desc->workspace, 0, need, s));
+    if (LENS_GRID.clear_tail(wgs, desc, need, s)) return 1;
     hipLaunchKernelGGL(hint_lensgen_kernel, dim3(wgs), dim3(256), 0, s, a, lens_tables());
     HIP_TRY(hipGetLastError());
     return 0;
@@ -340,7 +323,7 @@ int hint_lensgen_run(const hint_lensgen_desc* desc, void* stream) {
 
 size_t hint_fcoef_workspace_bytes(int64_t n_rows, int32_t p_max, int32_t n_coeffs) {
     if (fcoef_check_sizes("hint_fcoef_workspace_bytes", n_rows, p_max, n_coeffs)) return 0;
-    return (size_t)fcoef_groups(n_rows, n_coeffs, 0) * 4 * sizeof(int32_t);
+    return FCOEF_GRID.ws_bytes(fcoef_items(n_rows, n_coeffs));
 }
 
 int hint_fcoef_run(const hint_fcoef_desc* desc, void* stream) {
@@ -348,19 +331,16 @@ int hint_fcoef_run(const hint_fcoef_desc* desc, void* stream) {
     if (!desc) return fail("%s: desc is null", who);
     if (!desc->points) return fail("%s: points is null", who);
     if (!desc->x) return fail("%s: x is null", who);
-    if (!desc->workspace) return fail("%s: workspace is null", who);
+    if (workspace_null(who, desc->workspace)) return 1;
     if (fcoef_check_sizes(who, desc->n_rows, desc->p_max, desc->n_coeffs)) return 1;
-    if (desc->max_groups < 0) return fail("%s: max_groups must be >= 0 (got %d)", who, desc->max_groups);
-    if (misaligned(who, "points", desc->points, 7)) return 1;
-    if (misaligned(who, "counts", desc->counts, 3)) return 1;
-    if (misaligned(who, "x", desc->x, 3)) return 1;
-    if (misaligned(who, "workspace", desc->workspace, 15)) return 1;
-    const int wgs = fcoef_groups(desc->n_rows, desc->n_coeffs, desc->max_groups);
-    const size_t need = (size_t)fcoef_groups(desc->n_rows, desc->n_coeffs, 0) * 4 * sizeof(int32_t);
-    if (desc->workspace_bytes < need)
-        return fail("%s: workspace_bytes = %zu is too small (hint_fcoef_workspace_bytes: %zu)", who, desc->workspace_bytes, need);
+    if (check_groups(who, desc->max_groups)) return 1;
+    if (check_aligned(who, {{"points", desc->points, 7}, {"counts", desc->counts, 3}, {"x", desc->x, 3}})) return 1;
+    const long long items = fcoef_items(desc->n_rows, desc->n_coeffs);
+    const int wgs = FCOEF_GRID.groups(items, desc->max_groups);
+    const size_t need = FCOEF_GRID.ws_bytes(items);
+    if (workspace_fits(who, "fcoef", desc->workspace, desc->workspace_bytes, need)) return 1;
     hipStream_t s = (hipStream_t)stream;
-    if ((size_t)wgs * 4 * sizeof(int32_t) < need) HIP_TRY(hipMemsetAsync(desc->workspace, 0, need, s));
+    if (FCOEF_GRID.clear_tail(wgs, desc, need, s)) return 1;
     hipLaunchKernelGGL(hint_fcoef_kernel, dim3(wgs), dim3(256), 0, s, (const float2*)desc->points, desc->counts, (long long)desc->n_rows,
                        desc->p_max, desc->n_coeffs, desc->x, (int32_t*)desc->workspace);
     HIP_TRY(hipGetLastError());

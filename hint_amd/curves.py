@@ -26,6 +26,7 @@ import torch
 
 from . import _lib
 from ._lib import HintAmdError
+from ._ops import _check_no_grad, _check_real, _outputs, _run_desc
 
 __all__ = ["curve_features", "lens_forward_process", "target_distances", "mean_target_distance",
            "trace_fourier_curves", "hausdorff_distances", "chamfer_distances", "lens_fit_loss",
@@ -72,17 +73,6 @@ def _check_points(v, who: str, most: int = MAX_POINTS) -> int:
     return v
 
 
-def _check_real(v, name: str, who: str, nonneg: bool = True) -> float:
-    if isinstance(v, bool) or not isinstance(v, (int, float)):
-        raise HintAmdError(f"{who}: {name} must be a number (got {type(v).__name__})")
-    v = float(v)
-    if v != v or v in (float("inf"), float("-inf")):
-        raise HintAmdError(f"{who}: {name} must be finite (got {v})")
-    if nonneg and v < 0.0:
-        raise HintAmdError(f"{who}: {name} must be >= 0 (got {v})")
-    return v
-
-
 def _check_weight(v, name: str, who: str) -> float:
     """the weight of a loss's second term: any number but NaN (an infinite one included)"""
     if isinstance(v, bool) or not isinstance(v, (int, float)) or v != v:
@@ -124,18 +114,6 @@ def _noise_args(x: torch.Tensor, noise, eps, generator, who: str):
     return noise, torch.randn(x.shape[0], 2, device=x.device, dtype=torch.float32, generator=generator)
 
 
-def _outputs(desc, table, want, out, dev):
-    """the outputs named in `want` as a dict, by table = name -> (shape, dtype): the tensor `out` holds under the name (the tests'
-    guarded buffers) or a new one.  Sets the descriptor's pointer of every name of the table, None where it is not wanted"""
-    res = {}
-    for name in want:
-        shape, dtype = table[name]
-        res[name] = out[name] if out is not None and name in out else torch.empty(shape, dtype=dtype, device=dev)
-    for name in table:
-        setattr(desc, name, res[name].data_ptr() if name in res else None)
-    return res
-
-
 def _set_curve(desc, curve: Optional[torch.Tensor], n: int, k: int, p: int):
     """the descriptor's rows and curve source: curve [N, 4K] coefficients traced at p points, or (k = 0) [N, p, 2] points; None:
     the call reads no curve"""
@@ -150,29 +128,19 @@ _F32, _I32 = torch.float32, torch.int32
 def _run(x: torch.Tensor, n_points: int, eps: Optional[torch.Tensor] = None, noise: float = 0.0,
          target: Optional[torch.Tensor] = None, want_dist: bool = False, want_mean: bool = False, max_groups: int = 0):
     """one hint_curve_run on checked arguments: (y [N, 2], dist [N] or None, mean 0-dim or None)"""
-    lib = _lib.load()
     n, c = x.shape
-    with torch.cuda.device(x.device):
-        desc = _lib.CurveDesc()
-        desc.x, desc.n_rows, desc.n_coeffs, desc.n_points = x.data_ptr(), n, c // 4, n_points
-        desc.eps, desc.noise = (eps.data_ptr() if eps is not None else None), noise
-        desc.target = target.data_ptr() if target is not None else None
-        want = ["y"]
-        if want_dist:
-            want.append("dist")
-        if want_mean:
-            want.append("mean")
-        res = _outputs(desc, dict(y=((n, 2), _F32), dist=((n,), _F32), mean=((), _F32)), want, None, x.device)
-        desc.max_groups = max_groups
-        ws = None
-        if want_mean:
-            nbytes = lib.hint_curve_workspace_bytes(n, c // 4, n_points)
-            if nbytes == 0:
-                _lib.check(1, "hint_curve_workspace_bytes")
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
-            desc.workspace, desc.workspace_bytes = ws.data_ptr(), nbytes
-        st = lib.hint_curve_run(desc, torch.cuda.current_stream(x.device).cuda_stream)
-    _lib.check(st, "hint_curve_run")
+    desc = _lib.CurveDesc()
+    desc.x, desc.n_rows, desc.n_coeffs, desc.n_points = x.data_ptr(), n, c // 4, n_points
+    desc.eps, desc.noise = (eps.data_ptr() if eps is not None else None), noise
+    desc.target = target.data_ptr() if target is not None else None
+    want = ["y"]
+    if want_dist:
+        want.append("dist")
+    if want_mean:
+        want.append("mean")
+    res = _outputs(desc, dict(y=((n, 2), _F32), dist=((n,), _F32), mean=((), _F32)), want, None, x.device)
+    desc.max_groups = max_groups
+    _run_desc("hint_curve_run", desc, x.device, (n, c // 4, n_points) if want_mean else None)      # (only the mean needs a workspace)
     return res["y"], res.get("dist"), res.get("mean")
 
 
@@ -232,12 +200,6 @@ MAX_TEMPLATE_POINTS = 4096
 
 def _check_dense_points(v, who: str) -> int:
     return _check_points(v, who, MAX_DENSE_POINTS)
-
-
-def _check_no_grad(t: torch.Tensor, name: str, who: str) -> None:
-    if t.requires_grad and torch.is_grad_enabled():
-        raise HintAmdError(f"{who}: {name} requires grad, and no gradient is implemented; call it under torch.no_grad() or "
-                           "detach the input")
 
 
 def _check_dev_tensor(t, name: str, who: str, device=None) -> torch.Tensor:
@@ -342,27 +304,23 @@ def _hd_run(curve: torch.Tensor, k: int, p: int, template: Optional[torch.Tensor
     """one hint_hausdorff_run on checked arguments: (max_h [N], avg_h [N], chamfer [N, 2], points [N, P, 2]), None where not asked.
     k = 0: curve is [N, P, 2] points.  template None (points alone): the kernel then reads no template, and the descriptor names
     the first two floats of curve as one"""
-    lib = _lib.load()
     n, dev = curve.shape[0], curve.device
-    with torch.cuda.device(dev):
-        desc = _lib.HausdorffDesc()
-        _set_curve(desc, curve, n, k, p)
-        desc.a_points = template.data_ptr() if template is not None else curve.data_ptr()
-        desc.n_template = template.shape[0] if template is not None else 1
-        desc.a_offsets = offsets.data_ptr() if offsets is not None else None
-        desc.a_params = params.data_ptr() if params is not None else None
-        want = []
-        if want_h:
-            want += ["max_h", "avg_h"]
-        if want_chamfer:
-            want.append("chamfer")
-        if want_points:
-            want.append("points")
-        res = _outputs(desc, dict(max_h=((n,), _F32), avg_h=((n,), _F32), chamfer=((n, 2), _F32), points=((n, p, 2), _F32)),
-                       want, None, dev)
-        desc.max_groups = max_groups
-        st = lib.hint_hausdorff_run(desc, torch.cuda.current_stream(dev).cuda_stream)
-    _lib.check(st, "hint_hausdorff_run")
+    desc = _lib.HausdorffDesc()
+    _set_curve(desc, curve, n, k, p)
+    desc.a_points = template.data_ptr() if template is not None else curve.data_ptr()
+    desc.n_template = template.shape[0] if template is not None else 1
+    desc.a_offsets = offsets.data_ptr() if offsets is not None else None
+    desc.a_params = params.data_ptr() if params is not None else None
+    want = []
+    if want_h:
+        want += ["max_h", "avg_h"]
+    if want_chamfer:
+        want.append("chamfer")
+    if want_points:
+        want.append("points")
+    res = _outputs(desc, dict(max_h=((n,), _F32), avg_h=((n,), _F32), chamfer=((n, 2), _F32), points=((n, p, 2), _F32)), want, None, dev)
+    desc.max_groups = max_groups
+    _run_desc("hint_hausdorff_run", desc, dev)
     return res.get("max_h"), res.get("avg_h"), res.get("chamfer"), res.get("points")
 
 
@@ -466,16 +424,13 @@ def _plus_run(params: torch.Tensor, curve: Optional[torch.Tensor] = None, k: int
     """one hint_plus_run on checked arguments: a dict of the outputs named in `want` (segments [N, 12, 2, 2], keep [N] int32,
     counts [N, 12] int32, loss [N, 2], max_h [N], avg_h [N]).  k = 0: curve is [N, P, 2] points; curve None: no curve output.
     out: tensors to write into instead of new ones (the tests' guarded buffers)"""
-    lib = _lib.load()
     n, dev = params.shape[0], params.device
-    with torch.cuda.device(dev):
-        desc = _lib.PlusDesc()
-        _set_curve(desc, curve, n, k, p)
-        desc.params, desc.max_dist, desc.max_groups = params.data_ptr(), max_dist, max_groups
-        res = _outputs(desc, dict(segments=((n, 12, 2, 2), _F32), keep=((n,), _I32), counts=((n, 12), _I32), loss=((n, 2), _F32),
-                                  max_h=((n,), _F32), avg_h=((n,), _F32)), want, out, dev)
-        st = lib.hint_plus_run(desc, torch.cuda.current_stream(dev).cuda_stream)
-    _lib.check(st, "hint_plus_run")
+    desc = _lib.PlusDesc()
+    _set_curve(desc, curve, n, k, p)
+    desc.params, desc.max_dist, desc.max_groups = params.data_ptr(), max_dist, max_groups
+    res = _outputs(desc, dict(segments=((n, 12, 2, 2), _F32), keep=((n,), _I32), counts=((n, 12), _I32), loss=((n, 2), _F32),
+                              max_h=((n,), _F32), avg_h=((n,), _F32)), want, out, dev)
+    _run_desc("hint_plus_run", desc, dev)
     return res
 
 
@@ -573,23 +528,20 @@ def _fit_run(desc_cls, entry: str, n_params: int, fields: dict, curve: torch.Ten
              n_steps: int, lr: float, angle_lr: float, gamma: float, momentum: float, want, max_groups: int, out):
     """one run of a fit's entry point on checked arguments, what _lf_run and _pf_run share: a dict of the outputs named in `want`.
     fields: the descriptor's fields beside the curve, the starts and the schedule (a trace record is 2 n_params + 1 floats)"""
-    lib = _lib.load()
     n, dev, s = curve.shape[0], curve.device, starts.shape[1]
-    with torch.cuda.device(dev):
-        desc = desc_cls()
-        _set_curve(desc, curve, n, k, p)
-        desc.starts, desc.n_starts, desc.n_steps = starts.data_ptr(), s, n_steps
-        desc.lr, desc.angle_lr, desc.gamma, desc.momentum = lr, angle_lr, gamma, momentum
-        for name, v in fields.items():
-            setattr(desc, name, v)
-        table = dict(params=((n, n_params), _F32), loss=((n,), _F32), best=((n,), _I32), all_params=((n, s, n_params), _F32),
-                     all_loss=((n, s), _F32), grad=((n, s, n_params), _F32), trace=((n, s, n_steps, 2 * n_params + 1), _F32))
-        if hasattr(desc, "n_run"):
-            table["n_run"] = ((n,), _I32)
-        res = _outputs(desc, table, want, out, dev)
-        desc.max_groups = max_groups
-        st = getattr(lib, entry)(desc, torch.cuda.current_stream(dev).cuda_stream)
-    _lib.check(st, entry)
+    desc = desc_cls()
+    _set_curve(desc, curve, n, k, p)
+    desc.starts, desc.n_starts, desc.n_steps = starts.data_ptr(), s, n_steps
+    desc.lr, desc.angle_lr, desc.gamma, desc.momentum = lr, angle_lr, gamma, momentum
+    for name, v in fields.items():
+        setattr(desc, name, v)
+    table = dict(params=((n, n_params), _F32), loss=((n,), _F32), best=((n,), _I32), all_params=((n, s, n_params), _F32),
+                 all_loss=((n, s), _F32), grad=((n, s, n_params), _F32), trace=((n, s, n_steps, 2 * n_params + 1), _F32))
+    if hasattr(desc, "n_run"):
+        table["n_run"] = ((n,), _I32)
+    res = _outputs(desc, table, want, out, dev)
+    desc.max_groups = max_groups
+    _run_desc(entry, desc, dev)
     return res
 
 
@@ -917,20 +869,17 @@ def _ov_run(curve: torch.Tensor, k: int, p: int, polygon: Optional[torch.Tensor]
     the curve, of the intersection; iou [N]; dice [N]; crossings [N] int32).  k = 0: curve is [N, P, 2] points.  The template is
     polygon (with offsets, params as in _hd_run) or the outline of plus_params [N, 9]; neither: crossings alone.
     out: tensors to write into instead of new ones (the tests' guarded buffers)"""
-    lib = _lib.load()
     n, dev = curve.shape[0], curve.device
-    with torch.cuda.device(dev):
-        desc = _lib.OverlapDesc()
-        _set_curve(desc, curve, n, k, p)
-        desc.a_points = polygon.data_ptr() if polygon is not None else None
-        desc.n_template = polygon.shape[0] if polygon is not None else 0
-        desc.a_offsets = offsets.data_ptr() if offsets is not None else None
-        desc.a_params = params.data_ptr() if params is not None else None
-        desc.plus_params = plus_params.data_ptr() if plus_params is not None else None
-        res = _outputs(desc, dict(areas=((n, 3), _F32), iou=((n,), _F32), dice=((n,), _F32), crossings=((n,), _I32)), want, out, dev)
-        desc.max_groups = max_groups
-        st = lib.hint_overlap_run(desc, torch.cuda.current_stream(dev).cuda_stream)
-    _lib.check(st, "hint_overlap_run")
+    desc = _lib.OverlapDesc()
+    _set_curve(desc, curve, n, k, p)
+    desc.a_points = polygon.data_ptr() if polygon is not None else None
+    desc.n_template = polygon.shape[0] if polygon is not None else 0
+    desc.a_offsets = offsets.data_ptr() if offsets is not None else None
+    desc.a_params = params.data_ptr() if params is not None else None
+    desc.plus_params = plus_params.data_ptr() if plus_params is not None else None
+    res = _outputs(desc, dict(areas=((n, 3), _F32), iou=((n,), _F32), dice=((n,), _F32), crossings=((n,), _I32)), want, out, dev)
+    desc.max_groups = max_groups
+    _run_desc("hint_overlap_run", desc, dev)
     return res
 
 

@@ -17,6 +17,7 @@ from torch.autograd.function import once_differentiable
 
 from . import _lib
 from . import hint as _hint
+from ._ops import _run_desc
 from .hint import HintAmdError, _mark_launch
 
 MAX_D, MAX_N, MAX_B = 128, 256, 1 << 22
@@ -25,24 +26,15 @@ MAX_D, MAX_N, MAX_B = 128, 256, 1 << 22
 def _run(op: int, dev, *, B: int = 1, d: int, n: int = 1, transpose: bool = False, Vs=None, W=None, x=None, y=None, g_y=None,
          g_x=None, g_W=None, g_V=None, workspace=None):
     """one hint_householder_run on the current stream of `dev`; a grad run without a workspace allocates what it needs"""
-    lib = _lib.load()
     ptr = lambda t: t.data_ptr() if t is not None else None
-    with torch.cuda.device(dev):
-        desc = _lib.HouseholderDesc()
-        desc.op, desc.transpose, desc.B, desc.d, desc.n = op, int(bool(transpose)), B, d, n
-        desc.Vs, desc.W, desc.x, desc.y = ptr(Vs), ptr(W), ptr(x), ptr(y)
-        desc.g_y, desc.g_x, desc.g_W, desc.g_V = ptr(g_y), ptr(g_x), ptr(g_W), ptr(g_V)
-        if op == _lib.HOUSEHOLDER_GRAD and workspace is None and (g_W is not None or g_V is not None):
-            nbytes = lib.hint_householder_workspace_bytes(op, B, d, n)
-            if nbytes == 0:
-                _lib.check(1, "hint_householder_workspace_bytes")
-            workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        if workspace is not None:
-            desc.workspace, desc.workspace_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
-        desc.stream = torch.cuda.current_stream(dev).cuda_stream
-        _mark_launch()
-        st = lib.hint_householder_run(desc)
-    _lib.check(st, "hint_householder_run")
+    desc = _lib.HouseholderDesc()
+    desc.op, desc.transpose, desc.B, desc.d, desc.n = op, int(bool(transpose)), B, d, n
+    desc.Vs, desc.W, desc.x, desc.y = ptr(Vs), ptr(W), ptr(x), ptr(y)
+    desc.g_y, desc.g_x, desc.g_W, desc.g_V = ptr(g_y), ptr(g_x), ptr(g_W), ptr(g_V)
+    if workspace is not None:
+        desc.workspace, desc.workspace_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
+    needs_ws = op == _lib.HOUSEHOLDER_GRAD and workspace is None and (g_W is not None or g_V is not None)
+    _run_desc("hint_householder_run", desc, dev, (op, B, d, n) if needs_ws else None, before=_mark_launch)
 
 
 def _check_rows(x, d: int, what: str) -> torch.Tensor:

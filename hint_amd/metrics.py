@@ -20,6 +20,7 @@ import torch
 
 from . import _lib
 from ._lib import HintAmdError
+from ._ops import _run_desc
 
 __all__ = ["multi_mmd", "MultiMMD", "DEFAULT_WIDTHS_EXPONENTS", "mmd_jobs", "corrcoef", "corr_mse", "CorrelationTarget", "corr_jobs"]
 
@@ -71,22 +72,15 @@ def _check_pair(x: torch.Tensor, y: torch.Tensor):
 
 def _run(x: torch.Tensor, y: torch.Tensor, ks, yy=None) -> torch.Tensor:
     """out = [MMD, mean XX, mean YY, mean XY] of checked fp32 sets on one device (yy: a device float, mean YY known)"""
-    lib = _lib.load()
     n_x, n_y, d = x.shape[0], y.shape[0], x.shape[1]
-    nbytes = lib.hint_mmd_workspace_bytes(n_x, n_y, d)
-    if nbytes == 0:
-        _lib.check(1, "hint_mmd_workspace_bytes")
-    with torch.cuda.device(x.device):
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
-        out = torch.empty(4, dtype=torch.float32, device=x.device)
-        desc = _lib.MmdDesc()
-        desc.x, desc.y, desc.n_x, desc.n_y, desc.d, desc.n_kernels = x.data_ptr(), y.data_ptr(), n_x, n_y, d, len(ks)
-        for k, (C, a) in enumerate(ks):
-            desc.width[k], desc.exponent[k] = C, a
-        desc.yy = None if yy is None else yy.data_ptr()
-        desc.out, desc.workspace, desc.workspace_bytes = out.data_ptr(), ws.data_ptr(), nbytes
-        st = lib.hint_mmd_run(desc, torch.cuda.current_stream(x.device).cuda_stream)
-    _lib.check(st, "hint_mmd_run")
+    out = torch.empty(4, dtype=torch.float32, device=x.device)
+    desc = _lib.MmdDesc()
+    desc.x, desc.y, desc.n_x, desc.n_y, desc.d, desc.n_kernels = x.data_ptr(), y.data_ptr(), n_x, n_y, d, len(ks)
+    for k, (C, a) in enumerate(ks):
+        desc.width[k], desc.exponent[k] = C, a
+    desc.yy = None if yy is None else yy.data_ptr()
+    desc.out = out.data_ptr()
+    _run_desc("hint_mmd_run", desc, x.device, (n_x, n_y, d))
     return out
 
 
@@ -158,22 +152,15 @@ def _check_target(t, d: int, device, who: str) -> torch.Tensor:
 
 def _corr_run(x: torch.Tensor, target, want_corr: bool):
     """(out[4], corr or None) of a checked fp32 x and a checked float64 target (or None) on x's device"""
-    lib = _lib.load()
     n, d = x.shape
-    nbytes = lib.hint_corr_workspace_bytes(n, d)
-    if nbytes == 0:
-        _lib.check(1, "hint_corr_workspace_bytes")
-    with torch.cuda.device(x.device):
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
-        out = torch.empty(4, dtype=torch.float64, device=x.device)
-        corr = torch.empty((d, d), dtype=torch.float64, device=x.device) if want_corr else None
-        desc = _lib.CorrDesc()
-        desc.x, desc.n, desc.d = x.data_ptr(), n, d
-        desc.target = None if target is None else target.data_ptr()
-        desc.corr = None if corr is None else corr.data_ptr()
-        desc.out, desc.workspace, desc.workspace_bytes = out.data_ptr(), ws.data_ptr(), nbytes
-        st = lib.hint_corr_run(desc, torch.cuda.current_stream(x.device).cuda_stream)
-    _lib.check(st, "hint_corr_run")
+    out = torch.empty(4, dtype=torch.float64, device=x.device)
+    corr = torch.empty((d, d), dtype=torch.float64, device=x.device) if want_corr else None
+    desc = _lib.CorrDesc()
+    desc.x, desc.n, desc.d = x.data_ptr(), n, d
+    desc.target = None if target is None else target.data_ptr()
+    desc.corr = None if corr is None else corr.data_ptr()
+    desc.out = out.data_ptr()
+    _run_desc("hint_corr_run", desc, x.device, (n, d))
     return out, corr
 
 

@@ -23,38 +23,19 @@ import torch
 
 from . import _lib
 from ._lib import HintAmdError
-from .curves import _check_no_grad, _check_real, _outputs
-from .shapes import _check_device, _check_int, _rejected
+from ._ops import MAX_SAMPLE_ROWS, _check_device, _check_draws, _check_int, _check_real, _outputs, _rejected, _run_desc, _sample_args
 
 __all__ = ["sample_plus_prior", "sample_plus_joint", "sample_plus_targeted", "sample_plus_conditional", "plus_outlines",
            "plus_draws"]
 
-MAX_ROWS = 1 << 30
+MAX_ROWS = MAX_SAMPLE_ROWS
 OUTLINE_POINTS = 128
-N_DRAWS = 9
+_DRAWS = ("u_xl", "u_yl", "u_xw", "u_yw", "u_xs", "u_ys", "u_a", "n_x", "n_y")
+N_DRAWS = len(_DRAWS)
 _F32, _I32 = torch.float32, torch.int32
 _TABLE = lambda n: dict(x=((n, 100), _F32), y=((n, 4), _F32), outline=((n, OUTLINE_POINTS, 2), _F32), counts=((n,), _I32),  # noqa: E731
                         corners=((n,), _I32), draws_out=((n, N_DRAWS), _F32))
 _REFUSED = "a uniform outside [0, 1], or a draw that is not finite"
-
-
-def _check_draws(draws, n: Optional[int], who: str) -> torch.Tensor:
-    if not isinstance(draws, torch.Tensor):
-        raise HintAmdError(f"{who}: draws must be a tensor (got {type(draws).__name__})")
-    if draws.dim() != 2 or draws.shape[1] != N_DRAWS or draws.shape[0] < 1 or draws.shape[0] > MAX_ROWS:
-        raise HintAmdError(f"{who}: draws must be [1..{MAX_ROWS}, 9] = (u_xl, u_yl, u_xw, u_yw, u_xs, u_ys, u_a, n_x, n_y) "
-                           f"(got shape {tuple(draws.shape)})")
-    if n is not None and draws.shape[0] != n:
-        raise HintAmdError(f"{who}: draws holds {draws.shape[0]} rows and n is {n}")
-    if not draws.is_cuda:
-        raise HintAmdError(f"{who}: draws is on {draws.device}; the sampler is a GPU kernel and there is no CPU fallback")
-    if not draws.is_floating_point():
-        raise HintAmdError(f"{who}: draws is {draws.dtype}; expected a floating-point tensor")
-    _check_no_grad(draws, "draws", who)
-    draws = draws.detach()
-    if draws.dtype != torch.float32 or not draws.is_contiguous():
-        draws = draws.to(torch.float32).contiguous()
-    return draws
 
 
 def _check_target(target, who: str):
@@ -80,41 +61,20 @@ def _check_target(target, who: str):
     return t
 
 
-def _sample_args(n, seed, offset, device, draws, who: str):
-    n = _check_int(n, "n", who, 1, MAX_ROWS)
-    seed = _check_int(seed, "seed", who, 0, 2 ** 64 - 1)
-    offset = _check_int(offset, "offset", who, 0, 2 ** 64 - 1 - n)
-    if draws is not None:
-        draws = _check_draws(draws, n, who)
-        if device is not None and _check_device(device, who) != draws.device:
-            raise HintAmdError(f"{who}: draws is on {draws.device} and device is {device}")
-        return n, seed, offset, draws.device, draws
-    return n, seed, offset, _check_device(device, who), None
-
-
 def _plus_run(n: int, seed: int, offset: int, dev: torch.device, draws: Optional[torch.Tensor], want, target=None,
               rows: Optional[torch.Tensor] = None, out=None, max_groups: int = 0, who: str = "hint_plusgen_run"):
     """one hint_plusgen_run on checked arguments: the outputs named in `want` as a dict (`out`: the tests' guarded buffers).
     rows: uint64-as-int64 [n] on the device, the Philox rows of a gather"""
-    lib = _lib.load()
-    with torch.cuda.device(dev):
-        desc = _lib.PlusGenDesc()
-        desc.n_rows, desc.seed, desc.offset, desc.max_groups = n, seed, offset, max_groups
-        desc.draws = draws.data_ptr() if draws is not None else None
-        desc.rows = rows.data_ptr() if rows is not None else None
-        tgt = (C.c_float * 4)(*target) if target is not None else None          # (read during the call; alive until it returns)
-        desc.target = tgt
-        res = _outputs(desc, _TABLE(n), want, out, dev)
-        nbytes = lib.hint_plusgen_workspace_bytes(n)
-        if nbytes == 0:
-            _lib.check(1, "hint_plusgen_workspace_bytes")
-        ws = out["workspace"] if out is not None and "workspace" in out else torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        desc.workspace, desc.workspace_bytes = ws.data_ptr(), nbytes
-        desc.stream = torch.cuda.current_stream(dev).cuda_stream
-        st = lib.hint_plusgen_run(desc)
-    _lib.check(st, "hint_plusgen_run")
+    desc = _lib.PlusGenDesc()
+    desc.n_rows, desc.seed, desc.offset, desc.max_groups = n, seed, offset, max_groups
+    desc.draws = draws.data_ptr() if draws is not None else None
+    desc.rows = rows.data_ptr() if rows is not None else None
+    tgt = (C.c_float * 4)(*target) if target is not None else None              # (read during the call; alive until it returns)
+    desc.target = tgt
+    res = _outputs(desc, _TABLE(n), want, out, dev)
+    ws = _run_desc("hint_plusgen_run", desc, dev, (n,), out)
     if draws is not None:
-        _rejected(ws[:nbytes], _REFUSED, who)
+        _rejected(ws[:desc.workspace_bytes], _REFUSED, who)
     res["workspace"] = ws
     return res
 
@@ -126,7 +86,7 @@ def sample_plus_prior(n: int, seed: int, *, offset: int = 0, device=None, draws:
     the rows are checked, which reads one number back).  return_outline: (x, outline [n, 128, 2], counts [n]) - the dense, placed,
     zero-padded outline x is made of"""
     who = "sample_plus_prior"
-    n, seed, offset, dev, draws = _sample_args(n, seed, offset, device, draws, who)
+    n, seed, offset, dev, draws = _sample_args(n, seed, offset, device, draws, who, _DRAWS)
     res = _plus_run(n, seed, offset, dev, draws, ["x", "outline", "counts"] if return_outline else ["x"], who=who)
     return (res["x"], res["outline"], res["counts"]) if return_outline else res["x"]
 
@@ -135,7 +95,7 @@ def sample_plus_joint(n: int, seed: int, *, offset: int = 0, device=None, draws:
     """the reference's PlusShapeModel.sample_joint(n): (x [n, 100], y [n, 4]) in one launch, y = (center_x, center_y, angle,
     xwidth / ywidth); x is sample_plus_prior's, bit for bit"""
     who = "sample_plus_joint"
-    n, seed, offset, dev, draws = _sample_args(n, seed, offset, device, draws, who)
+    n, seed, offset, dev, draws = _sample_args(n, seed, offset, device, draws, who, _DRAWS)
     res = _plus_run(n, seed, offset, dev, draws, ["x", "y"], who=who)
     return res["x"], res["y"]
 
@@ -147,7 +107,7 @@ def sample_plus_targeted(n: int, seed: int, target, *, offset: int = 0, device=N
     target = _check_target(target, who)
     if target is None:
         raise HintAmdError(f"{who}: target must be 4 numbers (cx, cy, angle, ratio) (got None)")
-    n, seed, offset, dev, draws = _sample_args(n, seed, offset, device, draws, who)
+    n, seed, offset, dev, draws = _sample_args(n, seed, offset, device, draws, who, _DRAWS)
     res = _plus_run(n, seed, offset, dev, draws, ["x", "y"], target=target, who=who)
     return res["x"], res["y"]
 
@@ -158,7 +118,7 @@ def plus_outlines(draws: torch.Tensor, target=None):
     fourier_coeffs(outline, 25, counts) is sample_plus_prior's x up to rounding"""
     who = "plus_outlines"
     target = _check_target(target, who)
-    draws = _check_draws(draws, None, who)
+    draws = _check_draws(draws, None, who, _DRAWS)
     res = _plus_run(draws.shape[0], 0, 0, draws.device, draws, ["y", "outline", "counts"], target=target, who=who)
     return res["outline"], res["counts"], res["y"]
 
@@ -166,7 +126,7 @@ def plus_outlines(draws: torch.Tensor, target=None):
 def plus_draws(n: int, seed: int, *, offset: int = 0, device=None) -> torch.Tensor:
     """the draws sample_plus_prior(n, seed, offset=offset) uses, [n, 9]"""
     who = "plus_draws"
-    n, seed, offset, dev, _ = _sample_args(n, seed, offset, device, None, who)
+    n, seed, offset, dev, _ = _sample_args(n, seed, offset, device, None, who, _DRAWS)
     return _plus_run(n, seed, offset, dev, None, ["y", "draws_out"], who=who)["draws_out"]
 
 

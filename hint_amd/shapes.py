@@ -20,97 +20,32 @@ import torch
 
 from . import _lib
 from ._lib import HintAmdError
-from .curves import _check_no_grad, _check_real, _outputs, lens_forward_process
+from ._ops import MAX_SAMPLE_ROWS, _check_draws, _check_no_grad, _check_real, _outputs, _rejected, _run_desc, _sample_args
+from .curves import lens_forward_process
 
 __all__ = ["sample_lens_prior", "sample_lens_joint", "lens_rings", "lens_draws", "fourier_coeffs"]
 
-MAX_ROWS = 1 << 30
+MAX_ROWS = MAX_SAMPLE_ROWS
 RING_POINTS = 32
 MAX_COEFFS = 25
 MAX_POINTS = 1024
 MAX_POINT_ROWS = 1 << 24
 _F32, _I32 = torch.float32, torch.int32
+_DRAWS = ("u_r", "u_t", "n_x", "n_y")
 _LENS_TABLE = lambda n: dict(x=((n, 20), _F32), ring=((n, RING_POINTS, 2), _F32), counts=((n,), _I32), eps=((n, 2), _F32),  # noqa: E731
                              draws_out=((n, 4), _F32))
-
-
-def _check_int(v, name: str, who: str, lo: int, hi: int) -> int:
-    if isinstance(v, bool) or not isinstance(v, int):
-        raise HintAmdError(f"{who}: {name} must be an int (got {type(v).__name__})")
-    if v < lo or v > hi:
-        raise HintAmdError(f"{who}: {name} must be {lo}..{hi} (got {v})")
-    return v
-
-
-def _check_device(device, who: str) -> torch.device:
-    if device is None:
-        if not torch.cuda.is_available():
-            raise HintAmdError(f"{who}: no GPU is available; the sampler is a GPU kernel and there is no CPU fallback")
-        return torch.device("cuda", torch.cuda.current_device())
-    try:
-        dev = torch.device(device)
-    except (TypeError, RuntimeError) as e:
-        raise HintAmdError(f"{who}: device must name a device (got {device!r})") from e
-    if dev.type != "cuda":
-        raise HintAmdError(f"{who}: device is {dev}; the sampler is a GPU kernel and there is no CPU fallback")
-    return dev if dev.index is not None else torch.device("cuda", torch.cuda.current_device())
-
-
-def _check_draws(draws, n: Optional[int], who: str) -> torch.Tensor:
-    if not isinstance(draws, torch.Tensor):
-        raise HintAmdError(f"{who}: draws must be a tensor (got {type(draws).__name__})")
-    if draws.dim() != 2 or draws.shape[1] != 4 or draws.shape[0] < 1 or draws.shape[0] > MAX_ROWS:
-        raise HintAmdError(f"{who}: draws must be [1..{MAX_ROWS}, 4] = (u_r, u_t, n_x, n_y) (got shape {tuple(draws.shape)})")
-    if n is not None and draws.shape[0] != n:
-        raise HintAmdError(f"{who}: draws holds {draws.shape[0]} rows and n is {n}")
-    if not draws.is_cuda:
-        raise HintAmdError(f"{who}: draws is on {draws.device}; the sampler is a GPU kernel and there is no CPU fallback")
-    if not draws.is_floating_point():
-        raise HintAmdError(f"{who}: draws is {draws.dtype}; expected a floating-point tensor")
-    _check_no_grad(draws, "draws", who)
-    draws = draws.detach()
-    if draws.dtype != torch.float32 or not draws.is_contiguous():
-        draws = draws.to(torch.float32).contiguous()
-    return draws
-
-
-def _sample_args(n, seed, offset, device, draws, who: str):
-    n = _check_int(n, "n", who, 1, MAX_ROWS)
-    seed = _check_int(seed, "seed", who, 0, 2 ** 64 - 1)
-    offset = _check_int(offset, "offset", who, 0, 2 ** 64 - 1 - n)
-    if draws is not None:
-        draws = _check_draws(draws, n, who)
-        if device is not None and _check_device(device, who) != draws.device:
-            raise HintAmdError(f"{who}: draws is on {draws.device} and device is {device}")
-        return n, seed, offset, draws.device, draws
-    return n, seed, offset, _check_device(device, who), None
-
-
-def _rejected(ws: torch.Tensor, what: str, who: str) -> None:
-    """the one host read of the paths that take rows from the caller: the workspace's words add up to the rejected rows"""
-    bad = int(ws.view(torch.int32).sum().item())
-    if bad:
-        raise HintAmdError(f"{who}: {bad} row(s) rejected: {what}")
 
 
 def _lens_run(n: int, seed: int, offset: int, dev: torch.device, draws: Optional[torch.Tensor], want, out=None,
               max_groups: int = 0, who: str = "hint_lensgen_run"):
     """one hint_lensgen_run on checked arguments: the outputs named in `want` as a dict (`out`: the tests' guarded buffers)"""
-    lib = _lib.load()
-    with torch.cuda.device(dev):
-        desc = _lib.LensGenDesc()
-        desc.n_rows, desc.seed, desc.offset, desc.max_groups = n, seed, offset, max_groups
-        desc.draws = draws.data_ptr() if draws is not None else None
-        res = _outputs(desc, _LENS_TABLE(n), want, out, dev)
-        nbytes = lib.hint_lensgen_workspace_bytes(n)
-        if nbytes == 0:
-            _lib.check(1, "hint_lensgen_workspace_bytes")
-        ws = out["workspace"] if out is not None and "workspace" in out else torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        desc.workspace, desc.workspace_bytes = ws.data_ptr(), nbytes
-        st = lib.hint_lensgen_run(desc, torch.cuda.current_stream(dev).cuda_stream)
-    _lib.check(st, "hint_lensgen_run")
+    desc = _lib.LensGenDesc()
+    desc.n_rows, desc.seed, desc.offset, desc.max_groups = n, seed, offset, max_groups
+    desc.draws = draws.data_ptr() if draws is not None else None
+    res = _outputs(desc, _LENS_TABLE(n), want, out, dev)
+    ws = _run_desc("hint_lensgen_run", desc, dev, (n,), out)
     if draws is not None:
-        _rejected(ws[:nbytes], "u_r or u_t outside [0, 1], or a draw that is not finite", who)
+        _rejected(ws[:desc.workspace_bytes], "u_r or u_t outside [0, 1], or a draw that is not finite", who)
     res["workspace"] = ws
     return res
 
@@ -121,7 +56,7 @@ def sample_lens_prior(n: int, seed: int, *, offset: int = 0, device=None, draws:
     draws [n, 4] = (u_r, u_t, n_x, n_y) replaces the Philox stream (seed and offset then go unused; the rows are checked, which
     reads one number back).  return_ring: (x, ring [n, 32, 2], counts [n]) - the closed, centred, zero-padded ring x is made of"""
     who = "sample_lens_prior"
-    n, seed, offset, dev, draws = _sample_args(n, seed, offset, device, draws, who)
+    n, seed, offset, dev, draws = _sample_args(n, seed, offset, device, draws, who, _DRAWS)
     res = _lens_run(n, seed, offset, dev, draws, ["x", "ring", "counts"] if return_ring else ["x"], who=who)
     return (res["x"], res["ring"], res["counts"]) if return_ring else res["x"]
 
@@ -132,7 +67,7 @@ def sample_lens_joint(n: int, seed: int, noise: float = 0.05, *, offset: int = 0
     the stream-1 draws of (seed, offset + i).  return_eps: (x, y, eps)"""
     who = "sample_lens_joint"
     noise = _check_real(noise, "noise", who, nonneg=False)
-    n, seed, offset, dev, draws = _sample_args(n, seed, offset, device, draws, who)
+    n, seed, offset, dev, draws = _sample_args(n, seed, offset, device, draws, who, _DRAWS)
     res = _lens_run(n, seed, offset, dev, draws, ["x", "eps"], who=who)
     y = lens_forward_process(res["x"], noise, eps=res["eps"])
     return (res["x"], y, res["eps"]) if return_eps else (res["x"], y)
@@ -142,7 +77,7 @@ def lens_rings(draws: torch.Tensor):
     """(ring [n, 32, 2], counts [n] int32) of draws [n, 4]: the closed ring of each lens, centred and noised as generate_lens_shape
     returns it, zero-padded behind its 31 or 32 points; fourier_coeffs(ring, 5, counts) is sample_lens_prior's x up to rounding"""
     who = "lens_rings"
-    draws = _check_draws(draws, None, who)
+    draws = _check_draws(draws, None, who, _DRAWS)
     res = _lens_run(draws.shape[0], 0, 0, draws.device, draws, ["x", "ring", "counts"], who=who)
     return res["ring"], res["counts"]
 
@@ -150,29 +85,21 @@ def lens_rings(draws: torch.Tensor):
 def lens_draws(n: int, seed: int, *, offset: int = 0, device=None) -> torch.Tensor:
     """the draws sample_lens_prior(n, seed, offset=offset) uses, [n, 4] = (u_r, u_t, n_x, n_y)"""
     who = "lens_draws"
-    n, seed, offset, dev, _ = _sample_args(n, seed, offset, device, None, who)
+    n, seed, offset, dev, _ = _sample_args(n, seed, offset, device, None, who, _DRAWS)
     return _lens_run(n, seed, offset, dev, None, ["x", "draws_out"], who=who)["draws_out"]
 
 
 def _fcoef_run(points: torch.Tensor, n_coeffs: int, counts: Optional[torch.Tensor], out=None, max_groups: int = 0,
                who: str = "hint_fcoef_run"):
-    lib = _lib.load()
     n, p = points.shape[0], points.shape[1]
     dev = points.device
-    with torch.cuda.device(dev):
-        desc = _lib.FcoefDesc()
-        desc.points, desc.counts = points.data_ptr(), (counts.data_ptr() if counts is not None else None)
-        desc.n_rows, desc.p_max, desc.n_coeffs, desc.max_groups = n, p, n_coeffs, max_groups
-        res = _outputs(desc, dict(x=((n, 4 * n_coeffs), _F32)), ["x"], out, dev)
-        nbytes = lib.hint_fcoef_workspace_bytes(n, p, n_coeffs)
-        if nbytes == 0:
-            _lib.check(1, "hint_fcoef_workspace_bytes")
-        ws = out["workspace"] if out is not None and "workspace" in out else torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        desc.workspace, desc.workspace_bytes = ws.data_ptr(), nbytes
-        st = lib.hint_fcoef_run(desc, torch.cuda.current_stream(dev).cuda_stream)
-    _lib.check(st, "hint_fcoef_run")
+    desc = _lib.FcoefDesc()
+    desc.points, desc.counts = points.data_ptr(), (counts.data_ptr() if counts is not None else None)
+    desc.n_rows, desc.p_max, desc.n_coeffs, desc.max_groups = n, p, n_coeffs, max_groups
+    res = _outputs(desc, dict(x=((n, 4 * n_coeffs), _F32)), ["x"], out, dev)
+    ws = _run_desc("hint_fcoef_run", desc, dev, (n, p, n_coeffs), out)
     if counts is not None:
-        _rejected(ws[:nbytes], f"every count must be n_coeffs..{p}", who)
+        _rejected(ws[:desc.workspace_bytes], f"every count must be n_coeffs..{p}", who)
     return res["x"]
 
 

@@ -76,6 +76,6 @@ ROUTES = {
     "wrappers_shapes": (T + "test_wrappers", None),
     "wrappers_shapes_checked_rows": (
         T + "test_wrappers",
-        "hint_amd/shapes.py:91: rows taken from the caller (draws, counts) are checked, which reads the count of refused rows back"),
+        "hint_amd/_ops.py:132: rows taken from the caller (draws, counts) are checked, which reads the count of refused rows back"),
 }
 MAX_EXEMPT_SHARE = 0.25

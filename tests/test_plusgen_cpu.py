@@ -15,6 +15,7 @@ import torch
 import hint_amd
 from hint_amd import _lib, plusgen
 from hint_amd._lib import HintAmdError
+from fake_device import OnGpu
 import noise_oracle as no
 import plusgen_oracle as po
 from plusgen_cases import (CONDITIONAL, HIGH, N_BIG, SEED, SHARES, TARGETS, corner_case_draws, pattern_draws, sweep_arms)
@@ -179,6 +180,60 @@ def test_python_wrappers_reject_bad_arguments_without_a_gpu():
     g = torch.zeros(5, 9, requires_grad=True)
     with pytest.raises(HintAmdError):
         hint_amd.plus_outlines(g)
+
+
+def test_the_sampler_argument_checks_word_every_refusal_as_recorded():
+    """every branch of the draws / sampling-argument checks the samplers share, through this module's wrappers, the whole text"""
+    who, shape = "sample_plus_prior", "[1..1073741824, 9] = (u_xl, u_yl, u_xw, u_yw, u_xs, u_ys, u_a, n_x, n_y)"
+    ok = torch.zeros(10, 9)
+    fallback = "the sampler is a GPU kernel and there is no CPU fallback"
+    no_grad = "requires grad, and no gradient is implemented; call it under torch.no_grad() or detach the input"
+    bad_calls = [
+        (lambda: hint_amd.sample_plus_prior(0, 1), f"{who}: n must be 1..1073741824 (got 0)"),
+        (lambda: hint_amd.sample_plus_prior((1 << 30) + 1, 1), f"{who}: n must be 1..1073741824 (got 1073741825)"),
+        (lambda: hint_amd.sample_plus_prior(2.0, 1), f"{who}: n must be an int (got float)"),
+        (lambda: hint_amd.sample_plus_prior(True, 1), f"{who}: n must be an int (got bool)"),
+        (lambda: hint_amd.sample_plus_prior(10, -1), f"{who}: seed must be 0..18446744073709551615 (got -1)"),
+        (lambda: hint_amd.sample_plus_prior(10, 2 ** 64), f"{who}: seed must be 0..18446744073709551615 (got 18446744073709551616)"),
+        (lambda: hint_amd.sample_plus_prior(10, "1"), f"{who}: seed must be an int (got str)"),
+        (lambda: hint_amd.sample_plus_prior(10, 1, offset=2 ** 64 - 5),
+         f"{who}: offset must be 0..18446744073709551605 (got 18446744073709551611)"),
+        (lambda: hint_amd.sample_plus_prior(10, 1, offset=-1), f"{who}: offset must be 0..18446744073709551605 (got -1)"),
+        (lambda: hint_amd.sample_plus_prior(10, 1, device="cpu"), f"{who}: device is cpu; {fallback}"),
+        (lambda: hint_amd.sample_plus_prior(10, 1, device=3.5), f"{who}: device must name a device (got 3.5)"),
+        (lambda: hint_amd.sample_plus_prior(10, 1, draws=[[0.5] * 9] * 10), f"{who}: draws must be a tensor (got list)"),
+        (lambda: hint_amd.sample_plus_prior(10, 1, draws=torch.zeros(10, 4)), f"{who}: draws must be {shape} (got shape (10, 4))"),
+        (lambda: hint_amd.sample_plus_prior(10, 1, draws=torch.zeros(10)), f"{who}: draws must be {shape} (got shape (10,))"),
+        (lambda: hint_amd.sample_plus_prior(10, 1, draws=torch.zeros(0, 9)), f"{who}: draws must be {shape} (got shape (0, 9))"),
+        (lambda: hint_amd.sample_plus_prior(9, 1, draws=ok), f"{who}: draws holds 10 rows and n is 9"),
+        (lambda: hint_amd.sample_plus_prior(10, 1, draws=ok), f"{who}: draws is on cpu; {fallback}"),
+        (lambda: hint_amd.sample_plus_prior(10, 1, draws=OnGpu(ok.to(torch.int32))),
+         f"{who}: draws is torch.int32; expected a floating-point tensor"),
+        (lambda: hint_amd.sample_plus_prior(10, 1, draws=OnGpu(ok.clone().requires_grad_(True))), f"{who}: draws {no_grad}"),
+        (lambda: hint_amd.sample_plus_prior(10, 1, draws=OnGpu(ok), device="cuda:0"), f"{who}: draws is on cuda:1 and device is cuda:0"),
+        (lambda: hint_amd.sample_plus_prior(10, 1, draws=OnGpu(ok), device="cpu"), f"{who}: device is cpu; {fallback}"),
+        (lambda: hint_amd.sample_plus_joint(0, 1), "sample_plus_joint: n must be 1..1073741824 (got 0)"),
+        (lambda: hint_amd.sample_plus_joint(10, 1, draws=torch.zeros(10, 4)), f"sample_plus_joint: draws must be {shape} (got shape (10, 4))"),
+        (lambda: hint_amd.plus_draws(10, 1, offset=2 ** 64 - 5),
+         "plus_draws: offset must be 0..18446744073709551605 (got 18446744073709551611)"),
+        (lambda: hint_amd.plus_outlines(0.5), "plus_outlines: draws must be a tensor (got float)"),
+        (lambda: hint_amd.plus_outlines(torch.zeros(3, 4)), f"plus_outlines: draws must be {shape} (got shape (3, 4))"),
+        (lambda: hint_amd.plus_outlines(torch.zeros(3, 9)), f"plus_outlines: draws is on cpu; {fallback}"),
+        (lambda: hint_amd.plus_outlines(OnGpu(torch.zeros(3, 9, dtype=torch.int64))),
+         "plus_outlines: draws is torch.int64; expected a floating-point tensor"),
+        (lambda: hint_amd.plus_outlines(OnGpu(torch.zeros(3, 9, requires_grad=True))), f"plus_outlines: draws {no_grad}"),
+        (lambda: hint_amd.sample_plus_targeted(10, 1, (0.0, 0.0, 0.3, 1.5), draws=torch.zeros(10, 4)),
+         f"sample_plus_targeted: draws must be {shape} (got shape (10, 4))"),
+        (lambda: hint_amd.sample_plus_targeted(9, 1, (0.0, 0.0, 0.3, 1.5), draws=ok), "sample_plus_targeted: draws holds 10 rows and n is 9"),
+    ]
+    for call, text in bad_calls:
+        with pytest.raises(HintAmdError) as e:
+            call()
+        assert str(e.value) == text, (text, str(e.value))
+    with torch.no_grad():                                   # (no gradient is asked for: the check after it refuses the call)
+        with pytest.raises(HintAmdError) as e:
+            hint_amd.sample_plus_prior(10, 1, draws=OnGpu(ok.clone().requires_grad_(True)), device="cuda:0")
+    assert str(e.value) == f"{who}: draws is on cuda:1 and device is cuda:0"
 
 
 def test_draws_are_noise_oracles_philox_chunked_gathered_and_across_the_carry():

@@ -26,5 +26,6 @@ from .curves import (lens_iou_dice, lens_shape_scores, plus_iou_dice, plus_shape
 from .shapes import fourier_coeffs, lens_draws, lens_rings, sample_lens_joint, sample_lens_prior  # noqa: F401,E402
 from .plusgen import (plus_draws, plus_outlines, sample_plus_conditional, sample_plus_joint,  # noqa: F401,E402
                       sample_plus_prior, sample_plus_targeted)
+from .data import DeviceDataset, epoch_indices, reference_lr  # noqa: F401,E402
 
 __version__ = "0.1.0"

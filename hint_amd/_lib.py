@@ -132,6 +132,19 @@ class HouseholderDesc(C.Structure):
 
 HOUSEHOLDER_BUILD, HOUSEHOLDER_APPLY, HOUSEHOLDER_GRAD = 0, 1, 2
 
+
+class EpochDesc(C.Structure):
+    """mirror of `hint_epoch_desc` (include/hint_amd.h); the stream is a field, not a parameter of the run"""
+    _fields_ = [("op", C.c_int32), ("shuffle", C.c_int32), ("d", C.c_int32), ("dy", C.c_int32), ("epoch", C.c_uint32),
+                ("max_groups", C.c_int32), ("n_rows", C.c_int64), ("seed", C.c_uint64), ("first", C.c_int64), ("count", C.c_int64),
+                ("block", C.c_int64), ("block_stride", C.c_int64), ("x", C.c_void_p), ("x_stride", C.c_int64), ("y", C.c_void_p),
+                ("y_stride", C.c_int64), ("cursor", C.c_void_p), ("out_x", C.c_void_p), ("out_stride", C.c_int64),
+                ("out_y", C.c_void_p), ("indices_out", C.c_void_p), ("mean", C.c_void_p), ("std", C.c_void_p),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("stream", C.c_void_p)]
+
+
+EPOCH_GATHER, EPOCH_MOMENTS, EPOCH_STANDARDIZE = 0, 1, 2
+
 _lib = None
 
 _PROTOS = {
@@ -243,6 +256,9 @@ _PROTOS = {
     "hint_householder_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "hint_householder_run": (C.c_int, [C.POINTER(HouseholderDesc)]),
     "hint_householder_geometry": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
+    "hint_epoch_index": (C.c_int64, [C.c_int64, C.c_uint64, C.c_uint32, C.c_int32, C.c_int64]),
+    "hint_epoch_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int64, C.c_int64, C.c_int32]),
+    "hint_epoch_run": (C.c_int, [C.POINTER(EpochDesc)]),
 }
 
 

@@ -757,3 +757,32 @@ class ConditionalFlowTrainer(TrainerCore):
         self.last = (zy, zx, Jx, Jy)
         self._last_B = B
         return _LossPair(self)
+
+    def fit_epoch(self, dataset, epoch: int, batch_size: int, max_batches: int = 0, first_batch: int = 0, chunk: int = 16):
+        """one training epoch on a hint_amd.DeviceDataset holding x and y (FlowTrainer.fit_epoch's contract): batches first_batch
+        .. of epoch `epoch` in the data set's keyed order, the tail dropped, up to batch max_batches (0: all); one gather per
+        `chunk` batches, one step(x, y) per batch.  -> [n, 2] device tensor of the batches' loss pairs; nothing synchronises the
+        host beyond what step() does"""
+        from .data import DeviceDataset
+        who = "ConditionalFlowTrainer.fit_epoch"
+        if not isinstance(dataset, DeviceDataset):
+            raise HintAmdError(f"{who}: dataset must be a hint_amd.DeviceDataset (got {type(dataset).__name__})")
+        if dataset.device != self.device:
+            raise HintAmdError(f"{who}: the data set is on {dataset.device}, the model on {self.device}")
+        if dataset.d != self.flow.ndim_x or dataset.dy != self.flow.ndim_y:
+            raise HintAmdError(f"{who}: the data set has d = {dataset.d}, dy = {dataset.dy}; the model ndim_x = {self.flow.ndim_x}, "
+                               f"ndim_y = {self.flow.ndim_y}")
+        for name, v, lo in (("max_batches", max_batches, 0), ("first_batch", first_batch, 0), ("chunk", chunk, 1)):
+            if isinstance(v, bool) or not isinstance(v, int) or v < lo:
+                raise HintAmdError(f"{who}: {name} must be an int >= {lo} (got {v!r})")
+        rank, world = dp.world_info(self.group)
+        total = dataset.n_batches(batch_size, world)
+        n = max((min(total, max_batches) if max_batches > 0 else total) - first_batch, 0)
+        losses = torch.empty(n, 2, dtype=torch.float32, device=self.device)
+        for k in range(0, n, chunk):
+            K = min(chunk, n - k)
+            xs, ys = dataset.gather(epoch, first_batch + k, K, batch_size, rank, world)
+            for j in range(K):
+                l0, l1 = self.step(xs[j], ys[j])
+                losses[k + j] = torch.stack((l0, l1))
+        return losses

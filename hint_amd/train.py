@@ -399,6 +399,119 @@ class FlowTrainer(TrainerCore):
         st = self._static_for(x, c)
         return st["x"], st["c"]
 
+    # ---- device-resident epochs (hint_amd/data.py) ----------------------------------------------------
+    def _check_dataset(self, dataset, who: str, **counts):
+        """a DeviceDataset on the trainer's device with the flow's widths; counts: arguments that are ints >= 0"""
+        from .data import DeviceDataset
+        if not isinstance(dataset, DeviceDataset):
+            raise HintAmdError(f"{who}: dataset must be a hint_amd.DeviceDataset (got {type(dataset).__name__})")
+        if dataset.device != self.device:
+            raise HintAmdError(f"{who}: the data set is on {dataset.device}, the model on {self.device}")
+        if dataset.d != self.flow.ndim_x or dataset.dy != self.flow.ndim_c:
+            raise HintAmdError(f"{who}: the data set has d = {dataset.d}, dy = {dataset.dy}; the flow ndim_x = {self.flow.ndim_x}, "
+                               f"ndim_c = {self.flow.ndim_c}")
+        for name, v in counts.items():
+            if isinstance(v, bool) or not isinstance(v, int) or v < 0:
+                raise HintAmdError(f"{who}: {name} must be an int >= 0 (got {v!r})")
+
+    def fit_epoch(self, dataset, epoch: int, batch_size: int, max_batches: int = 0, first_batch: int = 0, chunk: int = 16):
+        """train_epoch(test=False) (train_unconditional.py:98-158) on a DeviceDataset: batches first_batch .. of epoch `epoch` in
+        the data set's keyed order, the tail dropped, at most up to batch max_batches (0: all).  Per `chunk` batches ONE gather
+        straight into step_many's input buffers and ONE step_many; the last, shorter chunk runs through step() (no second
+        multi-step graph).  A data-parallel job takes this rank's share of every global batch.  A conditional flow takes
+        dataset.y as c.  -> [n, 2] device tensor of the batches' (-log p(z), -log|det J|), its mean over the batches the
+        reference's return value; nothing synchronises the host.  (seed, epoch, first_batch) resume an epoch mid-way."""
+        who = "FlowTrainer.fit_epoch"
+        self._check_dataset(dataset, who, max_batches=max_batches, first_batch=first_batch, chunk=chunk)
+        if chunk < 1:
+            raise HintAmdError(f"{who}: chunk must be an int >= 1 (got {chunk!r})")
+        rank, world = dp.world_info(self.group)
+        total = dataset.n_batches(batch_size, world)
+        # (max_batches > 0 ends the epoch at that batch, as c.max_batches_per_epoch does: train_unconditional.py:118)
+        n = max((min(total, max_batches) if max_batches > 0 else total) - first_batch, 0)
+        losses = torch.empty(n, 2, dtype=torch.float32, device=self.device)
+        pair = lambda r: r if isinstance(r, tuple) else (r, None)        # noqa: E731
+        k = 0
+        while k < n:
+            K = min(chunk, n - k)
+            g = first_batch + k
+            if K == chunk and K > 1:
+                st = self._static_many if self._many_ok() and self._graph_many is not None else None
+                if st is not None and tuple(st["x"].shape) == (K, batch_size, dataset.d):
+                    xs, cs = pair(dataset.gather(epoch, g, K, batch_size, rank, world,
+                                                 out=st["x"] if st["c"] is None else (st["x"], st["c"])))
+                else:       # (the first chunk of this shape: step_many captures on it and keeps the copy)
+                    xs, cs = pair(dataset.gather(epoch, g, K, batch_size, rank, world))
+                    xs, cs = self.input_buffers_many(xs, cs)
+                self.step_many(xs, cs)
+                losses[k:k + K] = self.step_losses()
+            else:
+                xs, cs = pair(dataset.gather(epoch, g, K, batch_size, rank, world))
+                for j in range(K):
+                    self.step(xs[j], cs[j] if cs is not None else None)
+                    losses[k + j] = torch.stack(self.last_losses())
+            k += K
+        return losses
+
+    @torch.no_grad()
+    def evaluate(self, dataset, batch_size: Optional[int] = None, noise: Optional[float] = None, max_batches: int = 0,
+                 epoch: int = 0):
+        """evaluate(c) / train_epoch(test=True) (train_unconditional.py:66-95) on a DeviceDataset: its rows in sequential order
+        in batches of batch_size (None: all rows in one batch, data.py:505-506), the tail dropped, at most max_batches (0: all);
+        x + noise * N(0, 1) (default: the trainer's noise) through the flow, one forward launch and one slot of loss sums per
+        batch.  -> [2] device tensor, np.mean(loss_history, axis=0) = the batches' mean (-log p(z), -log|det J|); their sum is the
+        reference's return value.  The draws come from an evaluation stream of the trainer's own - the rank's seed under a tag of
+        its own, a counter that every evaluated batch advances, `epoch` in the counter's high word - so an evaluation between
+        two training steps changes no bit of training.  Nothing synchronises the host."""
+        who = "FlowTrainer.evaluate"
+        self._check_dataset(dataset, who, max_batches=max_batches, epoch=epoch)
+        if epoch >= 2 ** 31:
+            raise HintAmdError(f"{who}: epoch must be 0..2^31 - 1 (got {epoch!r})")
+        B = dataset.n_rows if batch_size is None else batch_size
+        n = dataset.n_batches(B)                                  # (every rank evaluates every row)
+        if max_batches > 0:
+            n = min(n, max_batches)
+        noise = self.noise if noise is None else float(noise)
+        if n < 1:
+            raise HintAmdError(f"{who}: {dataset.n_rows} rows hold no batch of {B}")
+        if getattr(self, "_eval_rng", None) is None:
+            self._eval_rng = self.rng_state.clone()               # {the rank's seed ^ "EVAL", counter}: device ops, no host read
+            self._eval_rng[0:1].bitwise_xor_(0x4556414C)
+            self._eval_count = 0
+        acc = torch.zeros(n, 64, 2, dtype=torch.float32, device=self.device)
+        out = torch.empty(n, 2, dtype=torch.float32, device=self.device)
+        chained = self._chainable
+        if chained:
+            self._check_arenas()
+            self._pack_all()
+            chain = self._chain_infer(B)
+            z = torch.empty(B, dataset.d, dtype=torch.float32, device=self.device)
+            J = torch.empty(B, dtype=torch.float32, device=self.device)
+        for k in range(n):
+            x, c = self._inputs(dataset.x[k * B:(k + 1) * B], dataset.y[k * B:(k + 1) * B] if dataset.y is not None else None)
+            self._eval_count += 1
+            step = (epoch << 32) | (self._eval_count & 0xFFFFFFFF)
+            if chained:
+                self._eval_rng[1:2].fill_(step)
+                with torch.cuda.device(self.device):
+                    _lib.check(self.lib.hint_chain_forward_noisy(
+                        chain, x.data_ptr(), c.data_ptr() if c is not None else None, z.data_ptr(), J.data_ptr(), None,
+                        acc[k].data_ptr(), float(noise), self._eval_rng.data_ptr() if noise > 0 else None, None, self._stream()),
+                        "hint_chain_forward_noisy")
+            else:           # walk the modules, as nll does; the draws from a generator of the evaluation's own
+                if noise > 0:
+                    gen = torch.Generator(device=self.device)
+                    gen.manual_seed(step ^ 0x4556414C)
+                    x = x.add(torch.randn(x.shape, dtype=x.dtype, device=x.device, generator=gen), alpha=noise)
+                zz = self.flow(x, c=c)
+                JJ = self.flow.log_jacobian(run_forward=False)
+                out[k, 0] = 0.5 * torch.sum(zz * zz, dim=1).mean()
+                out[k, 1] = -JJ.mean()
+        if chained:
+            s = acc.sum(dim=1)
+            out = torch.stack([s[:, 0] / B, -s[:, 1] / B], dim=1)
+        return out.mean(dim=0)
+
     def timed_step(self, x: torch.Tensor, c: Optional[torch.Tensor] = None):
         """one un-captured training step with HIP events between the launches (on the stream they
         are issued to); returns {launch: microseconds}.  For bench.py's roofline: the durations are

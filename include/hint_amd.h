@@ -1177,6 +1177,85 @@ size_t hint_householder_workspace_bytes(int32_t op, int32_t B, int32_t d, int32_
 int hint_householder_run(const hint_householder_desc* desc);
 int64_t hint_householder_geometry(int32_t B, int32_t d, int32_t field);
 
+/* Device-resident epochs: what stands between a resident table x [n_rows, d] (y [n_rows, dy]) and the training step - the
+ * reference's DataLoader(TensorDataset(...), shuffle=True, drop_last=True) (data.py:484-487, :503-506: one __getitem__ per row and a
+ * collate on the host) and the statistics of load_data_normalised (data.py:337-339).
+ * THE ORDER OF AN EPOCH IS THIS LIBRARY'S DEFINITION: the reference's is torch's host generator and cannot be pinned.  It is a function
+ * of (n_rows, seed, epoch, position) alone - no n_rows-sized randperm, no sort, no state:
+ *   N = rows, 1 <= N <= 2^40.  epoch is a uint32.  seed is a uint64.
+ *   h = max(1, ceil(bitlength(N-1) / 2)).  The domain is M = 4^h, so N <= M < 4N for N >= 2.  A value is split as v = L << h | R.
+ *   The permutation is a balanced Feistel network of 4 rounds: (L, R) -> (R, L ^ F_r(R)).
+ *   F_r(R) is the low h bits of word 0 of Philox4x32-10 with counter {R, r, epoch, 0x45504F43} and key {seed lo, seed hi}.
+ *   Cycle walking: v = p; do v = feistel(v); while (v >= N).  source_row(p) = v.
+ *   The walk is capped at 256 applications.  Every step succeeds with probability of at least 1/4, so a correct network exceeds
+ *   the cap with probability below 1e-31.  A row that reaches the cap is flagged; the loop never runs on.
+ *   shuffle = 0 is the identity.
+ * Chunks of an epoch at any boundaries give the bits of one call; a data-parallel rank computes its own shard with no communication;
+ * a run resumes mid-epoch from (seed, epoch, position).  hint_epoch_index is the host's twin, compiled from the same text
+ * (hint_amd/csrc/hint_epochperm.hpp): the source row of position pos, or -1 and an error message for n_rows outside 1..2^40, pos
+ * outside 0..n_rows-1 or a walk that reached the cap.
+ *   op gather       out_x[i, :] = x[source_row(p_i), :] for i < count, and, with y, out_y[i, :] = y[source_row(p_i), :].  Position
+ *                   p_i = first + i, or with block > 0 (a rank's share of every global batch) first + (i / block) * block_stride +
+ *                   i % block.  x, y fp32 with row strides x_stride, y_stride (floats, 0..2^22; rows need no alignment beyond 4
+ *                   bytes: no load is wider than a dword), 1 <= d <= 128, 0 <= dy <= 128 (dy > 0 exactly when y is given).  The
+ *                   outputs are contiguous [count, d] and [count, dy].  Index arithmetic is 64-bit throughout.  indices_out
+ *                   (may be NULL) receives the source rows; with it, x may be NULL (and y): the indices alone.  cursor (may be
+ *                   NULL): device int64[2] = {epoch, first}, read only,
+ *                   replacing the descriptor's epoch and first - a captured launch replays at a new position after a fill of the
+ *                   cursor.  Every position must be < n_rows; with a cursor the host cannot check this, and a position >= n_rows
+ *                   (or a cursor epoch outside 0..2^32-1, or first outside 0..n_rows-1) marks its row REJECTED, as a walk at its
+ *                   cap does: the output row is NaN, indices_out -1, no other row is disturbed.  The workspace is
+ *                   int32[workspace_bytes / 4]: every word is written by a run and their sum is the number of rejected rows, as
+ *                   for hint_plusgen_run.  One launch.
+ *   op moments      mean[j], std[j] (double[d] each) of column j over rows [first, first + count), in double: two passes over fixed
+ *                   slabs of rows (at most 1024 slabs of at least 256 rows), a slab's column sum the sum of its threads' partial
+ *                   sums (each over its rows ascending) in ascending order, the slabs added in ascending order; std =
+ *                   sqrt(sum (x - mean)^2 / count), np.std with ddof 0.  Four launches.
+ *   op standardize  out_x[i, j] = (float)(((double)x[i, j] - mean[j]) / std[j]) for rows [first, first + count) of the tables x
+ *                   (x_stride) and out_x (out_stride >= d): IEEE double subtract and divide, rounded once.  out_x may be x.  A zero
+ *                   std gives what numpy gives, NaN or +-inf; it is not guarded.  One launch.
+ *   run              stream-ordered on the current device, no host synchronisation, no allocation (capturable), no atomics: two
+ *                    runs give equal bits.  THE STREAM IS A FIELD OF THE DESCRIPTOR, as in hint_plusgen_desc and for the same reason.
+ *                    max_groups: 0 = the default grid, otherwise the workgroups at most (gather, standardize).  Rejects, before
+ *                    any device call and naming the field: a null desc or workspace; an unknown op; n_rows outside 1..2^40, count
+ *                    outside 1..n_rows, d outside 1..128; max_groups < 0; x NULL (but for a gather of indices_out alone);
+ *                    x_stride outside 0..2^22; first < 0; gather: dy
+ *                    outside 0..128, out_x NULL, y without dy or dy without y, out_y NULL with y, y_stride outside its range,
+ *                    block < 0 or 0 < block_stride < block; moments, standardize: mean or std NULL; standardize: out_x NULL,
+ *                    out_stride outside d..2^22; first + count > n_rows (gather: the last position; with a cursor, its offset
+ *                    from first); x, y, out_x or out_y not 4-byte, cursor, indices_out, mean or std not 8-byte, the workspace not
+ *                    16-byte aligned; a workspace smaller than workspace_bytes says.
+ *   workspace_bytes  bytes a run of `op` over `count` positions / rows needs (never 0 for sizes a run accepts: standardize uses
+ *                    none and is given 16).  For sizes run would reject: 0 and an error message.  Never decreases with count; at
+ *                    most 1 MiB (moments, d = 128), 32 KiB for gather. */
+#define HINT_EPOCH_GATHER 0
+#define HINT_EPOCH_MOMENTS 1
+#define HINT_EPOCH_STANDARDIZE 2
+typedef struct hint_epoch_desc {
+    int32_t op;                            /* HINT_EPOCH_GATHER / _MOMENTS / _STANDARDIZE */
+    int32_t shuffle;                       /* 0: source_row(p) = p */
+    int32_t d, dy;
+    uint32_t epoch;
+    int32_t max_groups;
+    int64_t n_rows;                        /* N: rows of the tables x and y */
+    uint64_t seed;
+    int64_t first, count;                  /* gather: the first position and the number of positions; otherwise the row range */
+    int64_t block, block_stride;           /* gather: 0, 0 (contiguous positions), or 1 <= block <= block_stride */
+    const float* x; int64_t x_stride;      /* device float table, row i at x + i * x_stride */
+    const float* y; int64_t y_stride;      /* NULL (dy = 0), or the same for y */
+    const int64_t* cursor;                 /* NULL, or device int64[2] = {epoch, first} */
+    float* out_x; int64_t out_stride;      /* gather: device float[count, d] (out_stride unused); standardize: a table as x */
+    float* out_y;                          /* gather with y: device float[count, dy] */
+    int64_t* indices_out;                  /* NULL, or device int64[count] */
+    double* mean;                          /* device double[d]: written by moments, read by standardize */
+    double* std;                           /* likewise */
+    void* workspace; size_t workspace_bytes;      /* 16-byte aligned */
+    void* stream;                          /* the hipStream_t the launches go to (NULL: the null stream) */
+} hint_epoch_desc;
+int64_t hint_epoch_index(int64_t n_rows, uint64_t seed, uint32_t epoch, int32_t shuffle, int64_t pos);
+size_t hint_epoch_workspace_bytes(int32_t op, int64_t n_rows, int64_t count, int32_t d);
+int hint_epoch_run(const hint_epoch_desc* desc);
+
 int hint_abi_version(void);
 const char* hint_last_error(void);
 /* what the library binary was built with and runs with: "libhint_amd abi N, gfx950, HIP x.y.z, clang ..., src <12 hex digits: hash

@@ -3,6 +3,10 @@ checked without a GPU by tests/test_large_cases_cpu.py): every descriptor kernel
 per-row array holds more than 2^31 elements - so that element indices pass 2^31 and byte offsets pass 2^31 and 2^32 inside one
 call - and the rows such a run is probed at.
 
+Three ledgers, and every entry point that takes a descriptor is in exactly one (tests/test_large_cases_cpu.py holds them against
+include/hint_amd.h): ROW_CASES, the cases; LIMITED, entry points whose documented limits keep every offset below 2^31, each with
+the test that runs it AT that limit; NOT_COVERED, the two left out, with the reason.
+
 A case's N is computed here from the width of the named array (rows_past, then ragged_up): never typed by hand.  `arrays` lists
 every device array of the case as (name, elements, bytes per element); `peak` is what the test asks torch.cuda.mem_get_info for
 before it allocates anything: the arrays plus 2 GiB for chunked temporaries (no temporary, and no float64 copy, is larger).
@@ -79,10 +83,12 @@ def runs_of(rows):
     return [tuple(v) for v in out]
 
 
-def _case(name, entry, named, width, N, arrays, limit, geometry=None, fixed_n=False, crossings=None, **params):
+def _case(name, entry, named, width, N, arrays, limit, geometry=None, fixed_n=False, crossings=None, grid=None, **params):
+    """grid: (rows a workgroup has in flight, workgroups at most) of an entry point that has no geometry query, from its kernel's
+    constants"""
     total = sum(n * b for _, n, b in arrays)
     return dict(name=name, entry=entry, named=named, width=width, N=N, arrays=arrays, bytes=total, peak=total + SLACK,
-                limit=limit, geometry=geometry, fixed_n=fixed_n, params=params,
+                limit=limit, geometry=geometry, fixed_n=fixed_n, params=params, grid=grid,
                 crossings=crossing_rows(width) if crossings is None else crossings)
 
 
@@ -177,6 +183,40 @@ def _lensgen():
                  seed=0x5EED0123456789AB, offset=(1 << 32) - N // 2)
 
 
+# hint_plusgen.hip: 16 lanes a row, so PG_WAVE_ROWS rows a wavefront, PG_WAVES wavefronts a workgroup, PG_MAX_WG workgroups at
+# most (tests/test_large_cases_cpu.py reads the three from the kernel's text)
+PG_WAVE_ROWS, PG_WAVES, PG_MAX_WG = 4, 4, 2048
+PG_MODULI = (64, PG_WAVE_ROWS, PG_WAVE_ROWS * PG_WAVES, PG_MAX_WG)
+
+
+def _plusgen(named):
+    """the plus-shape sampler's two wide arrays leave by different code - outline [N, 128, 2] per lane at row * PG_PTS, x [N, 100]
+    through LDS as 16-byte pieces at tile * (PG_WAVE_ROWS * PG_ROW / 4) - and each passes 2^31 elements at its own N: a case
+    each at the smallest such N, the other array NULL"""
+    w = dict(outline=256, x=100)[named]
+    N = ragged_up(rows_past(w), PG_MODULI)
+    arrays = [(named, N * w, 4), ("y", N * 4, 4)]
+    if named == "outline":
+        arrays += [("counts", N, 4), ("corners", N, 4)]
+    arrays.append(("draws_out", N * 9, 4))
+    return _case("plusgen_" + named, "hint_plusgen_run", named, w, N, arrays, 1 << 30, grid=(PG_WAVE_ROWS * PG_WAVES, PG_MAX_WG),
+                 seed=0x5EED0123456789AB, offset=(1 << 32) - N // 2)
+
+
+# hint_epoch.hip: EP_TILE rows a workgroup (gather, standardize), EP_MAX_WG workgroups at most, EP_MAX_SLABS slabs of the moments
+EP_TILE, EP_MAX_WG, EP_MAX_SLABS = 256, 2048, 1024
+
+
+def _epoch():
+    """one table x [N, 100] past 2^31 elements and one output of its shape: a whole shuffled epoch gathered (count = N: the
+    output's element offsets pass 2^31 as the source's do), the moments over all rows (the slab cap: slab_rows far above 256),
+    the standardisation out of place (the tile loop's later trips)"""
+    d = 100
+    N = ragged_up(rows_past(d), (64, EP_TILE, EP_MAX_WG, EP_MAX_SLABS))
+    return _case("epoch", "hint_epoch_run", "out_x", d, N, [("x", N * d, 4), ("out_x", N * d, 4), ("indices_out", N, 8)], 1 << 40,
+                 grid=(EP_TILE, EP_MAX_WG), d=d, seed=0xC0FFEE1234567, epoch=3)
+
+
 def _fcoef():
     p_max, K = 1024, 5
     w = 2 * p_max
@@ -201,12 +241,30 @@ def _corr():
 ROW_CASES = {c["name"]: c for c in (_curve(), _hausdorff_points(), _hausdorff_ragged(), _plus(), _overlap(),
                                        _fit("lensfit", "hint_lensfit_run", 4, 128, "hint_lensfit_geometry"),
                                        _fit("plusfit", "hint_plusfit_run", 9, 64, "hint_plusfit_geometry"), _lensgen(), _fcoef(),
-                                       _abc(), _corr())}
+                                       _abc(), _corr(), _plusgen("outline"), _plusgen("x"), _epoch())}
 
 # entry points the large-index tests do not reach, each with the reason (DESIGN.md says the same)
 NOT_COVERED = {
     "hint_mmd_run": "its smallest case past 2^31 elements is n ~ 2^19 at d = 4096: about 1e15 MFMA flops for the xx triangle alone",
     "hint_adam_*": "no model of this family comes within two orders of magnitude of 2^31 parameters; the case needs 34 GB",
+}
+
+# hint_householder.hip: the limits, and the apply grid - tiles of HH_T rows, HH_APPLY_WAVES wavefronts (a tile each) a workgroup,
+# HH_MAX_GRID workgroups at most: a workgroup's tile loop makes a second trip past HH_TRIP rows
+HH_GRAD, HH_MAX_B, HH_MAX_D, HH_MAX_N = 2, 1 << 22, 128, 256
+HH_T, HH_APPLY_WAVES, HH_MAX_GRID = 16, 4, 1024
+HH_TRIP = HH_T * HH_APPLY_WAVES * HH_MAX_GRID
+
+# entry points whose documented limits keep every element offset below 2^31, so that no case past 2^31 elements exists: each with
+# the reason, the size query and its arguments AT the limit (`at`), the arguments one past a limit that the query must refuse
+# (`over`), the elements of the widest array of a run at the limit (`elements`), and the test that runs the entry point there
+LIMITED = {
+    "hint_householder_run": dict(
+        reason="B <= 2^22 rows of d <= 128 floats: the widest array, [B, d], ends at element 2^29",
+        sizer="hint_householder_workspace_bytes", at=(HH_GRAD, HH_MAX_B, HH_MAX_D, HH_MAX_D),
+        over=((HH_GRAD, HH_MAX_B + 1, HH_MAX_D, HH_MAX_D), (HH_GRAD, HH_MAX_B, HH_MAX_D + 1, HH_MAX_D),
+              (HH_GRAD, HH_MAX_B, HH_MAX_D, HH_MAX_N + 1)),
+        elements=HH_MAX_B * HH_MAX_D, test="tests/test_gpu_householder.py::test_the_row_limit"),
 }
 
 

@@ -3,7 +3,9 @@ ConditionalFlowTrainer.fit_epoch): the gather's indices against tests/epoch_orac
 for bit, chunk and rank-shard invariance, guard-banded poisoned buffers, the cursor form captured in a graph and its one rejected
 row, a table past 2^31 elements, the column statistics inside the bounds tests/epoch_oracle.py derives, the standardisation bit for
 bit, an epoch of fit_epoch against step() over the oracle's batches bit for bit, evaluate against the float64 oracle, and every
-route on a gated non-default stream."""
+route on a gated non-default stream.  The regime boundaries of the three kernels run here at the smallest sizes that reach them -
+the moments' slab cap (1024 x 256 rows and one more), a second trip of the standardisation's and the gather's tile loops (2048 x
+256 rows and one more, and max_groups) - and the three ops past 2^31 elements in tests/test_gpu_large_rows.py::test_epoch."""
 import contextlib
 import copy
 import ctypes as C
@@ -17,7 +19,7 @@ from hint_amd import _lib, data
 import epoch_oracle as eo
 import session_script as ss
 import stream_gate
-from guarded import Guarded, bits_equal
+from guarded import NAN_BITS, Guarded, bits_equal
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -217,9 +219,16 @@ def test_a_table_past_2_31_elements():
         torch.cuda.empty_cache()
 
 
+SLAB_EDGE = 1024 * 256              # EP_MAX_SLABS slabs of EP_TILE rows: the most rows at which a slab holds 256 rows
+GRID_EDGE = 2048 * 256              # EP_MAX_WG workgroups of EP_TILE rows: the most rows the tile loops take in one trip
+
+
 @pytest.mark.parametrize("n,d,row0,rows", [(1, 1, 0, 1), (2, 6, 0, 2), (1000, 6, 0, 1000), (70001, 43, 0, 70001), (70001, 43, 1234, 50000),
-                                           (1000, 6, 999, 1)])
+                                           (1000, 6, 999, 1), (SLAB_EDGE, 6, 0, SLAB_EDGE), (SLAB_EDGE + 1, 6, 0, SLAB_EDGE + 1)])
 def test_moments_against_numpy_float64_inside_the_derived_bounds(n, d, row0, rows):
+    """(the last two: the slab cap - 1024 slabs of 256 rows, then 1020 slabs of 257 rows, one of 5 and three empty ones)"""
+    ws = _lib.load().hint_epoch_workspace_bytes(_lib.EPOCH_MOMENTS, n, rows, d)
+    assert ws == -(-8 * d * min(1024, -(-rows // 256)) // 16) * 16                  # one double per slab and column
     x = table(n, d, 11, wide=3) * 3.0 + 1.5
     ds = hint_amd.DeviceDataset(x, seed=1)
     nbytes = _lib.load().hint_epoch_workspace_bytes(_lib.EPOCH_MOMENTS, n, rows, d)
@@ -265,6 +274,50 @@ def test_standardize_is_torchs_double_arithmetic_bit_for_bit():
     ma, sa = a.standardize()
     b.apply_moments(ma, sa)
     assert bits_equal(b.x, ((x0[4000:].double() - ma) / sa).float())
+
+
+def standardize_run(ds, mean, std, out, max_groups=0):
+    """one hint_epoch_run STANDARDIZE of all rows of ds.x into `out`, with the descriptor's max_groups (DeviceDataset passes none)"""
+    desc = ds._stat_desc(_lib.EPOCH_STANDARDIZE, 0, ds.n_rows, mean, std)
+    desc.out_x, desc.out_stride, desc.max_groups = out.data_ptr(), out.stride(0), max_groups
+    data._run_desc("hint_epoch_run", desc, ds.device, (_lib.EPOCH_STANDARDIZE, ds.n_rows, ds.n_rows, ds.d))
+
+
+@pytest.mark.parametrize("n,max_groups", [(GRID_EDGE + 1, 0), (1000, 1)])
+def test_standardize_tile_loop_takes_a_second_trip(n, max_groups):
+    """more tiles than workgroups - one row past the default grid's 2048 tiles, and four tiles on one workgroup: out of place into
+    a poisoned, guard-banded buffer, every element torch's double arithmetic bit for bit, no word left unwritten"""
+    d = 6
+    x = table(n, d, 21) * 2.0 - 0.7
+    ds = hint_amd.DeviceDataset(x, seed=1)
+    mean, std = ds.moments()
+    g = Guarded(n * d, fill="nan")
+    standardize_run(ds, mean, std, g.view(n, d), max_groups)
+    torch.cuda.synchronize()
+    g.check_guards(f"standardize n={n} max_groups={max_groups}")
+    assert int((g.words == NAN_BITS).sum()) == 0
+    assert bits_equal(g.view(n, d), ((x.double() - mean) / std).float())
+    again = torch.empty(n, d, device=DEV)
+    standardize_run(ds, mean, std, again, 3)                            # another grid: the same bits
+    assert bits_equal(again, g.view(n, d))
+
+
+def test_gather_tile_loop_takes_a_second_trip_on_the_default_grid():
+    """count = 2048 x 256 + 1: the default grid's first workgroup takes a second tile, of one row.  The indices are a permutation
+    and the oracle's at the tile edges and a picket; the rows are index_select's bit for bit"""
+    n, d, epoch = GRID_EDGE + 1, 6, 9
+    x = table(n, d, 22)
+    res, guards = guarded_gather(x, None, n, epoch, (0, n, 0, 0), "nan")
+    torch.cuda.synchronize()
+    for name, g in guards:
+        g.check_guards(name)
+        assert int((g.words == NAN_BITS).sum()) == 0, name
+    idx = res["indices_out"]
+    assert torch.equal(idx.sort().values, torch.arange(n, device=DEV)) and int(res["workspace"].sum()) == 0
+    pos = np.unique(np.concatenate([np.arange(0, n, 997), np.arange(300), np.arange(GRID_EDGE - 300, n)])).astype(np.uint64)
+    want = torch.from_numpy(eo.source_rows(n, SEED, epoch, pos)).to(DEV)
+    assert torch.equal(idx[torch.from_numpy(pos.astype(np.int64)).to(DEV)], want)
+    assert bits_equal(res["out_x"], x.index_select(0, idx))
 
 
 # ---- trainers ----

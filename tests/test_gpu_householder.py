@@ -4,8 +4,27 @@ against the float64 statement of tests/householder_oracle.py.  The bounds, u = 2
          evaluations in different orders (about n (2 d + 8) 2^-53 with all norms <= 1)
   APPLY  per entry |y - y64| <= (d + 8) u (|x| |W64|)_ij: gamma of at most d + 3 fp32 multiply-adds in any order, 2 u for W's own
          rounding, slack to d + 8; g_x the same with g_y for x
-  g_W    per entry <= (B + 8) u (|x|^T |g_y|)_ij
-  g_V    rel_err < 1e-4, the project's gradient tolerance (tests/test_gpu_parity.py)
+  g_W    per entry <= (min(B, R / 4) + 8) u (|x|^T |g_y|)_ij, R the slab's rows from hint_householder_geometry.  Derivation, from
+         the kernel's order of operations (include/hint_amd.h): within a slab of R rows each of four wavefronts adds every fourth
+         k-block of 4 rows on the MFMA, so one accumulator is a chain of at most R / 4 fp32 products (and of at most B: products
+         with the exact zeros of rows past B add nothing and round nothing) - at most min(B, R / 4) roundings on partial sums that
+         never exceed the slab's sum of |x| |g_y|; three fp32 additions join the four wavefronts' partial tiles; the slabs of an
+         entry are added in double (2^-53 each: nothing at this scale); the sum is rounded to fp32 once at the store.  To first
+         order that is min(B, R / 4) + 4 roundings, each at most u times the entry's sum of |x| |g_y|; + 8 leaves the rest as
+         slack.  The slab count does not enter: every slab's chain is bounded against its own share of the sum.  It is never
+         looser than (B + 8) u, the bound this file held before, and at B = 2^22 (R = 65536, 64 slabs) it is 1 / 256 of it:
+         9.8e-4 of the entry's magnitude where a slab left out moves an entry of same-signed data by 1 / 64.
+  g_V    rel_err < 1e-4, the project's gradient tolerance (tests/test_gpu_parity.py).  d = 1 is the exception: W = (-1)^n does not
+         depend on Vs, so the gradient is exactly zero and a relative error has no denominator; the closed form's two terms, each
+         4 |G| / |v| in magnitude and the outcome of at most a dozen double operations, cancel: |g_V| <= 64 2^-53 4 |G| / |v|.
+The regimes no small batch reaches run at the smallest B that reaches them, each taken from hint_householder_geometry or from the
+apply grid's rule (tests/large_cases.py HH_TRIP; tests/test_large_cases_cpu.py holds the constants against the kernel's text): the
+last B with R = 256 and the first with R > 256, a second trip of the apply kernel's tile loop, a last trip on which part of the
+workgroups idle, and the documented limit B = 2^22, d = 128 itself (tests/large_cases.py LIMITED names that test).  There the
+references are float64 on the device in row chunks, x and g_y are randn + 2 (sums that do not cancel: a slab left out cannot
+hide inside the bound, which the test asserts from the geometry), y and g_x lie in guard-banded buffers over the NaN pattern, and
+the probe rows - head, tail, two rows on either side of every multiple of HH_TRIP, where a workgroup begins its next trip - equal
+a small call on the same rows bit for bit (the header's promise that any split of the batch gives the bits of one call).
 The worst measured ratio to every bound goes to householder_errors.json (pytest -q swallows prints) in the directory
 HINT_TEST_RECORDS names, test_records/ in the repository by default."""
 import contextlib
@@ -23,6 +42,7 @@ import hint_amd
 from hint_amd import _lib, householder as hh
 from hint_amd._lib import HintAmdError
 import householder_oracle as ho
+import large_cases as lc
 import stream_gate
 from guarded import FILLS, NAN_BITS, Guarded, bits_equal
 from util import rel_err
@@ -34,8 +54,24 @@ U = 2.0 ** -24
 BUILD, APPLY, GRAD = 0, 1, 2
 SLAB = _lib.load().hint_householder_geometry(1, 1, 0)
 BS = (1, 15, 16, 17, SLAB + 1, 2 * SLAB + 5)
-DN = sorted({(d, n) for d in (2, 5, 20, 100, 128) for n in (1, 2, d, d + 3)})
+# the edges: d = 1; the tile edge (16, 17); where hh_lds's ld takes its 16 more (32, 33); the ldx 68 / 132 switch and the build
+# kernel's second entry per lane (63, 64, 65); the most reflections (n = 256)
+DN = sorted({(d, n) for d in (2, 5, 20, 100, 128) for n in (1, 2, d, d + 3)}
+            | {(d, n) for d in (1, 16, 17, 32, 33, 63, 64, 65) for n in (1, d)} | {(20, 256), (128, 256)})
 WORST = {}
+
+
+def geometry(B, d):
+    """(R, slabs) of a grad run over B rows"""
+    lib = _lib.load()
+    R, slabs = int(lib.hint_householder_geometry(B, d, 0)), int(lib.hint_householder_geometry(B, d, 1))
+    assert R >= SLAB and R % 16 == 0 and (slabs - 1) * R < B <= slabs * R
+    return R, slabs
+
+
+def gw_factor(B, d):
+    """the g_W bound's factor of (|x|^T |g_y|)_ij (the module docstring derives it)"""
+    return (min(B, geometry(B, d)[0] // 4) + 8) * U
 
 
 def record(name, rec):
@@ -126,9 +162,16 @@ def test_build_apply_grad_against_the_statement(d, n):
             worst("g_x", r)
             assert r <= 1.0, (B, rev, r)
             a, b = (gy, x) if rev else (x, gy)
-            r = ratio(got["g_W"], gW64, (B + 8) * U * ho.abs_products(a.t(), b))
+            assert gw_factor(B, d) <= (B + 8) * U
+            r = ratio(got["g_W"], gW64, gw_factor(B, d) * ho.abs_products(a.t(), b))
             worst("g_W", r)
             assert r <= 1.0, (B, rev, r)
+            if d == 1:                                      # the gradient is exactly zero: two terms of 4 |G| / |v| cancel
+                cancel = 64 * 2.0 ** -53 * 4 * ho.abs_products(a.t(), b) / Vs.double().abs()
+                r = max(ratio(got["g_V"], torch.zeros(n, d, dtype=torch.float64), cancel), float((gV64.abs() / cancel).max()))
+                worst("g_V_d1_over_cancellation_bound", r)
+                assert r <= 1.0, (B, rev, r)
+                continue
             e = rel_err(got["g_V"].cpu().numpy(), gV64.numpy())
             worst("g_V_rel_err_over_1e-4", e / 1e-4)
             assert e < 1e-4, (B, rev, e)
@@ -144,6 +187,156 @@ def test_apply_in_three_ragged_calls_gives_the_bits_of_one():
             cuts = (0, 7, SLAB + 19, x.shape[0])
             parts = [apply(x[a:b].contiguous(), W, rev) for a, b in zip(cuts, cuts[1:])]
             assert bits_equal(whole, torch.cat(parts))
+
+
+# ---- the regimes of a large batch, and the limit ----
+def first_B(pred, lo, hi):
+    """the smallest B in lo..hi with pred(B); pred is monotone"""
+    assert pred(hi) and not pred(lo)
+    while hi - lo > 1:
+        mid = (lo + hi) // 2
+        lo, hi = (lo, mid) if pred(mid) else (mid, hi)
+    return hi
+
+
+def regime_batches():
+    """{name: B}, each from the geometry query or the apply grid's rule"""
+    grows = first_B(lambda B: geometry(B, 5)[0] > SLAB, SLAB, hh.MAX_B)         # the first B whose slabs hold more than SLAB rows
+    assert geometry(grows - 1, 128) == (SLAB, 64) and geometry(grows, 128)[0] == SLAB + 16         # (the geometry ignores d)
+    groups = lambda B: -(-(-(-B // lc.HH_T)) // lc.HH_APPLY_WAVES)                                 # noqa: E731
+    trip = first_B(lambda B: groups(B) > lc.HH_MAX_GRID, 1, hh.MAX_B)           # the first B with more workgroups than the grid
+    assert trip == lc.HH_TRIP + 1
+    out = {"last_R_256": grows - 1, "first_R_above_256": grows,
+           "second_trip": lc.HH_TRIP + lc.HH_T + 1,                              # the second trip: a whole tile and one of one row
+           "idle_last_trip": 2 * lc.HH_TRIP + lc.HH_TRIP // 2 + 5}               # the third trip: half the workgroups have no tile
+    assert groups(out["second_trip"]) == lc.HH_MAX_GRID + 1 and out["second_trip"] % lc.HH_T
+    assert 2 * lc.HH_MAX_GRID < groups(out["idle_last_trip"]) < 3 * lc.HH_MAX_GRID and out["idle_last_trip"] % lc.HH_T
+    return out
+
+
+REGIMES = regime_batches()
+REF_CHUNK = lc.CHUNK_ELEMS // 4       # elements of a float64 temporary of the device references: 0.5 GiB
+assert REF_CHUNK <= lc.CHUNK_ELEMS
+
+
+def row_chunks(B, d):
+    step = max(1, REF_CHUNK // d)
+    return [(a, min(B, a + step)) for a in range(0, B, step)]
+
+
+def rows_ratio(got, src, M64, k):
+    """largest |got - src M| / (k u |src| |M|) over the entries: float64 on the device, in row chunks"""
+    out = 0.0
+    for a, b in row_chunks(*src.shape):
+        s = src[a:b].double()
+        err = (got[a:b].double() - s @ M64).abs_()
+        bound = (s.abs_() @ M64.abs()).mul_(k * U).clamp_min_(1e-300)
+        assert bool(torch.isfinite(err).all())
+        out = max(out, float(err.div_(bound).max()))
+    return out
+
+
+def gram64(a, b):
+    """(a^T b, |a|^T |b|) in float64 on the device, in row chunks"""
+    d = a.shape[1]
+    G, A = torch.zeros(d, d, dtype=torch.float64, device=DEV), torch.zeros(d, d, dtype=torch.float64, device=DEV)
+    for lo, hi in row_chunks(*a.shape):
+        u, v = a[lo:hi].double(), b[lo:hi].double()
+        G += u.t() @ v
+        A += u.abs_().t() @ v.abs_()
+    return G, A
+
+
+def trip_probes(B):
+    """head, tail, and two rows on either side of every multiple of HH_TRIP inside the batch"""
+    rows = set(range(min(64, B))) | set(range(max(0, B - 80), B))
+    for m in range(lc.HH_TRIP, B + 2, lc.HH_TRIP):
+        rows |= {r for r in (m - 2, m - 1, m, m + 1) if 0 <= r < B}
+    return torch.tensor(sorted(rows), dtype=torch.int64, device=DEV)
+
+
+def no_nan_words(g, what):
+    left = lc.count_words(g.words, NAN_BITS)
+    assert left == 0, f"{what}: {left} words were never written"
+
+
+def large_batch(B, d, n, tag):
+    """apply and grad at both transposes over B rows of randn + 2, as the module docstring says"""
+    R, slabs = geometry(B, d)
+    assert 1.0 / slabs >= 10 * (R // 4 + 8) * U, (R, slabs)             # a slab left out moves an entry by ten bounds at least
+    Vs = ho.init_Vs(n, d, seed=1000 * d + n)
+    Vd, W64 = Vs.to(DEV), ho.W(Vs).to(DEV)
+    W = build(Vd)
+    g = torch.Generator(device=DEV).manual_seed(B % 100003 + d)
+    x, gy = torch.empty(B, d, device=DEV), torch.empty(B, d, device=DEV)
+    for t in (x, gy):
+        lc.fill_chunked(t, lambda m: torch.randn(m, d, generator=g, device=DEV).add_(2.0), REF_CHUNK)
+    rt = trip_probes(B)
+    xp, gyp = x[rt].contiguous(), gy[rt].contiguous()
+    ws = torch.empty(ws_bytes(B, d, n), dtype=torch.uint8, device=DEV)
+    y, g_x = Guarded(B * d, "nan"), Guarded(B * d, "nan")
+    for rev in (False, True):
+        M = W64.t() if rev else W64
+        what = f"B {B} d {d} rev {rev}"
+        y.fill("nan")
+        hh._run(APPLY, DEV, B=B, d=d, transpose=rev, W=W, x=x, y=y.view(B, d))
+        torch.cuda.synchronize()
+        y.check_guards(what + ": y")
+        no_nan_words(y, what + ": y")
+        r = rows_ratio(y.view(B, d), x, M, d + 8)
+        worst(tag + "apply", r)
+        assert r <= 1.0, (what, r)
+        assert bits_equal(y.view(B, d)[rt], apply(xp, W, rev)), what + ": a probe row's bits depend on its position"
+        g_x.fill("nan")
+        got = {"g_x": g_x.view(B, d), "g_W": torch.empty(d, d, device=DEV), "g_V": torch.empty(n, d, device=DEV)}
+        hh._run(GRAD, DEV, B=B, d=d, n=n, transpose=rev, Vs=Vd, W=W, x=x, g_y=gy, workspace=ws, **got)
+        torch.cuda.synchronize()
+        g_x.check_guards(what + ": g_x")
+        no_nan_words(g_x, what + ": g_x")
+        r = rows_ratio(got["g_x"], gy, M.t(), d + 8)
+        worst(tag + "g_x", r)
+        assert r <= 1.0, (what, r)
+        small = grad(xp, gyp, W, Vd, rev, want=("g_x",))
+        assert bits_equal(got["g_x"][rt], small["g_x"]), what + ": a probe row's bits of g_x depend on its position"
+        a, b = (gy, x) if rev else (x, gy)
+        G64, A64 = gram64(a, b)
+        r = ratio(got["g_W"], G64.cpu(), (gw_factor(B, d) * A64).cpu())
+        worst(tag + "g_W", r)
+        assert r <= 1.0, (what, r)
+        e = rel_err(got["g_V"].cpu().numpy(), ho.g_V_from_g_W(Vs, G64.cpu()).numpy())
+        worst(tag + "g_V_rel_err_over_1e-4", e / 1e-4)
+        assert e < 1e-4, (what, e)
+        # two grad runs give equal bits (the second g_x goes where y was: y has been checked)
+        y.fill("nan")
+        again = {"g_x": y.view(B, d), "g_W": torch.empty(d, d, device=DEV), "g_V": torch.empty(n, d, device=DEV)}
+        hh._run(GRAD, DEV, B=B, d=d, n=n, transpose=rev, Vs=Vd, W=W, x=x, g_y=gy, workspace=ws, **again)
+        torch.cuda.synchronize()
+        assert all(bits_equal(got[k], again[k]) for k in got), what + ": two grad runs differ"
+        print(f"householder {what}: R {R}, {slabs} slabs; ratios " + ", ".join(f"{k[len(tag):]} {v:.3g}" for k, v in WORST.items()
+                                                                                 if k.startswith(tag)))
+
+
+@pytest.mark.parametrize("d", (5, 100))
+@pytest.mark.parametrize("regime", list(REGIMES))
+def test_large_batch_regimes(regime, d):
+    large_batch(REGIMES[regime], d, d, "large_B_")
+
+
+LIMIT_BYTES = 4 * 4 * hh.MAX_B * hh.MAX_D + 6 * 8 * REF_CHUNK      # x, g_y, y, g_x; six float64 temporaries of a reference chunk
+
+
+@pytest.mark.timeout(120)
+def test_the_row_limit():
+    """B = 2^22, d = 128, n = 128: the documented limit, where the last element offset is 2^29 - 1 (tests/large_cases.py LIMITED)"""
+    torch.cuda.empty_cache()
+    free, _ = torch.cuda.mem_get_info()
+    if free < LIMIT_BYTES:
+        pytest.skip(f"needs {LIMIT_BYTES / lc.GIB:.1f} GiB of device memory, {free / lc.GIB:.1f} GiB are free")
+    assert _lib.load().hint_householder_workspace_bytes(GRAD, hh.MAX_B + 1, hh.MAX_D, hh.MAX_D) == 0
+    try:
+        large_batch(hh.MAX_B, hh.MAX_D, hh.MAX_D, "limit_B_")
+    finally:
+        torch.cuda.empty_cache()
 
 
 def test_nan_patterns():

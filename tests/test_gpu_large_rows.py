@@ -7,7 +7,11 @@ What each case asserts: the guards are intact (no write far from the buffer); no
 float64 oracle of the kernel at that oracle's own bounds, and, where the project promises that a row's bits do not depend on its
 position, bit equality with a small call on the same rows; whole-batch reductions against float64 on the device, in chunks.
 Inputs are seeded and generated on the device in row chunks; at most one case is alive at a time and its memory is handed back
-in a finally.  A case skips, naming the figure, only when the device has less free memory than it declares."""
+in a finally.  A case skips, naming the figure, only when the device has less free memory than it declares.
+The plus-shape sampler has a case for each of its two wide arrays (they leave the kernel by different code), with the Philox row
+counter's high word changing inside the call; the epoch case runs the three epoch ops in turn on one table, the output
+re-poisoned between them, and compares the WHOLE gathered and standardised tables bit for bit, in chunks.  Entry points whose
+documented limits keep every offset below 2^31 run at those limits in their own files (tests/large_cases.py LIMITED)."""
 import ctypes as C
 import time
 
@@ -16,15 +20,17 @@ import pytest
 import torch
 
 import hint_amd
-from hint_amd import _lib, curves
+from hint_amd import _lib, curves, data
 import abc_oracle as ao
 import corr_oracle as cro
 import curve_oracle as co
+import epoch_oracle as eo
 import hausdorff_oracle as ho
 import lensfit_oracle as lo
 import overlap_oracle as oo
 import plusfit_oracle as pfo
 import plus_oracle as po
+import plusgen_oracle as pgo
 import large_cases as lc
 import shapegen_oracle as so
 from guarded import NAN_BITS, Guarded, bits_equal
@@ -430,6 +436,96 @@ def test_lensgen():
         lc.release(bufs)
 
 
+PLUSGEN_TABLE = dict(x=((100,), torch.float32), y=((4,), torch.float32), outline=((128, 2), torch.float32), counts=((), torch.int32),
+                     corners=((), torch.int32), draws_out=((9,), torch.float32))
+NORMAL_BOUND = 2.0 ** -13            # the hardware's log2 / sin / cos, as tests/test_gpu_plusgen.py holds the sampler's normals
+
+
+def plusgen_case(name):
+    """hint_plusgen_run with one wide array (the other NULL) past 2^31 elements, the Philox row counter's high word changing inside
+    the call.  On the probe rows and the four rows around the flip: the bits of small calls of the public samplers at offset +
+    first (a row is a function of (seed, row) alone), the draws the oracle's Philox at offset + row, and the float64 oracle under
+    its own rule on the rows that are not ambiguous"""
+    case = CASES[name]
+    lc.require_memory(case)
+    lib, bufs, t0 = _lib.load(), {}, time.time()
+    N, w, named, seed, off = case["N"], case["width"], case["named"], case["params"]["seed"], case["params"]["offset"]
+    assert N * w > lc.EDGE and off < 2 ** 32 < off + N                                       # the high word changes mid-call
+    try:
+        nbytes = lib.hint_plusgen_workspace_bytes(N)
+        desc = _lib.PlusGenDesc()
+        desc.n_rows, desc.seed, desc.offset, desc.max_groups, desc.draws, desc.rows, desc.target = N, seed, off, 0, None, None, None
+        out = {}
+        for field, (shape, dtype) in PLUSGEN_TABLE.items():
+            elems = dict((a, n) for a, n, _ in case["arrays"]).get(field)
+            if elems is None:
+                setattr(desc, field, None)
+                continue
+            assert elems == N * int(np.prod(shape))
+            g = nan_out(bufs, field, elems, dtype)
+            setattr(desc, field, g.ptr)
+            out[field] = g.view(N, *shape)
+        assert named in out and ("x" in out) != ("outline" in out)
+        gw = nan_out(bufs, "workspace", nbytes // 4, torch.int32)
+        desc.workspace, desc.workspace_bytes, desc.stream = gw.ptr, nbytes, stream()
+        _lib.check(lib.hint_plusgen_run(C.byref(desc)), "hint_plusgen_run")
+        torch.cuda.synchronize()
+        check_written(bufs, tuple(out) + ("workspace",), name)
+        assert int(gw.words.sum()) == 0                                                      # no Philox row is rejected
+        flip = 2 ** 32 - off                                                                 # the first row of high word 1
+        rows, rt = probes(case, extra=(flip - 2, flip - 1, flip, flip + 1))
+        assert {flip - 2, flip - 1, flip, flip + 1} <= set(rows)
+        for first, n in lc.runs_of(rows):                                                    # small calls at offset + first
+            sl = slice(first, first + n)
+            xs, ys = hint_amd.sample_plus_joint(n, seed, offset=off + first, device=DEV)
+            assert bits_equal(ys, out["y"][sl]), first
+            if named == "x":
+                assert bits_equal(xs, out["x"][sl]) and bits_equal(hint_amd.sample_plus_prior(n, seed, offset=off + first, device=DEV),
+                                                                   out["x"][sl]), first
+            else:
+                _, o2, c2 = hint_amd.sample_plus_prior(n, seed, offset=off + first, device=DEV, return_outline=True)
+                o3, c3, y3 = hint_amd.plus_outlines(out["draws_out"][sl].contiguous())
+                assert bits_equal(o2, out["outline"][sl]) and torch.equal(c2, out["counts"][sl]), first
+                assert bits_equal(o3, out["outline"][sl]) and torch.equal(c3, out["counts"][sl]) and bits_equal(y3, out["y"][sl]), first
+        d = out["draws_out"][rt].cpu().numpy()
+        at, e_normal = 0, 0.0
+        for first, n in lc.runs_of(rows):                                                    # the draws are the oracle's Philox at
+            want_d = pgo.draws(seed, off + first, n)                                         # counter offset + row, high word included
+            assert (d[at:at + n, :7] == want_d[:, :7].astype(np.float32)).all(), first       # exact: part of the definition
+            e_normal = max(e_normal, float(np.abs(d[at:at + n, 7:] - want_d[:, 7:]).max()))
+            at += n
+        assert e_normal <= NORMAL_BOUND, e_normal
+        want = pgo.sample(d)
+        keep = ~pgo.ambiguous(d)
+        assert (~keep).mean() <= pgo.MAX_AMBIGUOUS
+        # (the oracle's rule takes every output: what this case leaves NULL is given as the oracle's own, and not reported)
+        got = {k: (out[k][rt].cpu().numpy() if k in out else want[k]) for k in ("x", "y", "outline", "counts")}
+        if "corners" in out:
+            c = out["corners"][rt].cpu().numpy()
+            got["corners"] = c & 15
+            assert ((c >> 4)[keep] == want["arms"][keep]).all()
+            cnt = got["counts"]
+            assert all((got["outline"][i, cnt[i]:] == 0).all() for i in range(len(rows)))    # zero padding behind the outline
+        else:
+            got["corners"] = want["corners"]
+        res = pgo.compare(got, want, keep)
+        assert pgo.passes(res), res
+        given = set(out) | {"center", "angle", "ratio"}
+        report(case, t0, normals=e_normal, ambiguous=float((~keep).mean()), **{k: v for k, v in res.items() if k in given})
+    finally:
+        lc.release(bufs)
+
+
+@pytest.mark.timeout(120)
+def test_plusgen_outline():
+    plusgen_case("plusgen_outline")
+
+
+@pytest.mark.timeout(120)
+def test_plusgen_x():
+    plusgen_case("plusgen_x")
+
+
 @pytest.mark.timeout(120)
 def test_fcoef():
     case = CASES["fcoef"]
@@ -575,5 +671,81 @@ def test_corr():
         assert out[2] == d * d and out[3] == 0 and abs(out[0] - mse) <= 2 * d * d * 2.0 ** -53 * mse, (out, mse)
         assert abs(out[0] - out[1] / out[2]) <= 2.0 ** -52 * out[0]
         report(case, t0, entry_err=err, bound=bound)
+    finally:
+        lc.release(bufs)
+
+
+@pytest.mark.timeout(120)
+def test_epoch():
+    """the three epoch ops in turn on one table x [N, 100] past 2^31 elements, the output re-poisoned between them.
+    GATHER, a whole shuffled epoch (count = N: the output's element offsets base * d pass 2^31 as the source's do): the indices
+    are a permutation and the oracle's at the probe positions, every row of the output is x.index_select's bit for bit.
+    MOMENTS over all rows (the slab cap: 1024 slabs of far more than 256 rows): against float64 column sums made on the device in
+    chunks, within the 2 E_m and 2 E_s tests/epoch_oracle.py derives, evaluated for this N; two runs give equal bits.
+    STANDARDIZE out of place (the tile loop's later trips): every element torch's double arithmetic, bit for bit"""
+    case = CASES["epoch"]
+    lc.require_memory(case)
+    lib, bufs, t0 = _lib.load(), {}, time.time()
+    N, d, seed, epoch = case["N"], case["params"]["d"], case["params"]["seed"], case["params"]["epoch"]
+    dev = torch.device(DEV)
+    assert N * d > lc.EDGE and case["width"] == d
+    try:
+        g = gen(901)
+        x = bufs["x"] = torch.empty(N, d, device=DEV)
+        lc.fill_chunked(x, lambda n: torch.randn(n, d, generator=g, device=DEV).mul_(3.0).add_(1.5))
+        go, gi = nan_out(bufs, "out_x", N * d), nan_out(bufs, "indices_out", 2 * N, torch.int32)
+        nbytes = lib.hint_epoch_workspace_bytes(_lib.EPOCH_GATHER, N, N, d)
+        gw = nan_out(bufs, "workspace", nbytes // 4, torch.int32)
+        out, idx = go.view(N, d), gi.words.view(torch.int64)
+        # ---- gather ----
+        data._gather_run(x, None, N, seed, epoch, True, (0, N, 0, 0), dev, want=("out_x", "indices_out"),
+                         out=dict(out_x=out, indices_out=idx, workspace=gw.t))
+        torch.cuda.synchronize()
+        check_written(bufs, ("out_x", "indices_out", "workspace"), "epoch gather")
+        assert int(gw.words.sum()) == 0                                                      # no position is rejected
+        assert torch.equal(idx.sort().values, torch.arange(N, device=DEV))                   # a permutation of the rows
+        rows, rt = probes(case)
+        want = eo.source_rows(N, seed, epoch, np.asarray(rows, dtype=np.uint64))
+        assert torch.equal(idx[rt], torch.from_numpy(want).to(DEV))
+        assert not torch.equal(idx[rt], rt)                                                  # (shuffled)
+        step = lc.CHUNK_ELEMS // d
+        for a in range(0, N, step):
+            assert bits_equal(out[a:a + step], x.index_select(0, idx[a:a + step])), a
+        # ---- moments ----
+        gm, gs = nan_out(bufs, "mean", 2 * d, torch.int32), nan_out(bufs, "std", 2 * d, torch.int32)
+        mbytes = lib.hint_epoch_workspace_bytes(_lib.EPOCH_MOMENTS, N, N, d)
+        gmw = nan_out(bufs, "moments_workspace", mbytes // 4, torch.int32)
+        ds = hint_amd.DeviceDataset(x, seed=seed)
+        assert ds.x.data_ptr() == x.data_ptr()                                               # the table is used in place
+        mean, std = ds.moments(0, N, out=dict(mean=gm.words.view(torch.float64), std=gs.words.view(torch.float64), workspace=gmw.t))
+        torch.cuda.synchronize()
+        check_written(bufs, ("mean", "std", "moments_workspace"), "epoch moments")
+        cs = lc.CHUNK_ELEMS // 4 // d                                                        # a float64 temporary of 0.5 GiB
+        zero = lambda: torch.zeros(d, dtype=torch.float64, device=DEV)                       # noqa: E731
+        s1, sa, s2 = zero(), zero(), zero()
+        for a in range(0, N, cs):
+            v = x[a:a + cs].double()
+            s1 += v.sum(0)
+            sa += v.abs_().sum(0)
+        m64, a64 = s1 / N, sa / N
+        for a in range(0, N, cs):
+            s2 += x[a:a + cs].double().sub_(m64).square_().sum(0)
+        sd64 = (s2 / N).sqrt()
+        e_m = (N + 1) * eo.U * a64                                                           # epoch_oracle's E_m and E_s for this N: the
+        e_s = ((N + 4) / 2 + 1) * eo.U * (sd64 + e_m) + e_m                                  # device and the reference each stay within them
+        dm, dsd = (mean - m64).abs(), (std - sd64).abs()
+        assert bool((dm <= 2 * e_m).all()) and bool((dsd <= 2 * e_s).all()), (dm / e_m, dsd / e_s)
+        assert float((2 * e_m / a64).max()) < 1e-8                                           # (256 rows left out move a mean by 1e-5 of it)
+        m2, sd2 = ds.moments(0, N)
+        assert bits_equal(m2, mean) and bits_equal(sd2, std)                                 # two runs: equal bits
+        # ---- standardize, out of place ----
+        go.fill("nan")
+        assert ds.apply_moments(mean, std, out=out) is out
+        torch.cuda.synchronize()
+        check_written(bufs, ("out_x",), "epoch standardize")
+        for a in range(0, N, cs):
+            assert bits_equal(out[a:a + cs], x[a:a + cs].double().sub_(mean).div_(std).float()), a
+        report(case, t0, mean_over_2Em=float((dm / (2 * e_m)).max()), std_over_2Es=float((dsd / (2 * e_s)).max()),
+               Em_over_mean_abs=float((e_m / a64).max()))
     finally:
         lc.release(bufs)

@@ -1,21 +1,34 @@
 """The table of the large-index tests (tests/large_cases.py) checked without a GPU: every case is admissible for its entry point,
 its named array holds more than 2^31 elements at the smallest ragged N, the probe rows bracket the three crossings, the declared
-memory covers the arrays and stays under the cap, and the oracle-side caps hold on the seeded probe rows."""
+memory covers the arrays and stays under the cap, and the oracle-side caps hold on the seeded probe rows.  The ledgers are held
+against include/hint_amd.h: every function that takes a descriptor is the `entry` of a case, or in LIMITED (its documented limits
+keep every offset below 2^31; the size query refuses one past them, and a named test runs it at them), or in NOT_COVERED; the
+moduli of the cases that have no geometry query are the constants of the kernels' text."""
+import ast
+import fnmatch
+import os
+import re
+
 import numpy as np
 import pytest
 
 from hint_amd import _lib
 import large_cases as lc
+import plusgen_oracle as pgo
 import shapegen_oracle as so
+from test_poison_table_cpu import ROOT, declarations
 
 CASES = list(lc.ROW_CASES.values())
 IDS = [c["name"] for c in CASES]
 
 
 def tiles(case):
-    """(rows a workgroup has in flight, workgroups) from the entry point's geometry query; (64, 256) where it has none"""
+    """(rows a workgroup has in flight, workgroups) from the entry point's geometry query; where it has none, the case's `grid`
+    (the kernel's constants, held against its text below), or (64, 256)"""
     lib = _lib.load()
     if case["geometry"] is None:
+        if case["grid"] is not None:
+            return case["grid"]
         return 64, 256
     fn, args = case["geometry"]
     f = getattr(lib, fn)
@@ -122,10 +135,139 @@ def test_lensgen_probe_rows_stay_within_the_ambiguity_cap():
     assert so.ambiguous(d).mean() <= so.MAX_AMBIGUOUS
 
 
+def test_plusgen_probe_rows_stay_within_the_ambiguity_cap():
+    """the oracle alone, on the Philox draws of both plusgen cases' probe rows (the rows around the counter's high-word flip
+    included): the share of rows whose ring or counts the fp32 kernel may miss"""
+    for name in ("plusgen_outline", "plusgen_x"):
+        case = lc.ROW_CASES[name]
+        seed, off, N = case["params"]["seed"], case["params"]["offset"], case["N"]
+        flip = 2 ** 32 - off
+        rows = lc.probe_rows(N, case["width"], extra=(flip - 2, flip - 1, flip, flip + 1))
+        assert {flip - 2, flip - 1, flip, flip + 1} <= set(rows) and off < 2 ** 32 < off + N
+        d = np.concatenate([pgo.draws(seed, off + first, n) for first, n in lc.runs_of(rows)])
+        assert d.shape == (len(rows), 9)
+        share = float(pgo.ambiguous(d).mean())
+        print(f"{name}: {share:.4f} of {len(rows)} probe rows are ambiguous")
+        assert share <= pgo.MAX_AMBIGUOUS
+
+
+def kernel_constants(source, names):
+    """{name: value} of `constexpr int NAME = <integer expression of literals and earlier constants>;` in a kernel's text"""
+    text = open(os.path.join(ROOT, "hint_amd", "csrc", source)).read()
+    env = {}
+    for m in re.finditer(r"constexpr\s+int\s+(\w+)\s*=\s*([\w\s+\-*/()<]+);", text):
+        try:
+            env[m.group(1)] = int(eval(m.group(2).replace("/", "//"), {"__builtins__": {}}, dict(env)))
+        except (NameError, SyntaxError):
+            pass
+    return {n: env[n] for n in names}
+
+
+def test_the_moduli_are_the_kernels_constants():
+    pg = kernel_constants("hint_plusgen.hip", ("PG_WAVE_ROWS", "PG_WAVES", "PG_MAX_WG", "PG_ROW", "PG_PTS"))
+    assert (pg["PG_WAVE_ROWS"], pg["PG_WAVES"], pg["PG_MAX_WG"]) == (lc.PG_WAVE_ROWS, lc.PG_WAVES, lc.PG_MAX_WG)
+    assert pg["PG_ROW"] == lc.ROW_CASES["plusgen_x"]["width"] and 2 * pg["PG_PTS"] == lc.ROW_CASES["plusgen_outline"]["width"]
+    ep = kernel_constants("hint_epoch.hip", ("EP_TILE", "EP_MAX_WG", "EP_MAX_SLABS"))
+    assert (ep["EP_TILE"], ep["EP_MAX_WG"], ep["EP_MAX_SLABS"]) == (lc.EP_TILE, lc.EP_MAX_WG, lc.EP_MAX_SLABS)
+    hh = kernel_constants("hint_householder.hip", ("HH_MAX_B", "HH_MAX_D", "HH_MAX_N", "HH_T", "HH_MAX_GRID"))
+    assert (hh["HH_MAX_B"], hh["HH_MAX_D"], hh["HH_MAX_N"]) == (lc.HH_MAX_B, lc.HH_MAX_D, lc.HH_MAX_N)
+    assert (hh["HH_T"], hh["HH_MAX_GRID"]) == (lc.HH_T, lc.HH_MAX_GRID) and lc.HH_TRIP == 16 * 4 * 1024
+    text = open(os.path.join(ROOT, "hint_amd", "csrc", "hint_householder.hip")).read()
+    assert f"t0 += {lc.HH_APPLY_WAVES} * (int)gridDim.x" in text and "cdiv(cdiv(B, HH_T), 4)" in text      # four tiles a workgroup
+    lib = _lib.load()
+    for name in ("plusgen_outline", "plusgen_x"):
+        c = lc.ROW_CASES[name]
+        N, off = c["N"], c["params"]["offset"]
+        assert lib.hint_plusgen_workspace_bytes(N) == 4 * lc.PG_WAVES * lc.PG_MAX_WG        # the grid is at its cap
+        assert lib.hint_plusgen_workspace_bytes(c["limit"] + 1) == 0
+        assert N % lc.PG_WAVE_ROWS and N % (lc.PG_WAVE_ROWS * lc.PG_WAVES) and -(-N // lc.PG_WAVE_ROWS) % (lc.PG_WAVES * lc.PG_MAX_WG)
+        assert off < 2 ** 32 < off + N < 2 ** 64                              # the row counter's high word changes inside the call
+    c = lc.ROW_CASES["epoch"]
+    N, d = c["N"], c["params"]["d"]
+    for op in (_lib.EPOCH_GATHER, _lib.EPOCH_MOMENTS, _lib.EPOCH_STANDARDIZE):
+        assert lib.hint_epoch_workspace_bytes(op, N, N, d) > 0 and lib.hint_epoch_workspace_bytes(op, N, N + 1, d) == 0
+    assert lib.hint_epoch_workspace_bytes(_lib.EPOCH_GATHER, c["limit"] + 1, 1, d) == 0
+    assert lib.hint_epoch_workspace_bytes(_lib.EPOCH_MOMENTS, N, N, d) == 8 * d * lc.EP_MAX_SLABS     # the slab cap is reached ...
+    assert -(-N // lc.EP_MAX_SLABS) > lc.EP_TILE and -(-N // lc.EP_TILE) > 2 * lc.EP_MAX_WG             # ... and the tile loops go round
+
+
+def descriptor_entry_points():
+    """every function of include/hint_amd.h whose first parameter is the descriptor of a run, `const hint_*_desc* desc` (the
+    planner's `const hint_node_desc* nodes` is an array of tree nodes, not a descriptor)"""
+    return sorted(n for n, ps in declarations().items()
+                  if ps and re.match(r"^const hint_\w+_desc ?\* ?desc$", " ".join(ps[0].split())))
+
+
+def ledger_errors(cases, not_covered, limited):
+    """what is wrong with the three ledgers against the header, as a list of sentences"""
+    decls, need = declarations(), descriptor_entry_points()
+    places = {"ROW_CASES": {c["entry"] for c in cases}, "NOT_COVERED": set(not_covered), "LIMITED": set(limited)}
+    out = []
+    missing = [e for e in need if not any(e in s for s in places.values())]
+    if missing:
+        out.append(f"descriptor entry points in none of ROW_CASES, LIMITED and NOT_COVERED of tests/large_cases.py: {missing}")
+    for e in need:
+        where = [k for k, s in places.items() if e in s]
+        if len(where) > 1:
+            out.append(f"{e} is in {where}: an entry point belongs to one ledger")
+    for k, s in places.items():
+        for e in sorted(s):
+            if "*" in e:                                                    # a family that takes no descriptor, by pattern
+                hit = fnmatch.filter(decls, e)
+                if k != "NOT_COVERED" or not hit or set(hit) & set(need):
+                    out.append(f"{k} names the pattern {e}, which matches {hit or 'nothing the header declares'}")
+            elif e not in need:
+                out.append(f"{k} names {e}, which is no descriptor entry point of the header")
+    return out
+
+
+def test_the_header_has_the_descriptor_entry_points():
+    need = descriptor_entry_points()
+    assert len(need) >= 14 and {"hint_curve_run", "hint_mmd_run", "hint_plusgen_run", "hint_householder_run", "hint_epoch_run"} <= set(need)
+    assert not [e for e in need if "plan" in e]
+    assert all(e in _lib.exported_symbols() for e in need)
+
+
 def test_the_entry_points_left_out_are_written_down():
+    """every descriptor entry point of the header is in exactly one of: a case's `entry`, LIMITED, NOT_COVERED; no ledger names
+    what the header does not declare"""
     assert set(lc.NOT_COVERED) == {"hint_mmd_run", "hint_adam_*"}
-    covered = {c["entry"] for c in CASES}
-    assert not covered & set(lc.NOT_COVERED) and all(e in _lib.exported_symbols() for e in covered)
+    errors = ledger_errors(CASES, lc.NOT_COVERED, getattr(lc, "LIMITED", {}))
+    assert not errors, "\n".join(errors)
+    assert all(r.strip() for r in lc.NOT_COVERED.values()) and all(rec["reason"].strip() for rec in lc.LIMITED.values())
+
+
+def test_the_ledger_check_notices_what_it_should():
+    need = descriptor_entry_points()
+    full = [dict(entry=e) for e in need]
+    assert ledger_errors(full, {}, {}) == []
+    e = ledger_errors(full[1:], {}, {})
+    assert len(e) == 1 and need[0] in e[0]
+    assert any("one ledger" in s for s in ledger_errors(full, {}, {need[0]: {}}))
+    assert any("one ledger" in s for s in ledger_errors(full, {need[0]: ""}, {}))
+    assert any("hint_gone_run" in s for s in ledger_errors(full, {"hint_gone_run": ""}, {}))
+    assert any("hint_gone_run" in s for s in ledger_errors(full + [dict(entry="hint_gone_run")], {}, {}))
+    assert any("hint_nothing_*" in s for s in ledger_errors(full, {"hint_nothing_*": ""}, {}))
+    assert any("hint_*_run" in s for s in ledger_errors(full, {"hint_*_run": ""}, {}))      # a pattern may not swallow a descriptor run
+    assert ledger_errors(full, {"hint_adam_*": ""}, {}) == []
+
+
+def test_limited_entry_points_are_refused_past_their_limits_and_run_at_them():
+    """LIMITED: the size query accepts the limit and refuses one past each of them, every element offset at the limit is below
+    2^31, and the test that runs the entry point AT the limit exists"""
+    lib = _lib.load()
+    for entry, rec in lc.LIMITED.items():
+        f = getattr(lib, rec["sizer"])
+        assert f(*rec["at"]) > 0, (entry, (lib.hint_last_error() or b"").decode())
+        for args in rec["over"]:
+            assert args != rec["at"] and f(*args) == 0 and lib.hint_last_error(), (entry, args)
+        assert 0 < rec["elements"] < lc.EDGE
+        path, name = rec["test"].split("::")
+        tree = ast.parse(open(os.path.join(ROOT, path)).read())
+        defined = {n.name for n in tree.body if isinstance(n, ast.FunctionDef) and n.name.startswith("test_")}
+        assert name in defined, f"{entry}: {rec['test']} does not exist"
+    hh = lc.LIMITED["hint_householder_run"]
+    assert hh["elements"] == hh["at"][1] * hh["at"][2] and hh["at"][1:] == (lc.HH_MAX_B, lc.HH_MAX_D, lc.HH_MAX_D)
 
 
 # ---- the flow cases ----

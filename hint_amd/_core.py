@@ -88,13 +88,15 @@ class TrainerCore:
     """The state both trainers keep and the launches both make on it.  `engines` is the model's engines in arena order."""
 
     def __init__(self, flow, engines, device: torch.device, lr: float, betas, eps: float, weight_decay: float, grad_clamp: float,
-                 noise: float, use_graph: bool, group, seed: Optional[int]):
+                 noise: float, use_graph: bool, group, seed: Optional[int], learned_perms: bool = False):
         from .householder import trainable        # (householder.py imports hint.py: not at module level here)
-        if any(map(trainable, flow.modules())):
-            # (the chained backward does not emit dL/dW of a permutation)
+        learned = [m for m in flow.modules() if trainable(m)]
+        if learned and not learned_perms:
+            # (the chained backward does not emit dL/dW of a permutation; FlowTrainer's block-by-block route does, on request)
             raise _lib.HintAmdError(f"{type(self).__name__}: the model has trainable Householder permutations (learned_perms=True), "
                                     "which the fused step does not train; use the module route - loss.backward() and "
-                                    "hint_amd.ClampAdam over model.parameters() - for such a model")
+                                    "hint_amd.ClampAdam over model.parameters() - for such a model, or, for a HintFlow, "
+                                    "FlowTrainer(flow, learned_perms=True)")
         self.lib = _lib.load()
         self.flow, self.device, self.group = flow, device, group
         self._lr, self.betas, self.eps, self.wd = lr, betas, eps, weight_decay
@@ -105,11 +107,18 @@ class TrainerCore:
         # model-wide arenas (parameters / gradients / Adam moments); every engine is bound to its slice
         self.engines = engines
         self.slices, self.n_floats = slice_layout([e.total for e in engines])
+        # the trainable permutations' Vs (all [n, d], FlowTrainer(learned_perms=True)) lie behind every block slice, perm_stride
+        # floats apart: block offsets are those of a model without them, and the arena-wide clamp + Adam steps them as well
+        self.perm_mods = learned
+        self.perm_base = self.n_floats
+        self.perm_stride = -(-learned[0].Vs.numel() // 4) * 4 if learned else 0
+        self.n_floats += len(learned) * self.perm_stride
         self.P, self.G, self.M, self.V = (torch.zeros(self.n_floats, dtype=torch.float32, device=device) for _ in range(4))
         for e, (a, b) in zip(engines, self.slices):
             e.bind_external_arena(self.P[a:b])
             e.ensure_arena()
             e.pack()
+        self._bind_perms()
         rank, world = dp.world_info(group)
         if world > 1:
             # data-parallel replicas must start from the same weights (the reference idiom
@@ -134,6 +143,27 @@ class TrainerCore:
             seed = int.from_bytes(os.urandom(8), "little") >> 2
         self.rng_state = torch.tensor([rank_seed(seed, rank), 0], dtype=torch.int64, device=device)
         self.opt_state = torch.tensor([lr, betas[0], betas[1], 0.0, 0.0, 0.0, 0.0, 0.0], dtype=torch.float32, device=device)
+
+    def perm_slice(self, j: int, arena: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """the [n, d] view of trainable permutation j's slice of an arena (default: P)"""
+        m = self.perm_mods[j]
+        a = self.perm_base + j * self.perm_stride
+        return (self.P if arena is None else arena)[a:a + m.n * m.d].view(m.n, m.d)
+
+    def _bind_perms(self) -> bool:
+        """every trainable permutation's Vs.data is a view of its P slice; one rebound from outside (p.data = ..., .to()) is
+        copied back in.  -> whether any was"""
+        moved = False
+        for j, m in enumerate(self.perm_mods):
+            view = self.perm_slice(j)
+            if m.Vs.data_ptr() != view.data_ptr() or m.Vs.device != self.device:
+                if m.Vs.dtype != torch.float32:
+                    raise _lib.HintAmdError("hint_amd kernels are fp32 only (parameter dtype %s)" % m.Vs.dtype)
+                with torch.no_grad():
+                    view.copy_(m.Vs.data.to(self.device))
+                    m.Vs.data = view
+                moved = True
+        return moved
 
     @property
     def lr(self) -> float:

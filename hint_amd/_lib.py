@@ -133,6 +133,18 @@ class HouseholderDesc(C.Structure):
 HOUSEHOLDER_BUILD, HOUSEHOLDER_APPLY, HOUSEHOLDER_GRAD = 0, 1, 2
 
 
+class HouseholderMany(C.Structure):
+    """mirror of `hint_householder_many` (include/hint_amd.h); the stream is a field, not a parameter of the run"""
+    _fields_ = [("op", C.c_int32), ("m", C.c_int32), ("j", C.c_int32), ("B", C.c_int32), ("d", C.c_int32), ("n", C.c_int32),
+                ("Vs", C.c_void_p), ("vs_stride", C.c_int64), ("W", C.c_void_p), ("w_stride", C.c_int64), ("x", C.c_void_p),
+                ("g_y", C.c_void_p), ("g_x", C.c_void_p), ("g_W", C.c_void_p), ("gw_stride", C.c_int64), ("g_V", C.c_void_p),
+                ("gv_stride", C.c_int64), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("ws_stride", C.c_int64),
+                ("stream", C.c_void_p)]
+
+
+HOUSEHOLDER_MANY_BUILD, HOUSEHOLDER_MANY_ROWS, HOUSEHOLDER_MANY_FINISH = 0, 1, 2
+
+
 class EpochDesc(C.Structure):
     """mirror of `hint_epoch_desc` (include/hint_amd.h); the stream is a field, not a parameter of the run"""
     _fields_ = [("op", C.c_int32), ("shuffle", C.c_int32), ("d", C.c_int32), ("dy", C.c_int32), ("epoch", C.c_uint32),
@@ -256,6 +268,8 @@ _PROTOS = {
     "hint_householder_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "hint_householder_run": (C.c_int, [C.POINTER(HouseholderDesc)]),
     "hint_householder_geometry": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
+    "hint_householder_many_workspace_bytes": (C.c_size_t, [C.c_int32] * 5),
+    "hint_householder_many_run": (C.c_int, [C.POINTER(HouseholderMany)]),
     "hint_epoch_index": (C.c_int64, [C.c_int64, C.c_uint64, C.c_uint32, C.c_int32, C.c_int64]),
     "hint_epoch_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int64, C.c_int64, C.c_int32]),
     "hint_epoch_run": (C.c_int, [C.POINTER(EpochDesc)]),

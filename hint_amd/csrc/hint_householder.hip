@@ -20,9 +20,14 @@
 //   hint_hh_finish_kernel  the slab slots of each entry added in slab order, in double -> g_W; then (one workgroup, g_V asked)
 //                          g_V from that sum and Vs, in double, walking i = n-1 .. 0 with P = H_0 .. H_(i-1) and
 //                          Gs = G (H_(i+1) .. H_(n-1))^T kept in the workspace (the header states the recurrence)
+// hint_householder_many_run (the m permutations of one flow, trained by FlowTrainer(learned_perms=True)) runs the same device
+// functions: hint_hh_build_many_kernel makes every matrix in one launch (grid y = the permutation), the row work of permutation j
+// is the apply and gram kernels on slot j of the workspace, and hint_hh_finish_many_kernel gives every permutation's finish a
+// workgroup of its own, so the m serial walks over the reflections run side by side - with Gs and P in LDS where they fit (d <= 94).
 // No atomics, no counters: the same bits on every run.  Nothing special happens for a zero or non-finite v_i: the division gives NaN.
 #include "hint_host.hpp"
 #include "hint_device.hpp"
+#include "hint_householder.hpp"
 
 namespace hint {
 
@@ -34,6 +39,10 @@ constexpr int HH_MIN_R = 256;               // rows per slab of the Gram, at lea
 constexpr int HH_MAX_SLABS = 64;            // ... and as many more as keep the slab count at this
 constexpr int HH_MAX_GRID = 1024;           // workgroups of an apply launch, at most (each stages W once)
 constexpr int HH_FIN_THREADS = 1024;
+constexpr int HH_FIN_LDS_D = 94;            // the batched finish keeps Gs and P in LDS up to this d
+// (2 d^2 doubles beside hh_finish's own 19 KiB of vectors and partial sums: 157.1 KiB at d = 94, 16 bytes too many at d = 95)
+static_assert(2 * HH_FIN_LDS_D * HH_FIN_LDS_D * 8 + (3 + 2 * 8) * HH_MAX_D * 8 <= 160 * 1024, "the finish's matrices and vectors fit in LDS");
+static_assert(2 * (HH_FIN_LDS_D + 1) * (HH_FIN_LDS_D + 1) * 8 + (3 + 2 * 8) * HH_MAX_D * 8 > 160 * 1024, "... and HH_FIN_LDS_D is the last d that does");
 
 struct HhGeom { int nt, R, slabs; };
 __host__ __device__ inline HhGeom hh_geom(int B, int d) {
@@ -80,8 +89,7 @@ __device__ __forceinline__ double hh_wave_sum(double v) {      // every lane end
 }
 
 // ---- BUILD: wavefront w of block b makes row 4 b + w ----
-__global__ __launch_bounds__(256) void hint_hh_build_kernel(const float* __restrict__ Vs, int d, int n, float* __restrict__ W) {
-    const int l = threadIdx.x & 63, r = 4 * (int)blockIdx.x + ((int)threadIdx.x >> 6);
+__device__ __forceinline__ void hh_build_row(const float* __restrict__ Vs, int d, int n, float* __restrict__ W, int r, int l) {
     if (r >= d) return;                                     // (whole wavefronts: no barrier follows)
     const int c0 = l, c1 = l + 64;
     const bool ok0 = c0 < d, ok1 = c1 < d;
@@ -97,6 +105,15 @@ __global__ __launch_bounds__(256) void hint_hh_build_kernel(const float* __restr
     }
     if (ok0) W[(size_t)r * d + c0] = (float)w0;
     if (ok1) W[(size_t)r * d + c1] = (float)w1;
+}
+__global__ __launch_bounds__(256) void hint_hh_build_kernel(const float* __restrict__ Vs, int d, int n, float* __restrict__ W) {
+    hh_build_row(Vs, d, n, W, 4 * (int)blockIdx.x + ((int)threadIdx.x >> 6), threadIdx.x & 63);
+}
+// ... of permutation blockIdx.y of m: the same rows from the same arithmetic, all permutations in one launch
+__global__ __launch_bounds__(256) void hint_hh_build_many_kernel(const float* __restrict__ Vs, long vs_stride, int d, int n,
+                                                                 float* __restrict__ W, long w_stride) {
+    const long j = blockIdx.y;
+    hh_build_row(Vs + j * vs_stride, d, n, W + j * w_stride, 4 * (int)blockIdx.x + ((int)threadIdx.x >> 6), threadIdx.x & 63);
 }
 
 // ---- APPLY: y = x M, M[k][j] = W[k][j] (T = 0) or W[j][k] (T = 1) ----
@@ -180,17 +197,15 @@ __global__ __launch_bounds__(256) void hint_hh_gram_kernel(const float* __restri
     }
 }
 
-// ---- FINISH: the slab sum (every workgroup a share of the entries), then g_V by the one workgroup of a run that asks for it ----
-__global__ __launch_bounds__(hint::HH_FIN_THREADS) void hint_hh_finish_kernel(const float* __restrict__ part, int slabs, int nt,
-                                                                              int d, int n, const float* __restrict__ W,
-                                                                              const float* __restrict__ Vs, float* __restrict__ g_W,
-                                                                              float* __restrict__ g_V, double* __restrict__ Gs,
-                                                                              double* __restrict__ P) {
+// ---- FINISH: the slab sum (workgroup wg of nwg a share of the entries), then g_V by the one workgroup of a run that asks for it ----
+__device__ __forceinline__ void hh_finish(const float* __restrict__ part, int slabs, int nt, int d, int n, const float* __restrict__ W,
+                                          const float* __restrict__ Vs, float* __restrict__ g_W, float* __restrict__ g_V,
+                                          double* __restrict__ Gs, double* __restrict__ P, int wg, int nwg) {
     __shared__ double vs[hint::HH_MAX_D], av[hint::HH_MAX_D], bv[hint::HH_MAX_D];
     __shared__ double red[2][8][hint::HH_MAX_D];
     const int t = threadIdx.x;
     const size_t tiles = (size_t)nt * nt;
-    for (int idx = (int)blockIdx.x * hint::HH_FIN_THREADS + t; idx < d * d; idx += (int)gridDim.x * hint::HH_FIN_THREADS) {
+    for (int idx = wg * hint::HH_FIN_THREADS + t; idx < d * d; idx += nwg * hint::HH_FIN_THREADS) {
         const int i = idx / d, j = idx - i * d;
         const size_t off = ((size_t)(i >> 4) * nt + (j >> 4)) * 256 + 16 * (i & 15) + (j & 15);
         double s = 0.0;
@@ -249,6 +264,32 @@ __global__ __launch_bounds__(hint::HH_FIN_THREADS) void hint_hh_finish_kernel(co
             g_V[(size_t)i * d + t] = (float)(-f * qs + (4.0 * ab / (s * s)) * vs[t]);
         }
     }
+}
+__global__ __launch_bounds__(hint::HH_FIN_THREADS) void hint_hh_finish_kernel(const float* __restrict__ part, int slabs, int nt,
+                                                                              int d, int n, const float* __restrict__ W,
+                                                                              const float* __restrict__ Vs, float* __restrict__ g_W,
+                                                                              float* __restrict__ g_V, double* __restrict__ Gs,
+                                                                              double* __restrict__ P) {
+    hh_finish(part, slabs, nt, d, n, W, Vs, g_W, g_V, Gs, P, (int)blockIdx.x, (int)gridDim.x);
+}
+// ... of m permutations at once: workgroup j is the one workgroup of permutation j's finish, on slot j of the workspace (the
+// serial walks over the reflections overlap on m compute units instead of following each other).  IN_LDS (d <= HH_FIN_LDS_D): Gs and
+// P, the two d x d double matrices every reflection reads and rewrites, live in LDS instead of the slot - the same values through
+// the same operations in the same order, so the same bits; the slot then holds the slab tiles alone
+template <bool IN_LDS>
+__global__ __launch_bounds__(hint::HH_FIN_THREADS) void hint_hh_finish_many_kernel(char* __restrict__ ws, long ws_stride, size_t off_Gs,
+                                                                                   size_t off_P, int slabs, int nt, int d, int n,
+                                                                                   const float* __restrict__ W, long w_stride,
+                                                                                   const float* __restrict__ Vs, long vs_stride,
+                                                                                   float* __restrict__ g_W, long gw_stride,
+                                                                                   float* __restrict__ g_V, long gv_stride) {
+    extern __shared__ double hh_fin_mats[];                 // IN_LDS: [Gs: d x d][P: d x d]
+    const long j = blockIdx.x;
+    char* slot = ws + j * ws_stride * 4;
+    double* Gs = IN_LDS ? hh_fin_mats : (double*)(slot + off_Gs);
+    double* P = IN_LDS ? hh_fin_mats + d * d : (double*)(slot + off_P);
+    hh_finish((const float*)slot, slabs, nt, d, n, W + j * w_stride, Vs + j * vs_stride, g_W ? g_W + j * gw_stride : nullptr,
+              g_V + j * gv_stride, Gs, P, 0, 1);
 }
 
 // ---- the C ABI ----
@@ -359,3 +400,60 @@ int hint_householder_run(const hint_householder_desc* desc) {
 }
 
 }  // extern "C"
+
+// ---- the launches of hint_householder_many_run (hint_householder_many.hip holds its checks): m permutations a stride apart ----
+namespace hint {
+
+HhLimits hh_limits() { return {HH_MAX_D, HH_MAX_N, HH_MAX_B}; }
+
+size_t hh_grad_workspace_bytes(int B, int d) { return hh_layout(B, d).total; }
+
+int hh_many_build(const float* Vs, int64_t vs_stride, float* W, int64_t w_stride, int m, int d, int n, hipStream_t s) {
+    hipLaunchKernelGGL(hint_hh_build_many_kernel, dim3(cdiv(d, 4), m), dim3(256), 0, s, Vs, (long)vs_stride, d, n, W, (long)w_stride);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// g_x = g_y W^T (g_x may be null) and the slab partial tiles of x^T g_y into `slot`, a single grad run's workspace
+int hh_many_rows(const float* x, const float* g_y, const float* W, float* g_x, void* slot, int B, int d, hipStream_t s) {
+    const HhLayout L = hh_layout(B, d);
+    const HhGeom g = hh_geom(B, d);
+    if (g_x && hh_launch_apply(g_y, W, B, d, 1, g_x, s)) return 1;
+    hipLaunchKernelGGL(hint_hh_gram_kernel, dim3((unsigned)(g.slabs * g.nt * g.nt)), dim3(256), 0, s, x, g_y, B, d, g.nt, g.R,
+                       (float*)((char*)slot + L.part));
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int hh_many_finish(void* ws, int64_t ws_stride, const float* W, int64_t w_stride, const float* Vs, int64_t vs_stride, float* g_W,
+                   int64_t gw_stride, float* g_V, int64_t gv_stride, int m, int B, int d, int n, hipStream_t s) {
+    const HhLayout L = hh_layout(B, d);
+    const HhGeom g = hh_geom(B, d);
+    if (d <= HH_FIN_LDS_D) {
+        const int lds = 2 * d * d * 8;
+        if (lds > 32 * 1024) {
+            // once per device: no launch after the first sets an attribute (a captured run is preceded by a plain one)
+            static std::mutex mu;
+            static bool done[64] = {};
+            int dev = 0;
+            HIP_TRY(hipGetDevice(&dev));
+            std::lock_guard<std::mutex> lock(mu);
+            if (dev < 0 || dev >= 64 || !done[dev]) {
+                HIP_TRY(hipFuncSetAttribute((const void*)hint_hh_finish_many_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                            2 * HH_FIN_LDS_D * HH_FIN_LDS_D * 8));
+                if (dev >= 0 && dev < 64) done[dev] = true;
+            }
+        }
+        hipLaunchKernelGGL(hint_hh_finish_many_kernel<true>, dim3(m), dim3(HH_FIN_THREADS), lds, s, (char*)ws, (long)ws_stride, L.Gs, L.P,
+                           g.slabs, g.nt, d, n, W, (long)w_stride, Vs, (long)vs_stride, g_W,
+                           (long)gw_stride, g_V, (long)gv_stride);
+    } else {
+        hipLaunchKernelGGL(hint_hh_finish_many_kernel<false>, dim3(m), dim3(HH_FIN_THREADS), 0, s, (char*)ws, (long)ws_stride, L.Gs, L.P,
+                           g.slabs, g.nt, d, n, W, (long)w_stride, Vs, (long)vs_stride, g_W,
+                           (long)gw_stride, g_V, (long)gv_stride);
+    }
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+}  // namespace hint

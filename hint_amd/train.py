@@ -22,7 +22,8 @@ from . import _lib, dp
 from ._core import TrainerCore, _LossPair
 from .flow import HintFlow
 from .hint import HintAmdError, _as_input
-from .householder import perm_matrix
+from ._ops import _run_desc
+from .householder import perm_matrix, trainable
 
 
 class FlowTrainer(TrainerCore):
@@ -31,13 +32,25 @@ class FlowTrainer(TrainerCore):
 
     def __init__(self, flow: HintFlow, lr: float = 0.01 * 3e-2, betas=(0.9, 0.95), eps: float = 1e-4,
                  weight_decay: float = 1.86e-5, grad_clamp: float = 5.0, noise: float = 0.01,
-                 use_graph: bool = True, group=None, use_chain: bool = True, seed: Optional[int] = None):
+                 use_graph: bool = True, group=None, use_chain: bool = True, seed: Optional[int] = None,
+                 learned_perms: bool = False):
         dev = next(flow.parameters()).device
         if dev.type != "cuda":
             raise HintAmdError("FlowTrainer needs the flow on a GPU (no CPU path)")
+        # learned_perms=True: the flow's trainable HouseholderPerms are trained as well (the block-by-block route below)
+        self._lp = self._learned_indices(flow, group) if learned_perms else []
         # model-wide arenas, every block's engine bound to its slice; step state (TrainerCore)
         super().__init__(flow, [blk.tree.engine(dev) for blk in flow.blocks], dev, lr, betas, eps, weight_decay, grad_clamp,
-                         noise, use_graph, group, seed)
+                         noise, use_graph, group, seed, learned_perms=bool(self._lp))
+        self._lp_W = None                       # [m, d * d]: the matrices of the trainable permutations, built by the step's prologue
+        self._lp_ws = {}                        # B -> (workspace of the m boundaries, its bytes)
+        self._grad_hook = None                  # debug: called with the trainer between an un-captured backward pass and the optimizer
+        self._lp_seen = None                    # ... and what that pass saw at the trainable boundaries: [(j, h_(j-1), g(x_j))]
+        if self._lp:
+            # tree levels of every block: the forward launch leaves a block's permuted input in slice levels - 1 of its tape
+            self._levels = [max(depth for _, _, depth in blk.tree._flat_nodes()) + 1 for blk in flow.blocks]
+            m0 = self.perm_mods[0]
+            self._lp_W = torch.empty(len(self._lp), m0.d * m0.d, dtype=torch.float32, device=dev)
         self._loss_single = self.loss_acc      # (step_many points loss_acc at its last iteration's sums)
         # chain handles, the one-launch re-pack and the inference chains (sample()) are the flow's ChainRunner's
         self._runner = flow.runner(dev)
@@ -52,7 +65,7 @@ class FlowTrainer(TrainerCore):
         self._reduced = False                   # the latest backward pass issued the bucket all-reduces itself
         # identical blocks (the configs stack copies of one block) run as ONE forward launch and
         # TWO backward launches for the whole flow (hint_chain_*)
-        self._chainable = use_chain and self._runner.chainable
+        self._chainable = use_chain and self._runner.chainable and not self._lp
         # one chain (handle, tapes, workspaces) per batch size: a captured graph keeps raw pointers into
         # its chain's buffers, so a chain is never destroyed while a graph that used it is alive
         self._chains = {}
@@ -77,6 +90,52 @@ class FlowTrainer(TrainerCore):
             self._chains = {}
         except Exception:
             pass
+
+    @staticmethod
+    def _learned_indices(flow, group):
+        """the blocks of `flow` with a trainable permutation in front, after the checks of learned_perms=True: raises
+        HintAmdError, before anything is launched, for what the route does not do"""
+        who = "FlowTrainer(learned_perms=True)"
+        idx = [i for i in range(flow.n_blocks) if trainable(flow.perms[i])]
+        if not idx:
+            return idx
+        if sum(map(trainable, flow.modules())) != len(idx):
+            raise HintAmdError(f"{who}: the model has trainable Householder permutations outside flow.perms, which no route of "
+                               "the trainer reaches")
+        if dp.world_info(group)[1] > 1:
+            raise HintAmdError(f"{who}: a data-parallel job (world > 1) is not implemented on this route; train learned "
+                               "permutations with one process")
+        if any(node.perm is not None for blk in flow.blocks for node, _, _ in blk.tree._flat_nodes()):
+            raise HintAmdError(f"{who}: reshuffle=True blocks compose their node permutations into the matrix in front of the "
+                               "block on the host, which a trained matrix does not allow; build the flow with reshuffle=False")
+        shapes = sorted({(flow.perms[i].n, flow.perms[i].d) for i in idx})
+        if len(shapes) > 1:
+            raise HintAmdError(f"{who}: n_reflections and d must be the same for every trainable permutation of the flow "
+                               f"(got (n, d) = {shapes}): their matrices and gradients are made in one launch each")
+        return idx
+
+    def _lp_many(self, op: int, B: int = 1, **fields):
+        """one hint_householder_many_run over the trainable permutations on the current stream: Vs and g_V are their slices of P
+        and G, W the trainer's own buffer"""
+        m0, m = self.perm_mods[0], len(self._lp)
+        job = _lib.HouseholderMany()
+        job.op, job.m, job.B, job.d, job.n = op, m, B, m0.d, m0.n
+        job.Vs, job.vs_stride = self.P.data_ptr() + 4 * self.perm_base, self.perm_stride
+        job.W, job.w_stride = self._lp_W.data_ptr(), m0.d * m0.d
+        job.g_V, job.gv_stride = self.G.data_ptr() + 4 * self.perm_base, self.perm_stride
+        if op != _lib.HOUSEHOLDER_MANY_BUILD:
+            ws = self._lp_ws.get(B)
+            if ws is None:
+                nbytes = int(self.lib.hint_householder_many_workspace_bytes(op, m, B, m0.d, m0.n))
+                if nbytes == 0:
+                    _lib.check(1, "hint_householder_many_workspace_bytes")
+                if len(self._lp_ws) >= 8:                  # (ragged batch sizes; a captured graph keeps its own alive: _static)
+                    self._lp_ws.clear()
+                ws = self._lp_ws[B] = (torch.empty(nbytes, dtype=torch.uint8, device=self.device), nbytes)
+            job.workspace, job.workspace_bytes, job.ws_stride = ws[0].data_ptr(), ws[1], ws[1] // (4 * m)
+        for k, v in fields.items():
+            setattr(job, k, v.data_ptr() if isinstance(v, torch.Tensor) else v)
+        _run_desc("hint_householder_many_run", job, self.device)
 
     def _inputs(self, x, c, many: bool = False, what: str = "x"):
         """the input contract of every entry point (hint._as_input): x [B, d] (many: [K, B, d]) and c [B, dc] ([K, B, dc]) as
@@ -205,11 +264,14 @@ class FlowTrainer(TrainerCore):
         # draws from (Philox keyed by rng_state: seed, step counter) - one stream whatever route runs the step
         self._xn = None
         in_kernel = self.noise > 0 and B > 0
-        if in_kernel and self.engines[0].compose_perm(perm_matrix(flow.perms[0]) if flow.has_perm(0) else None) is not None:
+        if in_kernel and (flow.has_perm(0) if self._lp else
+                          self.engines[0].compose_perm(perm_matrix(flow.perms[0]) if flow.has_perm(0) else None) is not None):
             # (a matrix in front of the first block - perm_first / reshuffle=True: the kernel perturbs what it reads behind the
             #  matrix, not x; no launch of its own exists for that, so this one shape keeps torch's generator)
             x = x.add(torch.randn_like(x), alpha=self.noise)
             in_kernel = False
+        if self._lp:
+            return self._fwd_bwd_learned(x, c, in_kernel, with_adam)
         inputs, tapes = [], []
         h, J = x, None
         n = len(self.engines)
@@ -233,6 +295,57 @@ class FlowTrainer(TrainerCore):
                                                -1.0 / B, perm, self.G[a:b], accumulate=True)
         return B
 
+    def _fwd_bwd_learned(self, x: torch.Tensor, c: Optional[torch.Tensor], in_kernel: bool, with_adam: bool):
+        """the block-by-block body with trainable permutations.  Prologue: ONE launch builds every W_j from its P slice.  Forward:
+        the block launches as they are, W_j their fused permutation.  Backward at a trainable boundary j: the block's backward
+        WITHOUT the permutation, on the permuted input x_j its tape holds, gives g(x_j); then g(h_(j-1)) = g(x_j) W_j^T and the
+        slab sums of h_(j-1)^T g(x_j) (hint_householder_many_run, op rows).  Epilogue: ONE launch turns every boundary's slabs
+        into g(Vs_j) in its G slice (op finish).  with_adam: the arena-wide clamp + Adam on the device-side step state."""
+        flow, B, n = self.flow, x.shape[0], len(self.engines)
+        slot = {i: j for j, i in enumerate(self._lp)}
+        if B > 0:
+            self._lp_many(_lib.HOUSEHOLDER_MANY_BUILD)
+        d = flow.ndim_x
+        mats = [self._lp_W[slot[i]].view(d, d) if i in slot else (perm_matrix(flow.perms[i]) if flow.has_perm(i) else None)
+                for i in range(n)]
+        ins, tapes = [], []                    # ins[i]: what stands in front of block i's permutation (h_(i-1); the input for i = 0)
+        h, J = x, None
+        for i, eng in enumerate(self.engines):
+            last = self.loss_acc if i == n - 1 else None
+            if i == 0 and in_kernel:
+                self._xn = torch.empty_like(h)
+                ins.append(self._xn)
+                h, J, tape = eng.forward_chain(h, c, mats[i], J, last, with_tape=True, noise=float(self.noise),
+                                               rng_state=self.rng_state, x_noisy=self._xn)
+            else:
+                ins.append(h)
+                h, J, tape = eng.forward_chain(h, c, mats[i], J, last, with_tape=True)
+            tapes.append(tape)
+        if B == 0:
+            return B
+        seen = [] if self._grad_hook is not None else None
+        g = h                                  # dL/dz = z / B : the scale is applied inside the kernel
+        for i in reversed(range(n)):
+            a, b = self.slices[i]
+            eng = self.engines[i]
+            scale = (1.0 / B) if i == n - 1 else 1.0
+            if i not in slot:
+                g = eng.backward_chain(ins[i] if mats[i] is None else None, tapes[i], c, g, scale, -1.0 / B, mats[i], self.G[a:b],
+                                       accumulate=True)
+                continue
+            L = self._levels[i]
+            xj = tapes[i][(L - 1) * B * d:L * B * d].view(B, d)          # x_j = h_(j-1) W_j, where the forward launch left it
+            gx = eng.backward_chain(xj, tapes[i], c, g, scale, -1.0 / B, None, self.G[a:b], accumulate=True)
+            g = torch.empty_like(gx) if i > 0 else None                  # (nothing stands in front of the input)
+            self._lp_many(_lib.HOUSEHOLDER_MANY_ROWS, B, j=slot[i], x=ins[i], g_y=gx, g_x=g)
+            if seen is not None:
+                seen.append((slot[i], ins[i], gx))
+        self._lp_many(_lib.HOUSEHOLDER_MANY_FINISH, B)
+        self._lp_seen = seen
+        if with_adam:
+            self._adam_dev()
+        return B
+
     def _pack_all(self, step_prologue: bool = False):
         """one launch re-packs every block (ChainRunner.pack_all).  step_prologue: the launch also zeroes the loss sums,
         advances the noise counter and writes Adam's factors of the step."""
@@ -250,6 +363,7 @@ class FlowTrainer(TrainerCore):
             if e.arena is not before or e._regathered:
                 e._regathered = False
                 e.pack()
+        self._bind_perms()
 
     def repack(self):
         """call after changing parameters in place from outside the trainer"""
@@ -277,8 +391,11 @@ class FlowTrainer(TrainerCore):
         if not self.use_graph:
             self._check_arenas()
             self._fwd_bwd(x, c)
+            if self._grad_hook is not None:
+                self._grad_hook(self)
         else:
-            if self._graph is not None and any(e.params[0].data_ptr() != e._ptrs[0] for e in self.engines):
+            if self._graph is not None and (any(e.params[0].data_ptr() != e._ptrs[0] for e in self.engines) or
+                                            any(m.Vs.data_ptr() != self.perm_slice(j).data_ptr() for j, m in enumerate(self.perm_mods))):
                 self._graph = None             # parameters were rebound from outside (p.data = ..., .to()): re-capture
             self._static_for(x, c)
             self._graph.replay()
@@ -597,7 +714,9 @@ class FlowTrainer(TrainerCore):
         # gradient all-reduce, clamp+Adam - is then one graph replay per rank (HINT_GRAPH_ALLREDUCE=0: off)
         self._allreduce_in_graph = self._chainable and dist_on and self.P.is_cuda and \
             torch.distributed.get_backend(self.group) == "nccl" and os.environ.get("HINT_GRAPH_ALLREDUCE", "1") != "0"
-        self._adam_in_graph = self._chainable and ((dp.world_info(self.group)[1] == 1 and not dist_on) or self._allreduce_in_graph)
+        # (trainable permutations: one process by construction, and the block-by-block body issues the optimizer launch itself)
+        self._adam_in_graph = (self._chainable and ((dp.world_info(self.group)[1] == 1 and not dist_on) or self._allreduce_in_graph)) \
+            or (bool(self._lp) and not dist_on)
         if self._allreduce_in_graph:           # communicator set up and used once outside the capture
             warm = torch.zeros(8, dtype=torch.float32, device=self.device)
             torch.distributed.all_reduce(warm, group=self.group)
@@ -620,6 +739,8 @@ class FlowTrainer(TrainerCore):
                 self._fwd_bwd(sx, sc, with_adam=False)
         self._graph = g
         self._static = dict(x=sx, c=sc, xn=self._xn)     # xn: what the captured forward perturbs x into
+        if self._lp:
+            self._static["lp_ws"] = self._lp_ws.get(sx.shape[0])      # (the captured launches hold its address)
 
     @torch.no_grad()
     def sample(self, z: torch.Tensor, c: Optional[torch.Tensor] = None):

@@ -1177,6 +1177,53 @@ size_t hint_householder_workspace_bytes(int32_t op, int32_t B, int32_t d, int32_
 int hint_householder_run(const hint_householder_desc* desc);
 int64_t hint_householder_geometry(int32_t B, int32_t d, int32_t field);
 
+/* The m trainable permutations of one flow at once (FlowTrainer(learned_perms=True), hint_amd/train.py): every one of them has
+ * the same d and n, its Vs, W, g_W, g_V and workspace slot lie a fixed stride of floats behind its predecessor's (the trainer's
+ * arenas), and a training step needs all matrices before its forward pass and all g_V behind its backward pass.  The arithmetic is
+ * hint_householder_run's, from the same device code: every output has the bits m single runs give.
+ *   op build   W_j = H_0 .. H_(n-1) of Vs_j for j = 0 .. m-1: op build of hint_householder_run for each, in ONE launch.
+ *   op rows    permutation j, the boundary in front of block j of the step's backward pass: g_x = g_y W_j^T (g_x may be NULL: not
+ *              computed) and the slab partial tiles of x^T g_y into slot j of the workspace - the apply and Gram launches of a
+ *              single grad run with transpose 0, the same slab geometry (hint_householder_geometry).  At most two launches.
+ *   op finish  for every j: the slabs of slot j added in slab order in double -> g_W_j (g_W may be NULL), then g_(V_j) by the
+ *              recurrence stated above in its order of operations, on W_j and Vs_j as they are now.  ONE launch, one workgroup per
+ *              permutation: the m serial walks over the reflections run side by side.  Every slot must have had its op rows.
+ *   run              stream-ordered on the current device, no host synchronisation, no allocation (capturable), no atomics: two
+ *                    runs give equal bits.  Every byte of each output given is written (build: W_j [d, d]; rows: g_x; finish:
+ *                    g_W_j [d, d], g_V_j [n, d] - the floats between two items of a stride are not touched) and nothing
+ *                    outside them and the workspace.  THE STREAM IS A FIELD OF THE STRUCT, as in hint_householder_desc.
+ *                    Limits: 1 <= m <= 64; d, n, B as for hint_householder_run; a stride is at most 2^30 floats.  Rejects, before
+ *                    any device call and naming the field: a null job; an unknown op; m, d, n outside their limits, B (rows,
+ *                    finish) outside its, j (rows) outside 0..m-1; a required pointer NULL - W for every op, Vs for build and
+ *                    finish, x and g_y for rows, g_V for finish, the workspace for rows and finish; a device pointer not
+ *                    4-byte or the workspace not 16-byte aligned; vs_stride < n d, w_stride < d d, gv_stride < n d, gw_stride
+ *                    < d d (with g_W), ws_stride below a slot's floats or no multiple of 4; a workspace smaller than
+ *                    (m - 1) ws_stride floats and one slot (workspace_bytes says it for dense slots); g_x aliasing g_y.
+ *   workspace_bytes  m dense slots of hint_householder_workspace_bytes(grad, B, d, n) for rows and finish - the dense ws_stride
+ *                    is a quarter of one slot's bytes - and 0 for build, which uses none.  For sizes run would reject: 0 and an
+ *                    error message.  Never decreases with B or m. */
+#define HINT_HOUSEHOLDER_MANY_BUILD 0
+#define HINT_HOUSEHOLDER_MANY_ROWS 1
+#define HINT_HOUSEHOLDER_MANY_FINISH 2
+typedef struct hint_householder_many {
+    int32_t op;                            /* HINT_HOUSEHOLDER_MANY_BUILD / _ROWS / _FINISH */
+    int32_t m;                             /* permutations, 1..64 */
+    int32_t j;                             /* rows: the permutation, 0..m-1 */
+    int32_t B, d, n;
+    const float* Vs; int64_t vs_stride;    /* device float[n, d] of permutation j at Vs + j * vs_stride */
+    float* W; int64_t w_stride;            /* device float[d, d] at W + j * w_stride: written by build, read by rows and finish */
+    const float* x;                        /* rows: device float[B, d], what permutation j was applied to */
+    const float* g_y;                      /* rows: device float[B, d], the gradient of its product */
+    float* g_x;                            /* rows: NULL, or device float[B, d] */
+    float* g_W; int64_t gw_stride;         /* finish: NULL, or device float[d, d] at g_W + j * gw_stride */
+    float* g_V; int64_t gv_stride;         /* finish: device float[n, d] at g_V + j * gv_stride */
+    void* workspace; size_t workspace_bytes;      /* 16-byte aligned; slot j at (float*)workspace + j * ws_stride */
+    int64_t ws_stride;
+    void* stream;                          /* the hipStream_t the launches go to (NULL: the null stream) */
+} hint_householder_many;
+size_t hint_householder_many_workspace_bytes(int32_t op, int32_t m, int32_t B, int32_t d, int32_t n);
+int hint_householder_many_run(const hint_householder_many* job);
+
 /* Device-resident epochs: what stands between a resident table x [n_rows, d] (y [n_rows, dy]) and the training step - the
  * reference's DataLoader(TensorDataset(...), shuffle=True, drop_last=True) (data.py:484-487, :503-506: one __getitem__ per row and a
  * collate on the host) and the statistics of load_data_normalised (data.py:337-339).
